@@ -9,12 +9,16 @@ weights / prompt embeddings / rectangle masks (no checkpoints exist offline).  `
 configs[2], the north-star headline: merged per-row LoRA weights, --t_stop 0.8) or `--kind custom` (configs[1]); with the
 default `--kind both` the line's `value` is the LoRA figure and `other_configs.custom` carries configs[1].
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 without a launcher: the script starts its own N ranks (tweediemix_amd/launch.py; one process per GPU, RCCL); under
-`python -m torch.distributed.run` it uses the ranks it is given.  Rank 0 prints ONE JSON line: the contract fields plus
-`roofline` (timed IN SITU: every GEMM / conv / attention / GroupNorm launch of the captured step records its own
-start / end on the device clock while the graph replays), `images_per_s` (whole 50-step trajectories incl. the VAE
-decode, all ranks), `parity_check` and, at N = 1, `cpu_baseline`.
+`python -m torch.distributed.run` it uses the ranks it is given.  Rank 0 prints ONE JSON line with the contract fields.
+A plain run builds the plan, replays the headline step untimed for a few seconds (the chip settles), runs W warm-up and
+K timed steps and prints the line: nothing else.
+`--full` adds every other measurement and check: `roofline` (timed IN SITU: every GEMM / conv / attention / GroupNorm
+launch of the captured step records its own start / end on the device clock while the graph replays), `images_per_s`
+(whole 50-step trajectories incl. the VAE decode, all ranks), `parity_check`, the other configs (Custom-Diffusion, fp8,
+video) and, at N = 1, `cpu_baseline`; its `value` is the same W + K steps timed again at the end of that run.
+`--dump-outputs DIR` writes what the last timed step left on rank 0 (latent.npy, x0.npy, eps.npy; float32).
 """
 import argparse
 import json
@@ -68,6 +72,10 @@ def parse(argv=None):
     ap.add_argument("--cpu-threads", type=int, default=64)
     ap.add_argument("--host-dry-run", action="store_true",
                     help="launcher / collective control flow only, on CPU over gloo with a stand-in step (tests; NOT a bench line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement and check (parity, in-situ roofline, trajectories, other configs, CPU baseline)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -109,8 +117,12 @@ def fusion_timesteps(tw):
     return [t for t in tw.scheduler.timesteps if t <= tw.t_cond_cur and t in tw._window]
 
 
-def timed_fusion_steps(tw, args, world, device, x):
-    """W warm-up + K timed fusion steps (barrier + synchronize on both sides).  Returns (seconds, final latent).
+SETTLE_S = 5.0      # untimed load ahead of a plain run's window: the chip holds its sustained clock after ~3 s of it (DESIGN.md section 6)
+
+
+def timed_fusion_steps(tw, args, world, device, x, settle_s=0.0):
+    """[settle_s seconds of untimed steps +] W warm-up + K timed fusion steps (barrier + synchronize on both sides).  Returns (seconds, {name: tensor}):
+    copies of what the last step left -- the next latent, its Tweedie estimate x0 and the UNet output eps it was built from.
     The steps walk the fusion window's timesteps in order; when the walk wraps around to the window's first timestep the latent is re-seeded from `x`
     (one 4*h*w-float device copy per pass through the window), so every step sees a latent of the scale its timestep has in a trajectory."""
     from tweediemix_amd import lib as L
@@ -123,6 +135,10 @@ def timed_fusion_steps(tw, args, world, device, x):
         t = ts[i % len(ts)]
         tw._run_step("fusion", L.STEP_FUSION, t, tw.alpha(t), tw.alpha(t - tw.skip))
 
+    t_end, i = time.perf_counter() + settle_s, 0
+    while time.perf_counter() < t_end:          # step(0) below re-seeds the latent: the settling steps leave no trace in the outputs
+        step(i)
+        i += 1
     for i in range(max(args.warmup, 2)):        # the first call builds the plan, the second captures the graph
         step(i)
     torch.cuda.synchronize()
@@ -140,7 +156,24 @@ def timed_fusion_steps(tw, args, world, device, x):
     dt = time.perf_counter() - t0
     assert torch.isfinite(tw.x_state).all()
     tw.last_window_max_abs_latent = float(tw.x_state.abs().max())
-    return dt, tw.x_state.clone()
+    return dt, {"latent": tw.x_state.clone(), "x0": tw.x0_state.clone(), "eps": tw.plan("fusion").eps.clone()}
+
+
+DUMP_CAP_BYTES = 60 << 20          # under 64 MB in decimal units too, .npy headers included
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  Should they exceed DUMP_CAP_BYTES together, each is replaced by
+    the same fixed, seeded sample of its flattened elements (a share of it in proportion to the cap), so two runs stay comparable."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_CAP_BYTES:
+            idx = np.random.RandomState(0).choice(a.size, int(a.size * DUMP_CAP_BYTES / total), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def chip_state_under_load(tw, device, x, n_steps=40, samples=4):
@@ -656,95 +689,127 @@ def main(argv=None):
     plan_build_s = time.perf_counter() - t_start - startup_s
     x = torch.randn(S_, 4, tw.h, tw.w, generator=torch.Generator().manual_seed(1000 + rank)).to(device)
     cdev = torch.device("cpu") if backend == "gloo" else device
-    # the FIRST window: W warm-up + K timed steps right behind the plan build -- what rounds 1-4 reported as `value`.  This chip needs ~3 s of load (~100 steps) to
-    # reach the state it then holds (tools/step_gap.py, same process, same graph: 31.2 -> 30.4 -> 28.6 -> 28.6 ms per step over consecutive 50-step windows; the
-    # 32-byte parameter upload and the replay-to-replay gap cost nothing: upload + replay 28.56, replay only 28.55, one replay behind a synchronize 28.56), and a
-    # denoising trajectory is 75 UNet calls = 2 s long.  So the line's `value` is the SAME measurement (W untimed + exactly K timed steps, barrier + synchronize on both
-    # sides, MAX over ranks) taken once more at the END of the run, behind the parity check, the in-situ profile and the trajectory measurement -- the sustained state;
-    # the first window stays in the line as `first_window`.
-    dt_first, _x = timed_fusion_steps(tw, args, world, device, x)
+    # the FIRST window: W warm-up + K timed steps right behind the plan build (what rounds 1-4 reported as `value`).  A plain run puts SETTLE_S seconds of untimed
+    # replays of the same step in front of it, so that its `value` is the chip's sustained state, as the end-of-run window of --full is (see there).
+    dt_first, outputs = timed_fusion_steps(tw, args, world, device, x, settle_s=0.0 if args.full else SETTLE_S)
     dt_first = D.max_over_ranks(dt_first, cdev)                                         # through the group also at N = 1
-    check = parity_check(tw, args, parts, primary, device)
-    prof = insitu_profile(tw) if rank == 0 else None
-    traj = None if args.no_trajectory else run_trajectories(tw, args, rank, world, device)
-    dt, _x = timed_fusion_steps(tw, args, world, device, x)
-    dt = D.max_over_ranks(dt, cdev)
-    max_abs_latent = tw.last_window_max_abs_latent
-    chip = chip_state_under_load(tw, device, x) if rank == 0 else None
-    # the same window once more on the OTHER synthetic mask kind, same process, same graph (the masks live at a fixed address the captured step reads), chip state
-    # beside it: rounds 1-5 timed intersecting rectangles, on which the un-normalised blend doubles the overlap region every fusion step
-    other_kind = "overlap" if args.masks == "partition" else "partition"
-    tw.masks = tw.mask_sets(other_kind)
-    dt_o, _xo = timed_fusion_steps(tw, args, world, device, x)
-    dt_o = D.max_over_ranks(dt_o, cdev)
-    other_masks = {"masks": other_kind, "ms_per_step": 1e3 * dt_o / (args.steps * args.seeds_per_gpu), "value": world * args.seeds_per_gpu * args.steps / dt_o,
-                   "max_abs_latent_at_end_of_window": tw.last_window_max_abs_latent,
-                   "chip_state_under_load": chip_state_under_load(tw, device, x) if rank == 0 else None,
-                   "what": "the same W + K steps, same captured graph, right behind the `value` window, with the other synthetic mask kind"}
-    tw.masks = tw.mask_sets()
+    dt, max_abs_latent, flops_step = dt_first, tw.last_window_max_abs_latent, plan.flops
+    full_line, full_config = {}, {"value_window": f"W + K steps behind {SETTLE_S:g} s of untimed replays of the same step (sustained state)"}
+    if args.full:
+        # This chip needs ~3 s of load (~100 steps) to reach the state it then holds (tools/step_gap.py, same process, same graph: 31.2 -> 30.4 -> 28.6 -> 28.6 ms per
+        # step over consecutive 50-step windows; the 32-byte parameter upload and the replay-to-replay gap cost nothing: upload + replay 28.56, replay only 28.55, one
+        # replay behind a synchronize 28.56), and a denoising trajectory is 75 UNet calls = 2 s long.  So --full's `value` is the SAME measurement (W untimed + exactly
+        # K timed steps, barrier + synchronize on both sides, MAX over ranks) taken once more at the END of the run, behind the parity check, the in-situ profile and
+        # the trajectory measurement -- the sustained state; the first window stays in the line as `first_window`.
+        check = parity_check(tw, args, parts, primary, device)
+        prof = insitu_profile(tw) if rank == 0 else None
+        traj = None if args.no_trajectory else run_trajectories(tw, args, rank, world, device)
+        dt, outputs = timed_fusion_steps(tw, args, world, device, x)
+        dt = D.max_over_ranks(dt, cdev)
+        max_abs_latent = tw.last_window_max_abs_latent
+        chip = chip_state_under_load(tw, device, x) if rank == 0 else None
+        # the same window once more on the OTHER synthetic mask kind, same process, same graph (the masks live at a fixed address the captured step reads), chip state
+        # beside it: rounds 1-5 timed intersecting rectangles, on which the un-normalised blend doubles the overlap region every fusion step
+        other_kind = "overlap" if args.masks == "partition" else "partition"
+        tw.masks = tw.mask_sets(other_kind)
+        dt_o, _xo = timed_fusion_steps(tw, args, world, device, x)
+        dt_o = D.max_over_ranks(dt_o, cdev)
+        other_masks = {"masks": other_kind, "ms_per_step": 1e3 * dt_o / (args.steps * args.seeds_per_gpu), "value": world * args.seeds_per_gpu * args.steps / dt_o,
+                       "max_abs_latent_at_end_of_window": tw.last_window_max_abs_latent,
+                       "chip_state_under_load": chip_state_under_load(tw, device, x) if rank == 0 else None,
+                       "what": "the same W + K steps, same captured graph, right behind the `value` window, with the other synthetic mask kind"}
+        tw.masks = tw.mask_sets()
 
-    other = {}
-    if args.kind == "both" and world == 1:
         alg = gemm_alg_bytes(plan)
         conv_alg = conv_alg_bytes(plan)
-        flops_step = plan.flops
-        del tw, plan
-        torch.cuda.empty_cache()
-        tw2, _parts2 = build_sampler(args, "custom", device, seed=rank)
-        dt2, _ = timed_fusion_steps(tw2, args, world, device, x)
-        other["custom"] = {"workload": "BASELINE configs[1]: Custom-Diffusion K/V deltas", "value": S_ * args.steps / dt2, "unit": "steps/s",
-                           "ms_per_step": 1e3 * dt2 / (args.steps * S_), "parity_check": parity_check(tw2, args, _parts2, "custom", device)}
-        del tw2
-        torch.cuda.empty_cache()
-        if args.dtype == "bf16" and not args.tiny:
-            tw3, _parts3 = build_sampler(args, primary, device, seed=rank, fp8=True)
-            dt3, _ = timed_fusion_steps(tw3, args, world, device, x)
-            other["fp8"] = {"workload": f"{primary} deltas; every projection of every transformer block (attn1 q/k/v, both attention out-projections, attn2 to_q, FF1, "
-                                        "FF2: 420 of the 442 GEMM launches) on e4m3 operands with power-of-two scales (tmix_gemm_fp8); no quantiser launch inside a block: "
-                                        "the GEMMs that write the residual stream and the attention kernels (tmix_attn_fwd_f8) leave e4m3 + MX-block copies, FF1 -> FF2 "
-                                        "chained through the GEGLU epilogue; the ResnetBlock2D convolutions whose K-tile can be 128 channels of one tap and that carry no shortcut taps "
-                                        "(15 of 38) on e4m3 as well (tmix_conv3x3_nhwc_fp8 behind tmix_groupnorm_nhwc_pre_f8); proj_in / proj_out, the other convolutions and the "
-                                        "attention inner products stay bf16",
-                            "dtype": "fp8", "value": S_ * args.steps / dt3, "unit": "steps/s", "ms_per_step": 1e3 * dt3 / (args.steps * S_),
-                            "parity_check": parity_check(tw3, args, _parts3, primary, device)}
-            if rank == 0:
-                other["fp8"]["roofline"] = fp8_roofline(insitu_profile(tw3))
-            if not args.no_trajectory:                 # the same whole-trajectory / images-per-second measurement on the fp8 plans (every call kind: B = K+1 and B = 2)
-                tr8 = run_trajectories(tw3, args, rank, world, device)
-                other["fp8"].update({"trajectory_steps_per_s": tr8["trajectory_steps_per_s"], "images_per_s": tr8["images_per_s"],
-                                     "single_image_seconds_loop": tr8["single_image"]["seconds_loop"], "cobatch": tr8["cobatch"]})
-            del tw3
+        other = {}
+        if args.kind == "both" and world == 1:
+            del tw, plan
             torch.cuda.empty_cache()
-        if not args.tiny and not args.no_video:
-            other["video"] = video_step_bench()
-    else:
-        alg = gemm_alg_bytes(plan)
-        conv_alg = conv_alg_bytes(plan)
-        flops_step = plan.flops
+            tw2, _parts2 = build_sampler(args, "custom", device, seed=rank)
+            dt2, _ = timed_fusion_steps(tw2, args, world, device, x)
+            other["custom"] = {"workload": "BASELINE configs[1]: Custom-Diffusion K/V deltas", "value": S_ * args.steps / dt2, "unit": "steps/s",
+                               "ms_per_step": 1e3 * dt2 / (args.steps * S_), "parity_check": parity_check(tw2, args, _parts2, "custom", device)}
+            del tw2
+            torch.cuda.empty_cache()
+            if args.dtype == "bf16" and not args.tiny:
+                tw3, _parts3 = build_sampler(args, primary, device, seed=rank, fp8=True)
+                dt3, _ = timed_fusion_steps(tw3, args, world, device, x)
+                other["fp8"] = {"workload": f"{primary} deltas; every projection of every transformer block (attn1 q/k/v, both attention out-projections, attn2 to_q, FF1, "
+                                            "FF2: 420 of the 442 GEMM launches) on e4m3 operands with power-of-two scales (tmix_gemm_fp8); no quantiser launch inside a block: "
+                                            "the GEMMs that write the residual stream and the attention kernels (tmix_attn_fwd_f8) leave e4m3 + MX-block copies, FF1 -> FF2 "
+                                            "chained through the GEGLU epilogue; the ResnetBlock2D convolutions whose K-tile can be 128 channels of one tap and that carry no shortcut taps "
+                                            "(15 of 38) on e4m3 as well (tmix_conv3x3_nhwc_fp8 behind tmix_groupnorm_nhwc_pre_f8); proj_in / proj_out, the other convolutions and the "
+                                            "attention inner products stay bf16",
+                                "dtype": "fp8", "value": S_ * args.steps / dt3, "unit": "steps/s", "ms_per_step": 1e3 * dt3 / (args.steps * S_),
+                                "parity_check": parity_check(tw3, args, _parts3, primary, device)}
+                if rank == 0:
+                    other["fp8"]["roofline"] = fp8_roofline(insitu_profile(tw3))
+                if not args.no_trajectory:                 # the same whole-trajectory / images-per-second measurement on the fp8 plans (every call kind: B = K+1 and B = 2)
+                    tr8 = run_trajectories(tw3, args, rank, world, device)
+                    other["fp8"].update({"trajectory_steps_per_s": tr8["trajectory_steps_per_s"], "images_per_s": tr8["images_per_s"],
+                                         "single_image_seconds_loop": tr8["single_image"]["seconds_loop"], "cobatch": tr8["cobatch"]})
+                del tw3
+                torch.cuda.empty_cache()
+            if not args.tiny and not args.no_video:
+                other["video"] = video_step_bench()
+
+        if rank == 0:
+            g = prof["gemm"] if args.dtype == "bf16" or "gemm_fp8" not in prof else prof["gemm_fp8"]
+            peak_tf = BF16_DENSE_PEAK_TFLOPS if g is prof.get("gemm") else FP8_DENSE_PEAK_TFLOPS
+            pmc = pmc_evidence()
+            full_config = {"value_window": "end of run (sustained state); first_window_ms_per_step = the same W + K steps right behind the plan build (what rounds 1-4 reported)",
+                           "first_window_ms_per_step": 1e3 * dt_first / (args.steps * S_),
+                           "other_mask_kind_ms_per_step": other_masks["ms_per_step"]}
+            full_line = {
+                "first_window": {"ms_per_step": 1e3 * dt_first / (args.steps * S_), "value": world * S_ * args.steps / dt_first,
+                                 "what": "the same W + K steps timed right behind the plan build (rounds 1-4 reported this window); `value` is the window at the end of the "
+                                         "run, after >= 3 s of load (parity check, in-situ profile, trajectories): the state the chip holds through a 2 s trajectory"},
+                "chip_state_under_load": chip,
+                "other_mask_kind_window": other_masks,
+                "parity_check": check,
+                "roofline": {"bound": "mfma", "kernel": "gemm_conv_kernel<..,CONV=0> (tmix_gemm_bf16)" if g is prof.get("gemm") else "gemm_conv_kernel<..,PH=2|3> (tmix_gemm_fp8)",
+                             "achieved": g["tflops"], "peak": peak_tf, "unit": "TFLOP/s", "frac": g["tflops"] / peak_tf,
+                             "traffic": pmc[0],
+                             "traffic_source": "NOT measured in this run: read from the committed rocprofv3 PMC passes named in profiles/MANIFEST.json (the builder's box, same command; "
+                                               "counters cannot be read from inside the process) -- see pmc.files",
+                             "pmc": pmc[1], "algorithmic_bytes_per_launch": alg,
+                             "how": "achieved = sum(2MNK of the step's GEMM launches, plus the 4*M*77*N attention flops of the one-launch attn2 -- tmix_gemm_q_cross_attn -- which that launch performs) / sum(their durations), each launch timed on the device clock "
+                                    "INSIDE the captured step while the graph replays (concurrent chains included, so the sum can exceed the wall time)",
+                             "launches_per_step": g["launches"], "avg_launch_us": g["avg_launch_us"], "flops_per_step": g["flops"],
+                             "launches_per_step_all_classes": prof["launches_total"], "kernel_boundaries_ms": prof["boundaries_ms"],
+                             "conv": {"traffic": (pmc[1].get("traffic_bytes_per_launch_by_class") or {}).get("conv"),
+                                      "algorithmic_bytes_per_launch": conv_alg, "achieved": (prof.get("conv") or {}).get("tflops")},
+                             "graph_replay_ms": prof["replay_ms"], "uninstrumented_graph_replay_ms": prof["uninstrumented_replay_ms"],
+                             "instrumented_busy_ms": prof["instrumented_busy_ms"],
+                             "classes": {k: {kk: v[kk] for kk in ("launches", "sum_launch_ms", "busy_ms", "avg_launch_us", "tflops")}
+                                         for k, v in prof.items() if isinstance(v, dict)}},
+            }
+            if traj is not None:
+                full_line["images_per_s"] = traj["images_per_s"]
+                full_line["vae_decode_ms"] = traj["vae_decode_ms"]
+                full_line["trajectory_steps_per_s"] = traj["trajectory_steps_per_s"]
+                full_line["trajectory"] = traj
+            if other:
+                full_line["other_configs"] = other
+            if world == 1 and not args.no_cpu_baseline:
+                full_line["cpu_baseline"] = cpu_baseline(args, parts)
 
     if rank == 0:
-        g = prof["gemm"] if args.dtype == "bf16" or "gemm_fp8" not in prof else prof["gemm_fp8"]
-        peak_tf = BF16_DENSE_PEAK_TFLOPS if g is prof.get("gemm") else FP8_DENSE_PEAK_TFLOPS
-        pmc = pmc_evidence()
+        if args.dump_outputs:
+            dump_outputs(outputs, args.dump_outputs)
         line = {
             "metric": METRIC, "value": world * S_ * args.steps / dt, "unit": "steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * dt / (args.steps * S_), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "first_window": {"ms_per_step": 1e3 * dt_first / (args.steps * S_), "value": world * S_ * args.steps / dt_first,
-                             "what": "the same W + K steps timed right behind the plan build (rounds 1-4 reported this window); `value` is the window at the end of the "
-                                     "run, after >= 3 s of load (parity check, in-situ profile, trajectories): the state the chip holds through a 2 s trajectory"},
-            "chip_state_under_load": chip,
             "max_abs_latent_at_end_of_window": max_abs_latent,
-            "other_mask_kind_window": other_masks,
             "config": {"workload": f"SDXL-base UNet shapes, {args.res}x{args.res}, K=3 concepts ({primary} deltas"
                                    + (", --t_stop 0.8 window" if primary == "lora" else "") + "), "
                                    f"fusion-phase step = UNet B={K + 1} + fused Tweedie/CFG/blend/DDIM kernel, one hipGraph per step"
                                    + (" [TINY DEBUG CONFIG]" if args.tiny else ""),
                        "masks": f"{args.masks}: synthetic rectangles " + ("that partition the image (fg_1 + fg_2 + bg = 1 on every pixel)" if args.masks == "partition"
                                                                             else "that may intersect (un-normalised blend weights sum to 2 on the overlap)"),
-                       "value_window": "end of run (sustained state); first_window_ms_per_step = the same W + K steps right behind the plan build (what rounds 1-4 reported)",
-                       "first_window_ms_per_step": 1e3 * dt_first / (args.steps * S_),
-                       "other_mask_kind_ms_per_step": other_masks["ms_per_step"],
+                       **full_config,
                        "seeds_per_gpu": S_, "streams": args.streams, "hip_graph": not args.no_graphs,
                        "parallelism": f"replicas x{world} (seed-sharded, no data-path collective)", "tilings": tilings},
             "dist": {"backend": backend + (" (RCCL)" if backend == "nccl" else ""), "world_size": world, "ranks_seen": ranks_seen,
@@ -755,33 +820,8 @@ def main(argv=None):
                                      "concurrently, each on its own device: no shared host-side stage)"},
             "unet_tflop_per_step": flops_step / 1e12 / S_,
             "achieved_tflops_whole_step": flops_step / 1e12 / (dt / args.steps),
-            "parity_check": check,
-            "roofline": {"bound": "mfma", "kernel": "gemm_conv_kernel<..,CONV=0> (tmix_gemm_bf16)" if g is prof.get("gemm") else "gemm_conv_kernel<..,PH=2|3> (tmix_gemm_fp8)",
-                         "achieved": g["tflops"], "peak": peak_tf, "unit": "TFLOP/s", "frac": g["tflops"] / peak_tf,
-                         "traffic": pmc[0],
-                         "traffic_source": "NOT measured in this run: read from the committed rocprofv3 PMC passes named in profiles/MANIFEST.json (the builder's box, same command; "
-                                           "counters cannot be read from inside the process) -- see pmc.files",
-                         "pmc": pmc[1], "algorithmic_bytes_per_launch": alg,
-                         "how": "achieved = sum(2MNK of the step's GEMM launches, plus the 4*M*77*N attention flops of the one-launch attn2 -- tmix_gemm_q_cross_attn -- which that launch performs) / sum(their durations), each launch timed on the device clock "
-                                "INSIDE the captured step while the graph replays (concurrent chains included, so the sum can exceed the wall time)",
-                         "launches_per_step": g["launches"], "avg_launch_us": g["avg_launch_us"], "flops_per_step": g["flops"],
-                         "launches_per_step_all_classes": prof["launches_total"], "kernel_boundaries_ms": prof["boundaries_ms"],
-                         "conv": {"traffic": (pmc[1].get("traffic_bytes_per_launch_by_class") or {}).get("conv"),
-                                  "algorithmic_bytes_per_launch": conv_alg, "achieved": (prof.get("conv") or {}).get("tflops")},
-                         "graph_replay_ms": prof["replay_ms"], "uninstrumented_graph_replay_ms": prof["uninstrumented_replay_ms"],
-                         "instrumented_busy_ms": prof["instrumented_busy_ms"],
-                         "classes": {k: {kk: v[kk] for kk in ("launches", "sum_launch_ms", "busy_ms", "avg_launch_us", "tflops")}
-                                     for k, v in prof.items() if isinstance(v, dict)}},
+            **full_line,
         }
-        if traj is not None:
-            line["images_per_s"] = traj["images_per_s"]
-            line["vae_decode_ms"] = traj["vae_decode_ms"]
-            line["trajectory_steps_per_s"] = traj["trajectory_steps_per_s"]
-            line["trajectory"] = traj
-        if other:
-            line["other_configs"] = other
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args, parts)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if dist.is_initialized():
         dist.destroy_process_group()

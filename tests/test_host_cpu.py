@@ -356,3 +356,21 @@ def test_weight_hint_policy_caps_large_tensors_of_single_seed_calls_only(monkeyp
     monkeypatch.setenv("TMIX_PF_CAP_MB", "1.5"); monkeypatch.setenv("TMIX_PF_CAP_OVER_MB", "12")
     cap, over = U.hint_policy(32, 128, 128)
     assert (cap, over) == (3 * MB // 2, 12 * MB) and U.hint_bytes(13 * MB, cap, over) == 3 * MB // 2
+
+
+def test_bench_dump_outputs_are_float32_and_a_fixed_sample_under_the_cap(tmp_path):
+    """bench.py --dump-outputs: arrays under the cap are written whole as float32; larger ones as the same seeded sample every time, under 64 MB in all."""
+    import bench
+    small = {"latent": torch.randn(2, 4, 8, 8), "eps": torch.randn(8, 4, 8, 8, dtype=torch.bfloat16)}
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    for n, t in small.items():
+        a = np.load(tmp_path / "small" / f"{n}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy())
+    big = {"latent": torch.randn(4, 4, 64, 64), "eps": torch.randn(20000, 1024)}
+    for run in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / run))
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in big) <= 64e6
+    for n, t in big.items():
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < t.numel() and np.array_equal(a, b)
+        assert np.isin(a, t.numpy().reshape(-1)).all()

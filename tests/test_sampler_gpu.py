@@ -349,13 +349,13 @@ def test_cli_sd_path_prompts_to_png(tmp_path, golden_dir):
 
 
 def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline` (tiny network, 2 steps)."""
+    """bench.py --full prints ONE JSON line with the driver's keys plus `roofline` and `cpu_baseline` (tiny network, 2 steps)."""
     need_gpu()
     import json, subprocess, sys
     import os as _os
     root = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, _os.path.join(root, "bench.py"), "--tiny", "--res", "256", "--steps", "2", "--warmup", "1",
-                        "--cpu-threads", "8"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--cpu-threads", "8", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads(lines[0])
@@ -377,6 +377,33 @@ def test_bench_line_contract(tmp_path):
     assert cfgd["masks"].startswith("partition") and cfgd["first_window_ms_per_step"] > 0 and cfgd["other_mask_kind_ms_per_step"] > 0
     assert d["other_mask_kind_window"]["masks"] == "overlap" and d["max_abs_latent_at_end_of_window"] < 1e3
     assert "profiles/MANIFEST.json" in rf["traffic_source"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """a plain bench.py run prints the contract line without the --full measurements, and --dump-outputs writes the last timed step's
+    latent / x0 / eps as float32; two runs with the same arguments write the same arrays (tiling pinned: the tiny shapes are not in the table)."""
+    need_gpu()
+    import json, subprocess, sys
+    import os as _os
+    root = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
+    env = dict(_os.environ, TMIX_FORCE_TILE="1")
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, _os.path.join(root, "bench.py"), "--tiny", "--res", "256", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "config"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert not set(d) & {"roofline", "parity_check", "trajectory", "other_configs", "cpu_baseline", "first_window"}
+        dumps.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("latent", "x0", "eps")})
+    a, b = dumps
+    assert a["latent"].shape == a["x0"].shape == (1, 4, 32, 32) and a["eps"].shape == (4, 4, 32, 32)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all() and np.abs(a[n]).max() > 0
+        assert np.array_equal(a[n], b[n]), n
 
 
 def test_bench_two_ranks_control_flow(tmp_path):
@@ -412,7 +439,7 @@ def test_bench_gpus2_self_launch_sharded_seeds(tmp_path):
     env = {k: v for k, v in _os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["TMIX_SINGLE_GPU_DIST_TEST"] = "1"
     r = subprocess.run([sys.executable, _os.path.join(root, "bench.py"), "--gpus", "2", "--tiny", "--res", "256", "--steps", "2", "--warmup", "1",
-                        "--num-seeds", "3", "--kind", "custom"], capture_output=True, text=True, timeout=1200, cwd=root, env=env)
+                        "--num-seeds", "3", "--kind", "custom", "--full"], capture_output=True, text=True, timeout=1200, cwd=root, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads(lines[0])

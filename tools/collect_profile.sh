@@ -5,7 +5,7 @@
 tag=${1:-r1}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
-BARGS="--kind lora --no-trajectory --no-cpu-baseline --no-video ${BENCH_EXTRA:-}"
+BARGS="--full --kind lora --no-trajectory --no-cpu-baseline --no-video ${BENCH_EXTRA:-}"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ${tag} -- python bench.py $BARGS > $out/${tag}_bench_line.json 2> $out/bench.log
 # the fp8 plan (--dtype fp8: attn1 q/k/v, attn2 to_q and both FF projections on e4m3 operands) under the same kernel trace
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ${tag}_fp8 -- python bench.py --dtype fp8 $BARGS > $out/${tag}_fp8_bench_line.json 2> $out/bench_fp8.log

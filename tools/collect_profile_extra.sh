@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/prof_$tag; mkdir -p $out
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ${tag}_video -- python tools/video_bench.py --steps 10 > $out/${tag}_video_bench_line.json 2> $out/video.log
 timeout 900 rocprofv3 --pmc MfmaUtil --kernel-trace --output-format csv -d $out -o ${tag}_video_MFMA -- python tools/video_bench.py --steps 2 --warmup 1 > $out/pmc_video_MFMA.log 2>&1
-timeout 900 rocprofv3 --pmc MfmaUtil --kernel-trace --output-format csv -d $out -o ${tag}_fp8_MFMA -- python bench.py --dtype fp8 --steps 2 --warmup 1 --no-graphs --kind lora --no-trajectory --no-cpu-baseline --no-video > $out/pmc_fp8_MFMA.log 2>&1
+timeout 900 rocprofv3 --pmc MfmaUtil --kernel-trace --output-format csv -d $out -o ${tag}_fp8_MFMA -- python bench.py --full --dtype fp8 --steps 2 --warmup 1 --no-graphs --kind lora --no-trajectory --no-cpu-baseline --no-video > $out/pmc_fp8_MFMA.log 2>&1
 python - $out $tag <<'PY'
 import csv, sys, json, collections, re
 out, tag = sys.argv[1], sys.argv[2]
