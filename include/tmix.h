@@ -92,6 +92,21 @@ int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float*
  *   out = sa_next x0 + s1_next eps.  TMIX_F16 rounds after every binary op like the reference's fp16 tensors. */
 int tmix_vpred_step(const void* x, const void* v, void* out, int dtype, int64_t n, float g,
                     float sa, float s1, float sa_next, float s1_next, void* stream);
+/* Batched video step (S videos in one UNet call; tweediemix_amd.video.VideoSampler).  Both read the device parameter buffer
+ * params = {t, sa, s1, sa_next, s1_next, g, ...} (fp32), so ONE captured launch serves every timestep of a graph replay.
+ * The state x is fp32 in the pipeline layout [videos][channels][frames][hw].  A CFG half (u = unconditional, c = text) is a plan
+ * buffer of per-frame rows [(clip*frames + f)][row channels][hw] whose clip s starts at s * clip_stride floats: two chains of
+ * `videos` clips each, or one plan of 2*videos clips with the text half's base pointer at clip `videos`.
+ * tmix_video_step_prologue: x -> channels [0, channels) of both halves' input rows (row_channels per row; the image-latent
+ *   channels [channels, row_channels) are never written), t_u[0..videos) = t_c[0..videos) = params[0].
+ * tmix_vpred_step_dev: x <- tmix_vpred_step(x, [v_u; v_c]) (TMIX_F32) element for element, in place, with v_u / v_c read from the
+ *   halves' prediction rows ([(clip*frames + f)][channels][hw]) -- bit-identical to that kernel on the same video.
+ * Both: TMIX_EINVAL on a null pointer, TMIX_ESHAPE on an empty shape or a clip stride shorter than one clip. */
+int tmix_video_step_prologue(const float* x, float* x_u, int64_t clip_stride_u, float* t_u, float* x_c, int64_t clip_stride_c,
+                             float* t_c, const float* params, int videos, int channels, int frames, int64_t hw, int row_channels,
+                             void* stream);
+int tmix_vpred_step_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
+                        const float* params, int videos, int channels, int frames, int64_t hw, void* stream);
 /* First-frame feature injection of the patched ResnetBlock2D.forward (video_gen/utils_attn.py:433-455), in place on
  * x [clips][frames][per_frame]: frames 1.. <- frame 0 (hard) or interp*frame0 + one_minus_interp*frame. */
 int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,

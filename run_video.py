@@ -14,7 +14,17 @@ with the reference's values as defaults, and the model comes from local files:
 
 Per step: native UNet forward on the CFG pair (tweediemix_amd/i2vgen.py) with the first-frame feature injection of
 video_gen/utils_attn.py:389-474 for the first int(steps * injection_timestep) steps, then the fused CFG / v-prediction /
-DDIM update (tmix_vpred_step).  Output: output_i2v_seed_<seed>.latent.pt, plus output_i2v_seed_<seed>.gif with --vae_path."""
+DDIM update (tmix_vpred_step).  Output: output_i2v_seed_<seed>.latent.pt, plus output_i2v_seed_<seed>.gif with --vae_path.
+
+Many videos per run (a video is one (image, seed) pair; the videos are the images x seeds, image-major):
+  --image_path a.png+b.png  several images ('+'-separated); outputs are then named <image stem>_seed_<seed>.*
+  --num_seeds N             seeds seed .. seed+N-1; video (image i, seed s) is exactly the single run `--image_path i --seed s`
+  --seeds_per_batch K       videos that share every UNet call (0: all of this rank's videos, at most 4; a ragged last batch is padded)
+  --gpus G                  videos sharded round-robin over G GPUs (one process per GPU, started by this script); latents (and
+                            decoded frames) are gathered over RCCL and rank 0 writes every file
+  --output_dir D            where the files go (default .)
+Such runs go through tweediemix_amd.video.VideoSampler: the whole step of S videos on the device (tmix_video_step_prologue ->
+both CFG chains -> tmix_vpred_step_dev), one parameter upload and one graph replay per timestep; frames are decoded in batches."""
 import argparse
 import os
 import sys
@@ -52,73 +62,138 @@ def build_parser():
     p.add_argument("--tiny", action="store_true", help="tiny network (smoke tests)")
     p.add_argument("--no_graphs", action="store_true")
     p.add_argument("--streams", type=int, default=2, choices=[1, 2], help="2: the two clips of the CFG pair run as two launch chains")
+    # many videos per run
+    p.add_argument("--num_seeds", type=int, default=1, help="videos per image: seeds seed..seed+n-1")
+    p.add_argument("--seeds_per_batch", type=int, default=0, help="videos co-batched into every UNet call (0: all of this rank's videos, at most 4)")
+    p.add_argument("--gpus", type=int, default=1, help="shard the videos over this many GPUs (one process per GPU, started by this script; at most 8)")
+    p.add_argument("--output_dir", default=".")
     return p
 
 
-def native_conditioning(opt, gen, have):
-    """what I2VGenXLPipeline.__call__ computes before its loop (video_gen/pipeline_i2vgen_xl.py:604-639), from the checkpoint's
-    tokenizer/ + text_encoder/ (prompt embeddings), image_encoder/ (CLIP image embedding) and vae/ (image latents); entries
-    already present in the --conditioning_path file are kept."""
+def video_list(image_paths, seed, num_seeds):
+    """the run's videos: (image, seed) pairs, image-major."""
+    return [(im, seed + k) for im in image_paths for k in range(num_seeds)]
+
+
+def padded_batches(items, per):
+    """consecutive batches of `per` items; a ragged last batch is padded with repeats of its own items.  -> [(batch, n_real)]"""
+    out = []
+    for b0 in range(0, len(items), per):
+        b = items[b0:b0 + per]
+        out.append(((b * per)[:per], len(b)))
+    return out
+
+
+def output_stem(image, seed, several_images):
+    """output_i2v_seed_<seed> (one image, the reference's name) or <image stem>_seed_<seed> (several images)."""
+    if not several_images:
+        return f"output_i2v_seed_{seed}"
+    return f"{os.path.splitext(os.path.basename(image))[0]}_seed_{seed}"
+
+
+def check_args(opt):
+    """the run's video list; refuses what a multi-video run cannot do (before anything touches the GPU)."""
+    images = [p for p in opt.image_path.split("+") if p]
+    if not images:
+        raise SystemExit("--image_path: no image given")
+    if opt.num_seeds < 1 or opt.seeds_per_batch < 0:
+        raise SystemExit("--num_seeds must be >= 1 and --seeds_per_batch >= 0")
+    if not 1 <= opt.gpus <= 8:
+        raise SystemExit("--gpus must be between 1 and 8")
+    videos = video_list(images, opt.seed, opt.num_seeds)
+    if len(videos) > 1 and opt.conditioning_path:
+        raise SystemExit(f"--conditioning_path holds the conditioning of ONE video; this run has {len(videos)} videos "
+                         f"({len(images)} image(s) x {opt.num_seeds} seed(s)): drop it or run one image with one seed")
+    return images, videos
+
+
+def _vae_config(j):
+    return dict(block_out_channels=tuple(j["block_out_channels"]), layers_per_block=j.get("layers_per_block", 2),
+                latent_channels=j.get("latent_channels", 4), out_channels=j.get("out_channels", 3), groups=j.get("norm_num_groups", 32))
+
+
+def encode_prompt(opt):
+    """encode_prompt: [negative, prompt] last hidden states [2,77,cross] (negative row first, CFG order)."""
+    from tweediemix_amd import text as T
+    tok = T.ClipBPETokenizer.from_pretrained(os.path.join(opt.i2v_path, "tokenizer"))
+    enc = T.load_text_tower(os.path.join(opt.i2v_path, "text_encoder"))
+    return enc.last_hidden_state(tok([opt.negative_prompt, opt.prompt])).float().cpu()
+
+
+def encode_images(opt, paths, need):
+    """the CLIP image embeddings [n,cross] ('image_embeddings' in need) and the VAE encoder's (mean, logvar) [n,4,h,w] plus the
+    scaling factor ('image_latents' in need) of the images `paths`, each tower run once, batched over the images."""
     import json
     from PIL import Image
     from fusion_generation.fusion_sampling import find_weights, load_state_dict
     from tweediemix_amd import text as T, vae as VA, video as V
-    out = {}
     root = opt.i2v_path
-    if "prompt_embeds" not in have:                     # encode_prompt: negative row first (CFG order)
-        tok = T.ClipBPETokenizer.from_pretrained(os.path.join(root, "tokenizer"))
-        enc = T.load_text_tower(os.path.join(root, "text_encoder"))
-        out["prompt_embeds"] = enc.last_hidden_state(tok([opt.negative_prompt, opt.prompt])).float().cpu()
-    if "image_embeddings" in have and "image_latents" in have:
-        return out
-    image = Image.open(opt.image_path).convert("RGB")
-    if "image_embeddings" not in have:                  # :623-628 + _encode_image: crop to (w, w), bilinear to the tower's size, CLIP stats
+    images = [Image.open(p).convert("RGB") for p in paths]
+    out = {}
+    if "image_embeddings" in need:                  # :623-628 + _encode_image: crop to (w, w), bilinear to the tower's size, CLIP stats
         icfg = json.load(open(os.path.join(root, "image_encoder", "config.json")))
         fx = os.path.join(root, "feature_extractor", "preprocessor_config.json")
         fcfg = json.load(open(fx)) if os.path.exists(fx) else {}
         size = icfg.get("image_size", 224)
         tower = T.ClipVisionEncoder(load_state_dict(find_weights(os.path.join(root, "image_encoder"), "model")), icfg["num_attention_heads"],
                                     icfg["patch_size"], icfg.get("hidden_act", "gelu"), icfg.get("layer_norm_eps", 1e-5))
-        crop = V.resize_bilinear(V.center_crop_wide(image, (opt.width, opt.width)), (size, size))
         kw = {k: tuple(fcfg[k2]) for k, k2 in (("mean", "image_mean"), ("std", "image_std")) if k2 in fcfg}
-        emb = tower(V.clip_pixel_values(crop, **kw)).float().cpu()
-        out["image_embeddings"] = torch.cat([torch.zeros_like(emb), emb])
-    if "image_latents" not in have:                     # :631-639 prepare_image_latents
+        px = torch.cat([V.clip_pixel_values(V.resize_bilinear(V.center_crop_wide(im, (opt.width, opt.width)), (size, size)), **kw) for im in images])
+        out["image_embeddings"] = tower(px).float().cpu()
+    if "image_latents" in need:                     # :631-639 prepare_image_latents, up to the sample
         vdir = os.path.join(root, "vae")
         j = json.load(open(os.path.join(vdir, "config.json")))
-        vcfg = dict(block_out_channels=tuple(j["block_out_channels"]), layers_per_block=j.get("layers_per_block", 2),
-                    latent_channels=j.get("latent_channels", 4), out_channels=j.get("out_channels", 3), groups=j.get("norm_num_groups", 32))
-        encp = VA.VAEEncoderPlan(vcfg, load_state_dict(find_weights(vdir, "diffusion_pytorch_model")), 1, opt.height, opt.width)
-        mean, logvar = encp(V.vae_pixel_values(V.center_crop_wide(image, (opt.width, opt.height))).cuda())
-        sample = mean.cpu() + torch.exp(0.5 * logvar.cpu()) * torch.randn(mean.shape, generator=gen)       # latent_dist.sample()
-        out["image_latents"] = V.prepare_image_latents(sample, opt.num_frames, j.get("scaling_factor", 0.18215))
+        encp = VA.VAEEncoderPlan(_vae_config(j), load_state_dict(find_weights(vdir, "diffusion_pytorch_model")), len(images), opt.height, opt.width)
+        px = torch.cat([V.vae_pixel_values(V.center_crop_wide(im, (opt.width, opt.height))) for im in images])
+        mean, logvar = encp(px.cuda())
+        out["moments"] = (mean.cpu(), logvar.cpu())
+        out["scaling_factor"] = j.get("scaling_factor", 0.18215)
     return out
 
 
-def main(argv=None):
-    opt = build_parser().parse_args(argv)
-    from tweediemix_amd import i2vgen as I, video as V
-    cfg = I.TINY if opt.tiny else I.FULL
-    h, w, Fr = opt.height // 8, opt.width // 8, opt.num_frames
-    if Fr != 16:
-        print("note: the reference's injection hook hard-codes 16 frames (video_gen/utils_attn.py:439)")
-    gen = torch.Generator().manual_seed(opt.seed)
+def image_latents(mean, logvar, gen, num_frames, scaling_factor):
+    """latent_dist.sample() of one image ([1,4,h,w] moments; the noise is drawn from the video's generator) -> [2,4,F,h,w]."""
+    from tweediemix_amd import video as V
+    sample = mean + torch.exp(0.5 * logvar) * torch.randn(mean.shape, generator=gen)
+    return V.prepare_image_latents(sample, num_frames, scaling_factor)
+
+
+def native_conditioning(opt, gen, have):
+    """what I2VGenXLPipeline.__call__ computes before its loop (video_gen/pipeline_i2vgen_xl.py:604-639), from the checkpoint's
+    tokenizer/ + text_encoder/ (prompt embeddings), image_encoder/ (CLIP image embedding) and vae/ (image latents); entries
+    already present in the --conditioning_path file are kept."""
+    out = {}
+    if "prompt_embeds" not in have:
+        out["prompt_embeds"] = encode_prompt(opt)
+    need = [k for k in ("image_embeddings", "image_latents") if k not in have]
+    if not need:
+        return out
+    enc = encode_images(opt, [opt.image_path], need)
+    if "image_embeddings" in need:
+        emb = enc["image_embeddings"]
+        out["image_embeddings"] = torch.cat([torch.zeros_like(emb), emb])
+    if "image_latents" in need:
+        out["image_latents"] = image_latents(*enc["moments"], gen, opt.num_frames, enc["scaling_factor"])
+    return out
+
+
+def unet_state_dict(opt, cfg):
     if opt.synthetic:
         from tweediemix_amd.weights import synthetic_i2vgen_state_dict
-        sd = synthetic_i2vgen_state_dict(cfg)
-        cond = {"prompt_embeds": torch.randn(2, 77, cfg.cross_dim, generator=gen), "image_embeddings": torch.randn(2, cfg.cross_dim, generator=gen),
-                "image_latents": torch.randn(2, 4, Fr, h, w, generator=gen)}
-    else:
-        if not opt.i2v_path:
-            sys.exit("need --i2v_path (or --synthetic); there is no hub download here")
-        from fusion_generation.fusion_sampling import find_weights, load_state_dict
-        sd = load_state_dict(find_weights(os.path.join(opt.i2v_path, "unet"), "diffusion_pytorch_model"))
-        cond = torch.load(opt.conditioning_path, map_location="cpu") if opt.conditioning_path else {}
-        cond.update(native_conditioning(opt, gen, cond))
-    Wt = I.I2VWeights(cfg, sd)
-    fps = torch.tensor([float(opt.target_fps)] * 2)
-    fe, ctx, ilf = I.conditioning(Wt, fps, cond["image_latents"], cond["image_embeddings"], cond["prompt_embeds"])
-    plan = (I.I2VPlanGroup if opt.streams == 2 else I.I2VPlan)(Wt, 2, Fr, h, w, fe, ctx, ilf, interp=opt.interp_ratio)
+        return synthetic_i2vgen_state_dict(cfg)
+    if not opt.i2v_path:
+        sys.exit("need --i2v_path (or --synthetic); there is no hub download here")
+    from fusion_generation.fusion_sampling import find_weights, load_state_dict
+    return load_state_dict(find_weights(os.path.join(opt.i2v_path, "unet"), "diffusion_pytorch_model"))
+
+
+def synthetic_conditioning(cfg, gen, Fr, h, w):
+    return {"prompt_embeds": torch.randn(2, 77, cfg.cross_dim, generator=gen), "image_embeddings": torch.randn(2, cfg.cross_dim, generator=gen),
+            "image_latents": torch.randn(2, 4, Fr, h, w, generator=gen)}
+
+
+def video_schedule(opt):
+    from tweediemix_amd import video as V
     sched_json = os.path.join(opt.i2v_path, "scheduler", "scheduler_config.json") if opt.i2v_path else ""
     sch_kw = {}
     if opt.alphas_cumprod:
@@ -132,7 +207,53 @@ def main(argv=None):
                   "i2vgen-xl settings (squaredcos_cap_v2, rescale_betas_zero_snr, steps_offset 1, set_alpha_to_one False)")
         acp, sch_kw = V.alphas_from_scheduler_config(dict(beta_schedule="squaredcos_cap_v2", rescale_betas_zero_snr=True,
                                                           steps_offset=1, set_alpha_to_one=False))
-    sch = V.VideoSchedule(acp, opt.num_inference_steps, **sch_kw)
+    return V.VideoSchedule(acp, opt.num_inference_steps, **sch_kw)
+
+
+def vae_decoder(opt):
+    """(config, state dict) of the --vae_path decoder."""
+    import json
+    from fusion_generation.fusion_sampling import find_weights, load_state_dict
+    from tweediemix_amd import vae as VA
+    vcfg = VA.FULL
+    if os.path.isdir(opt.vae_path) and os.path.exists(os.path.join(opt.vae_path, "config.json")):
+        vcfg = _vae_config(json.load(open(os.path.join(opt.vae_path, "config.json"))))
+    return vcfg, load_state_dict(find_weights(opt.vae_path, "diffusion_pytorch_model"))
+
+
+def save_gif(frames_chw, path, fps):
+    """frames [F,3,H,W] in [0,1] -> GIF (the pipeline's uint8 conversion)."""
+    from PIL import Image
+    frames = [Image.fromarray((img.permute(1, 2, 0).float().cpu().numpy() * 255).round().astype("uint8")) for img in frames_chw]
+    frames[0].save(path, save_all=True, append_images=frames[1:], duration=1000 // fps, loop=0)
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
+    images, videos = check_args(opt)
+    from tweediemix_amd import launch as LA
+    if opt.gpus > 1 and not LA.launched():
+        return LA.self_launch(opt.gpus)
+    rank, local, world = LA.rank_env()
+    if len(videos) > 1 or world > 1:
+        return main_batched(opt, images, videos, rank, local, world)
+    from tweediemix_amd import i2vgen as I, video as V
+    cfg = I.TINY if opt.tiny else I.FULL
+    h, w, Fr = opt.height // 8, opt.width // 8, opt.num_frames
+    if Fr != 16:
+        print("note: the reference's injection hook hard-codes 16 frames (video_gen/utils_attn.py:439)")
+    gen = torch.Generator().manual_seed(opt.seed)
+    sd = unet_state_dict(opt, cfg)
+    if opt.synthetic:
+        cond = synthetic_conditioning(cfg, gen, Fr, h, w)
+    else:
+        cond = torch.load(opt.conditioning_path, map_location="cpu") if opt.conditioning_path else {}
+        cond.update(native_conditioning(opt, gen, cond))
+    Wt = I.I2VWeights(cfg, sd)
+    fps = torch.tensor([float(opt.target_fps)] * 2)
+    fe, ctx, ilf = I.conditioning(Wt, fps, cond["image_latents"], cond["image_embeddings"], cond["prompt_embeds"])
+    plan = (I.I2VPlanGroup if opt.streams == 2 else I.I2VPlan)(Wt, 2, Fr, h, w, fe, ctx, ilf, interp=opt.interp_ratio)
+    sch = video_schedule(opt)
     inj = V.FeatureInjector(sch.injection_schedule(opt.injection_timestep), opt.interp_ratio, clips=2, frames=Fr)
     x = torch.randn(1, 4, Fr, h, w, generator=gen).cuda()          # latents * init_noise_sigma (= 1 for DDIM)
     graphs = {}
@@ -159,29 +280,103 @@ def main(argv=None):
 
     unet.plan = plan
     lat = V.sample_loop(unet, x, sch, opt.guidance_scale, inj)
-    out = f"output_i2v_seed_{opt.seed}.latent.pt"
+    os.makedirs(opt.output_dir, exist_ok=True)
+    stem = os.path.join(opt.output_dir, output_stem(opt.image_path, opt.seed, False))
+    out = stem + ".latent.pt"
     torch.save(lat.cpu(), out)
     print("saved", out)
     if opt.vae_path:
-        import json
-        from PIL import Image
-        from fusion_generation.fusion_sampling import find_weights, load_state_dict
         from tweediemix_amd import vae as VA
-        vcfg = VA.FULL
-        if os.path.isdir(opt.vae_path) and os.path.exists(os.path.join(opt.vae_path, "config.json")):
-            j = json.load(open(os.path.join(opt.vae_path, "config.json")))
-            vcfg = dict(block_out_channels=tuple(j["block_out_channels"]), layers_per_block=j.get("layers_per_block", 2),
-                        latent_channels=j.get("latent_channels", 4), out_channels=j.get("out_channels", 3), groups=j.get("norm_num_groups", 32))
-        dec = VA.VAEDecoderPlan(vcfg, load_state_dict(find_weights(opt.vae_path, "diffusion_pytorch_model")), 1, h, w, 1 / 0.18215, "cuda")
+        vcfg, vsd = vae_decoder(opt)
+        dec = VA.VAEDecoderPlan(vcfg, vsd, 1, h, w, 1 / 0.18215, "cuda")
         frames = []
         for f in range(Fr):                                         # pipeline decode_latents: 1/scaling_factor, per frame
-            img = dec(lat[:, :, f].contiguous())[0].clamp(0, 1)
-            frames.append(Image.fromarray((img.permute(1, 2, 0).float().cpu().numpy() * 255).round().astype("uint8")))
-        gif = f"output_i2v_seed_{opt.seed}.gif"
-        frames[0].save(gif, save_all=True, append_images=frames[1:], duration=1000 // opt.target_fps, loop=0)
+            frames.append(dec(lat[:, :, f].contiguous())[0].clamp(0, 1))
+        gif = stem + ".gif"
+        save_gif(frames, gif, opt.target_fps)
         print("saved", gif)
     return lat
 
 
+def main_batched(opt, images, videos, rank, local, world):
+    """several videos (and / or several ranks): conditioning batched over the images, VideoSampler over batches of co-batched
+    videos, batched decode, the gather to rank 0, which writes every file."""
+    from tweediemix_amd import dist as D, i2vgen as I, video as V
+    if world > 1:
+        single = bool(os.environ.get("TMIX_SINGLE_GPU_DIST_TEST"))      # tests: all ranks on GPU 0, gloo
+        device = torch.device("cuda:0" if single else f"cuda:{local}")
+        torch.cuda.set_device(device)
+        D.init(device, world, backend="gloo" if single else None)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    say = print if rank == 0 else (lambda *a, **k: None)
+    cfg = I.TINY if opt.tiny else I.FULL
+    h, w, Fr = opt.height // 8, opt.width // 8, opt.num_frames
+    if Fr != 16:
+        say("note: the reference's injection hook hard-codes 16 frames (video_gen/utils_attn.py:439)")
+    mine = D.seed_shard(videos, rank, world)
+    sd = unet_state_dict(opt, cfg)
+    # per video, from its own generator in the single run's order: (synthetic conditioning | latent_dist noise), then x_T
+    if not opt.synthetic and mine:
+        pe = encode_prompt(opt)
+        distinct = sorted(set(im for im, _s in mine), key=images.index)
+        enc = encode_images(opt, distinct, ("image_embeddings", "image_latents"))
+    conds, xs = [], []
+    for im, seed in mine:
+        gen = torch.Generator().manual_seed(seed)
+        if opt.synthetic:
+            c = synthetic_conditioning(cfg, gen, Fr, h, w)
+        else:
+            k = distinct.index(im)
+            emb = enc["image_embeddings"][k:k + 1]
+            mean, logvar = enc["moments"]
+            c = {"prompt_embeds": pe, "image_embeddings": torch.cat([torch.zeros_like(emb), emb]),
+                 "image_latents": image_latents(mean[k:k + 1], logvar[k:k + 1], gen, Fr, enc["scaling_factor"])}
+        conds.append(c)
+        xs.append(torch.randn(1, 4, Fr, h, w, generator=gen))
+    Wt = I.I2VWeights(cfg, sd)
+    sch = video_schedule(opt)
+    per = opt.seeds_per_batch or min(max(len(mine), 1), 4)
+    lats = []
+    smp = plan = None
+    for batch, n_real in padded_batches(list(range(len(mine))), per):
+        S = len(batch)
+        rows = lambda key: torch.cat([conds[i][key][r:r + 1] for r in (0, 1) for i in batch])     # the S unconditional rows, then the S text rows
+        fps = torch.tensor([float(opt.target_fps)] * 2 * S)
+        fe, ctx, ilf = I.conditioning(Wt, fps, rows("image_latents"), rows("image_embeddings"), rows("prompt_embeds"))
+        smp = plan = None                                            # the previous batch's plan and graphs go before the next are built
+        plan = I.I2VVideoPlan(Wt, S, Fr, h, w, fe, ctx, ilf, streams=opt.streams, interp=opt.interp_ratio)
+        inj = V.FeatureInjector(sch.injection_schedule(opt.injection_timestep), opt.interp_ratio, clips=2 * S, frames=Fr)
+        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs)
+        lats.append(smp.sample(torch.cat([xs[i] for i in batch]).to(dev))[:n_real])
+    smp = plan = None
+    lat = torch.cat(lats) if lats else torch.zeros(0, 4, Fr, h, w, device=dev)
+    img = None
+    if opt.vae_path:                                                 # decode_latents in batches of frames, not one B = 1 decode per frame
+        from tweediemix_amd import vae as VA
+        vae, plans = vae_decoder(opt), {}
+        img = torch.stack([VA.decode_in_groups(vae, v.permute(1, 0, 2, 3).contiguous(), 1 / 0.18215, plans, dev).float().clamp(0, 1)
+                           for v in lat]) if len(lat) else torch.zeros(0, Fr, 3, opt.height, opt.width, device=dev)
+    if world > 1:                                                    # the result gather: the only collective of this path
+        import torch.distributed as dist
+        lat = D.gather_latents(lat.contiguous(), len(videos), rank, world)
+        if img is not None:
+            img = D.gather_latents(img.contiguous(), len(videos), rank, world)
+    if rank == 0:
+        os.makedirs(opt.output_dir, exist_ok=True)
+        several = len(images) > 1
+        for i, (im, seed) in enumerate(videos):
+            stem = os.path.join(opt.output_dir, output_stem(im, seed, several))
+            torch.save(lat[i:i + 1].cpu(), stem + ".latent.pt")
+            print("saved", stem + ".latent.pt")
+            if img is not None:
+                save_gif(img[i], stem + ".gif", opt.target_fps)
+                print("saved", stem + ".gif")
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    return lat
+
+
 if __name__ == "__main__":
-    main()
+    rc = main()
+    sys.exit(rc if isinstance(rc, int) else 0)

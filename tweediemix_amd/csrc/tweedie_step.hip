@@ -164,6 +164,53 @@ frame_inject_kernel(typename EpsT<DT>::T* __restrict__ x, int64_t per_frame, int
     }
 }
 
+// ------------------------------------------------------------------ batched video step (S videos, both CFG halves)
+// index i of the pipeline-layout state [S][C][F][hw] -> offset of (video s, frame f, channel c, pixel p) in a per-row plan buffer
+// [(clip*F + f)][row_channels][hw] whose clip s starts at s * clip_stride
+__device__ __forceinline__ int64_t video_row_offset(int64_t i, int C, int F, int64_t hw, int row_channels, int64_t clip_stride) {
+    const int64_t p = i % hw;
+    int64_t r = i / hw;
+    const int64_t f = r % F; r /= F;
+    const int64_t c = r % C;
+    const int64_t s = r / C;
+    return s * clip_stride + (f * row_channels + c) * hw + p;
+}
+
+// head of the captured video step: the state goes into channels [0, C) of the frame rows of both CFG halves' inputs (the image-latent
+// channels [C, row_channels) are not touched) and prm[0] = t into both halves' per-clip timestep inputs
+__global__ void __launch_bounds__(256)
+video_prologue_kernel(const float* __restrict__ x, float* __restrict__ xu, int64_t su, float* __restrict__ tu,
+                      float* __restrict__ xc, int64_t sc, float* __restrict__ tc, const float* __restrict__ prm,
+                      int videos, int C, int F, int64_t hw, int row_channels, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float v = x[i];
+        xu[video_row_offset(i, C, F, hw, row_channels, su)] = v;
+        xc[video_row_offset(i, C, F, hw, row_channels, sc)] = v;
+    }
+    if (blockIdx.x == 0) {
+        const float t = prm[0];
+        for (int k = threadIdx.x; k < videos; k += blockDim.x) { tu[k] = t; tc[k] = t; }
+    }
+}
+
+// vpred_step_kernel<TMIX_F32> for S videos with the coefficients from prm = {t, sa, s1, sa_next, s1_next, g, ...} and v_u / v_c read
+// from the plans' prediction rows [(clip*F + f)][C][hw]; the same operations in the same order, so the result is that kernel's bit for bit.
+// x is updated in place (element i is read before it is written).
+__global__ void __launch_bounds__(256)
+vpred_step_dev_kernel(float* __restrict__ x, const float* __restrict__ vu, int64_t su, const float* __restrict__ vc, int64_t sc,
+                      const float* __restrict__ prm, int C, int F, int64_t hw, int64_t n) {
+    const float sa = prm[1], s1 = prm[2], sa_n = prm[3], s1_n = prm[4], g = prm[5];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float xv = x[i];
+        const float vv = cfg<TMIX_F32>(vu[video_row_offset(i, C, F, hw, C, su)], vc[video_row_offset(i, C, F, hw, C, sc)], g);
+        const float eps = rnd<TMIX_F32>(rnd<TMIX_F32>(sa * vv) + rnd<TMIX_F32>(s1 * xv));
+        const float x0 = rnd<TMIX_F32>(rnd<TMIX_F32>(sa * xv) - rnd<TMIX_F32>(s1 * vv));
+        x[i] = rnd<TMIX_F32>(rnd<TMIX_F32>(sa_n * x0) + rnd<TMIX_F32>(s1_n * eps));
+    }
+}
+
 template <int DT>
 int launch_vpred(const void* x, const void* v, void* out, int64_t n, float g, float sa, float s1, float sa_n, float s1_n, hipStream_t st) {
     typedef typename EpsT<DT>::T T;
@@ -258,6 +305,39 @@ extern "C" int tmix_step_prologue(const float* x, float* latent, float* t_dev, c
     if (!aligned16(x) || !aligned16(latent)) TMIX_FAIL(TMIX_EALIGN, "step_prologue: x / latent must be 16-byte aligned");
     int64_t bx = (n / 4 + 255) / 256; if (bx > 256) bx = 256;
     step_prologue_kernel<<<dim3((unsigned)bx, (unsigned)seeds), 256, 0, (hipStream_t)stream>>>(x, latent, t_dev, params, rows, n);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+extern "C" int tmix_video_step_prologue(const float* x, float* x_u, int64_t clip_stride_u, float* t_u, float* x_c, int64_t clip_stride_c,
+                                        float* t_c, const float* params, int videos, int channels, int frames, int64_t hw,
+                                        int row_channels, void* stream) {
+    if (!x || !x_u || !t_u || !x_c || !t_c || !params) TMIX_FAIL(TMIX_EINVAL, "video_step_prologue: null pointer");
+    if (videos < 1 || channels < 1 || frames < 1 || hw < 1 || row_channels < channels)
+        TMIX_FAIL(TMIX_ESHAPE, "video_step_prologue: videos=%d channels=%d frames=%d hw=%lld row_channels=%d", videos, channels, frames, (long long)hw, row_channels);
+    const int64_t clip = (int64_t)frames * row_channels * hw;
+    if (clip_stride_u < clip || clip_stride_c < clip)
+        TMIX_FAIL(TMIX_ESHAPE, "video_step_prologue: clip strides %lld / %lld < one clip's %lld floats", (long long)clip_stride_u, (long long)clip_stride_c, (long long)clip);
+    const int64_t n = (int64_t)videos * channels * frames * hw;
+    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    video_prologue_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, x_u, clip_stride_u, t_u, x_c, clip_stride_c, t_c, params,
+                                                                             videos, channels, frames, hw, row_channels, n);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+extern "C" int tmix_vpred_step_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
+                                   const float* params, int videos, int channels, int frames, int64_t hw, void* stream) {
+    if (!x || !v_u || !v_c || !params) TMIX_FAIL(TMIX_EINVAL, "vpred_step_dev: null pointer");
+    if (videos < 1 || channels < 1 || frames < 1 || hw < 1)
+        TMIX_FAIL(TMIX_ESHAPE, "vpred_step_dev: videos=%d channels=%d frames=%d hw=%lld", videos, channels, frames, (long long)hw);
+    const int64_t clip = (int64_t)frames * channels * hw;
+    if (clip_stride_u < clip || clip_stride_c < clip)
+        TMIX_FAIL(TMIX_ESHAPE, "vpred_step_dev: clip strides %lld / %lld < one clip's %lld floats", (long long)clip_stride_u, (long long)clip_stride_c, (long long)clip);
+    const int64_t n = (int64_t)videos * channels * frames * hw;
+    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    vpred_step_dev_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, v_u, clip_stride_u, v_c, clip_stride_c, params,
+                                                                             channels, frames, hw, n);
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
 }

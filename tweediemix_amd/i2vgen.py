@@ -519,3 +519,50 @@ class I2VPlanGroup:
         self.set_input(sample, t)
         self.run()
         return self.eps.view(self.clips, self.frames, self.cfg.out_channels, self.h, self.w).permute(0, 2, 1, 3, 4)
+
+
+class I2VVideoPlan:
+    """S videos in one UNet call, for tweediemix_amd.video.VideoSampler.  Conditioning rows [2S]: the S unconditional clips, then the
+    S text clips (conditioning() of both halves in one call).  streams=2: two chains, I2VPlan(clips=S) per CFG half, each on its own
+    HIP stream (I2VPlanGroup's trick at S clips per chain); streams=1: one I2VPlan(clips=2S).  `halves` are the (input rows, timestep
+    input, prediction rows) of the unconditional and the text half; the sampler's kernels read and write them in place, so no copy
+    or permute sits between the chains and the step."""
+
+    def __init__(self, W: I2VWeights, videos: int, frames: int, h: int, w: int, fps_emb, context, il_feat, streams: int = 2,
+                 autotune: bool = True, interp: float = 0.7):
+        assert streams in (1, 2) and fps_emb.shape[0] == context.shape[0] == il_feat.shape[0] == 2 * videos
+        self.cfg, self.videos, self.frames, self.h, self.w, self.n_streams = W.cfg, videos, frames, h, w, streams
+        S, Fr = videos, frames
+        if streams == 2:
+            self.plans = [I2VPlan(W, S, Fr, h, w, fps_emb[i * S:(i + 1) * S], context[i * S:(i + 1) * S], il_feat[i * S:(i + 1) * S],
+                                  autotune=autotune, interp=interp, shared=True) for i in range(2)]
+            self.streams = [None, torch.cuda.Stream(device=W.device)]
+            self.halves = [(p.x_in, p.t_dev, p.eps) for p in self.plans]
+        else:
+            p = I2VPlan(W, 2 * S, Fr, h, w, fps_emb, context, il_feat, autotune=autotune, interp=interp)
+            self.plans, self.streams = [p], [None]
+            self.halves = [(p.x_in[i * S * Fr:(i + 1) * S * Fr], p.t_dev[i * S:(i + 1) * S], p.eps[i * S * Fr:(i + 1) * S * Fr]) for i in range(2)]
+        self.flops = sum(p.flops for p in self.plans)
+        self.ops = [op for p in self.plans for op in p.ops]
+
+    inject = property(lambda self: self.plans[0].inject, lambda self, v: [setattr(p, "inject", v) for p in self.plans])
+    interp = property(lambda self: self.plans[0].interp, lambda self, v: [setattr(p, "interp", v) for p in self.plans])
+
+    def refine(self, **kw):
+        return refine_group(self, **kw)
+
+    def run(self):
+        if len(self.plans) == 1:
+            self.plans[0].run()
+            return
+        main = torch.cuda.current_stream()
+        fork = torch.cuda.Event()
+        fork.record(main)
+        st = self.streams[1]
+        st.wait_event(fork)
+        with torch.cuda.stream(st):
+            self.plans[1].run()
+            join = torch.cuda.Event()
+            join.record(st)
+        self.plans[0].run()
+        main.wait_event(join)

@@ -105,6 +105,8 @@ SIGNATURES = {
     "tmix_temporal_attn": (C.c_int, [vp, i64, vp, i64, C.c_int, C.c_int, i64, C.c_int, f32, vp]),
     "tmix_vpred_step": (C.c_int, [vp, vp, vp, C.c_int, i64, f32, f32, f32, f32, f32, vp]),
     "tmix_frame_inject": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, f32, f32, vp]),
+    "tmix_video_step_prologue": (C.c_int, [vp, vp, i64, vp, vp, i64, vp, vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp]),
+    "tmix_vpred_step_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_int, C.c_int, i64, vp]),
     "tmix_gemm_tile_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tmix_gemm_stats_parts": (C.c_int, [C.c_int, C.c_int]),
     "tmix_concat_channels": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, i64, vp]),

@@ -612,6 +612,49 @@ def vpred_step(x, v, g, at, at_next, out=None):
     return out
 
 
+def video_step_prologue(x, x_u, t_u, x_c, t_c, params, clip_stride_u=None, clip_stride_c=None):
+    """head of the batched video step: x [S,C,F,h,w] fp32 (pipeline layout) -> channels [0, C) of the CFG halves' plan inputs
+    x_u / x_c (frame rows [(S*F), R, h, w], R >= C, clip s at s * clip_stride floats: default one contiguous clip), and
+    params[0] -> t_u / t_c [S].  Channels [C, R) are not written."""
+    _need_cuda(x, x_u, t_u, x_c, t_c, params)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x_u.dtype == x_c.dtype == torch.float32
+    S, Cc, Fr, h, w = x.shape
+    R = x_u.shape[1]
+    su = clip_stride_u or Fr * R * h * w
+    sc = clip_stride_c or Fr * R * h * w
+    for buf, st, tt in ((x_u, su, t_u), (x_c, sc, t_c)):        # the kernel writes up to clip S-1's last frame row and S timesteps
+        assert buf.is_contiguous() and buf.shape[1] == R and buf.numel() >= (S - 1) * st + Fr * R * h * w and tt.numel() >= S
+    L.check(L.load().tmix_video_step_prologue(_p(x), _p(x_u), su, _p(t_u), _p(x_c), sc, _p(t_c), _p(params), S, Cc, Fr, h * w, R,
+                                              _stream()), "tmix_video_step_prologue")
+
+
+def vpred_step_dev(x, v_u, v_c, params, clip_stride_u=None, clip_stride_c=None):
+    """vpred_step for S videos in place on x [S,C,F,h,w] fp32, the CFG halves' predictions read from the plans' frame rows
+    v_u / v_c [(S*F), C, h, w] (clip s at s * clip_stride floats) and the coefficients from params {t, sa, s1, sa', s1', g}."""
+    _need_cuda(x, v_u, v_c, params)
+    assert x.dtype == v_u.dtype == v_c.dtype == torch.float32 and x.is_contiguous()
+    S, Cc, Fr, h, w = x.shape
+    su = clip_stride_u or Fr * Cc * h * w
+    sc = clip_stride_c or Fr * Cc * h * w
+    for buf, st in ((v_u, su), (v_c, sc)):
+        assert buf.is_contiguous() and buf.numel() >= (S - 1) * st + Fr * Cc * h * w
+    L.check(L.load().tmix_vpred_step_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(params), S, Cc, Fr, h * w, _stream()),
+            "tmix_vpred_step_dev")
+    return x
+
+
+def video_step_params(t, g, at, at_next, out=None):
+    """the 8 floats {t, sa, s1, sa_next, s1_next, g, 0, 0} the batched video step reads (coefficients as vpred_step computes them)."""
+    f = np.float32
+    vals = [float(t), float(np.sqrt(f(at))), float(np.sqrt(f(1) - f(at))), float(np.sqrt(f(at_next))), float(np.sqrt(f(1) - f(at_next))),
+            float(g), 0.0, 0.0]
+    if out is None:
+        return torch.tensor(vals, dtype=torch.float32)
+    for i, v in enumerate(vals):
+        out[i] = v
+    return out
+
+
 def frame_inject(x, clips, frames, interp=None):
     """first-frame feature injection (video_gen/utils_attn.py:433-455), in place on x [(clips*frames), ...] contiguous."""
     _need_cuda(x)

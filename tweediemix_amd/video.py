@@ -105,6 +105,78 @@ def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_s
     return x
 
 
+class VideoSampler:
+    """sample_loop for S videos in one UNet call, with the whole step on the device.  `plan` is an i2vgen.I2VVideoPlan; the state
+    [S,4,F,h,w] fp32 is updated in place.  One step = tmix_video_step_prologue (state -> both CFG halves' inputs, t -> their
+    timestep inputs) -> the plan's chains -> tmix_vpred_step_dev (CFG + v-prediction + DDIM for every video, coefficients from the
+    device parameter buffer).  With graphs (default) that sequence is captured once per injection state (the injection ops are
+    decided at record time) and a timestep is one 32-byte upload from a pinned staging ring plus one replay; use_graphs=False issues
+    the same launches eagerly.  Video s of a batch is bit for bit what sample_loop gives for it alone (tmix_vpred_step_dev is
+    tmix_vpred_step per element)."""
+
+    def __init__(self, plan, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None, use_graphs: bool = True):
+        self.plan, self.schedule, self.g, self.injector, self.use_graphs = plan, schedule, float(guidance_scale), injector, use_graphs
+        cfg = plan.cfg
+        dev = plan.plans[0].dev
+        self.state = torch.zeros(plan.videos, cfg.in_channels, plan.frames, plan.h, plan.w, device=dev, dtype=torch.float32)
+        self.params = torch.zeros(8, device=dev, dtype=torch.float32)           # {t, sa, s1, sa_next, s1_next, g, -, -}
+        # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it has
+        # completed (as the image sampler's step_params)
+        self._hp = torch.zeros(64, 8, dtype=torch.float32).pin_memory()
+        self._hp_ev = [None] * self._hp.shape[0]
+        self._hp_i = 0
+        self.graphs = {}
+
+    def _enqueue(self):
+        (xu, tu, eu), (xc, tc, ec) = self.plan.halves
+        ops.video_step_prologue(self.state, xu, tu, xc, tc, self.params)
+        self.plan.run()
+        ops.vpred_step_dev(self.state, eu, ec, self.params)
+
+    def _upload(self, t):
+        sch = self.schedule
+        i = self._hp_i
+        self._hp_i = (i + 1) % self._hp.shape[0]
+        if self._hp_ev[i] is not None:
+            self._hp_ev[i].synchronize()
+        hp = self._hp[i]
+        ops.video_step_params(t, self.g, sch.alpha(int(t)), sch.alpha(int(t) - sch.skip), out=hp)
+        self.params.copy_(hp, non_blocking=True)
+        self._hp_ev[i] = torch.cuda.Event()
+        self._hp_ev[i].record()
+
+    def step(self, t):
+        inject = False
+        if self.injector is not None:
+            self.injector.register_time(t)
+            inject = injection_active(int(t), self.injector.schedule)
+            self.plan.inject, self.plan.interp = inject, self.injector.interp
+        self._upload(t)
+        if not self.use_graphs:
+            self._enqueue()
+            return
+        g = self.graphs.get(inject)
+        if g is None:
+            self._enqueue()                               # warm-up outside capture; it has already performed this step
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            keep = self.state.clone()
+            with torch.cuda.graph(g):
+                self._enqueue()
+            self.state.copy_(keep)
+            self.graphs[inject] = g
+            return
+        g.replay()
+
+    @torch.no_grad()
+    def sample(self, latents: torch.Tensor) -> torch.Tensor:
+        """latents [S,4,F,h,w] -> the final latents (a copy of the state)."""
+        self.state.copy_(latents)
+        for t in self.schedule.timesteps:
+            self.step(int(t))
+        return self.state.clone()
+
+
 # ------------------------------------------------------------------------------------------ image side of the pipeline (host)
 def center_crop_wide(image, resolution):
     """video_gen/pipeline_i2vgen_xl.py:772-793: BOX-resize so the image covers `resolution` (w, h), then centre crop (PIL)."""
