@@ -14,7 +14,7 @@ with the reference's values as defaults, and the model comes from local files:
 
 Per step: native UNet forward on the CFG pair (tweediemix_amd/i2vgen.py) with the first-frame feature injection of
 video_gen/utils_attn.py:389-474 for the first int(steps * injection_timestep) steps, then the fused CFG / v-prediction /
-DDIM update (tmix_vpred_step).  Output: output_i2v_seed_<seed>.latent.pt, plus output_i2v_seed_<seed>.gif with --vae_path.
+DDIM update.  Output: output_i2v_seed_<seed>.latent.pt, plus output_i2v_seed_<seed>.gif with --vae_path.
 
 Many videos per run (a video is one (image, seed) pair; the videos are the images x seeds, image-major):
   --image_path a.png+b.png  several images ('+'-separated); outputs are then named <image stem>_seed_<seed>.*
@@ -23,8 +23,9 @@ Many videos per run (a video is one (image, seed) pair; the videos are the image
   --gpus G                  videos sharded round-robin over G GPUs (one process per GPU, started by this script); latents (and
                             decoded frames) are gathered over RCCL and rank 0 writes every file
   --output_dir D            where the files go (default .)
-Such runs go through tweediemix_amd.video.VideoSampler: the whole step of S videos on the device (tmix_video_step_prologue ->
-both CFG chains -> tmix_vpred_step_dev), one parameter upload and one graph replay per timestep; frames are decoded in batches."""
+Every run, one video or many, goes through tweediemix_amd.video.VideoSampler: the whole step of S videos on the device
+(tmix_video_step_prologue -> both CFG chains -> tmix_vpred_step_dev), one parameter upload and one graph replay per timestep;
+frames are decoded in batches (vae.decode_in_groups), so a video's GIF does not depend on whether it ran alone or in a batch."""
 import argparse
 import os
 import sys
@@ -158,25 +159,6 @@ def image_latents(mean, logvar, gen, num_frames, scaling_factor):
     return V.prepare_image_latents(sample, num_frames, scaling_factor)
 
 
-def native_conditioning(opt, gen, have):
-    """what I2VGenXLPipeline.__call__ computes before its loop (video_gen/pipeline_i2vgen_xl.py:604-639), from the checkpoint's
-    tokenizer/ + text_encoder/ (prompt embeddings), image_encoder/ (CLIP image embedding) and vae/ (image latents); entries
-    already present in the --conditioning_path file are kept."""
-    out = {}
-    if "prompt_embeds" not in have:
-        out["prompt_embeds"] = encode_prompt(opt)
-    need = [k for k in ("image_embeddings", "image_latents") if k not in have]
-    if not need:
-        return out
-    enc = encode_images(opt, [opt.image_path], need)
-    if "image_embeddings" in need:
-        emb = enc["image_embeddings"]
-        out["image_embeddings"] = torch.cat([torch.zeros_like(emb), emb])
-    if "image_latents" in need:
-        out["image_latents"] = image_latents(*enc["moments"], gen, opt.num_frames, enc["scaling_factor"])
-    return out
-
-
 def unet_state_dict(opt, cfg):
     if opt.synthetic:
         from tweediemix_amd.weights import synthetic_i2vgen_state_dict
@@ -229,79 +211,14 @@ def save_gif(frames_chw, path, fps):
 
 
 def main(argv=None):
+    """every run, one video or many, one rank or many: conditioning batched over the images, VideoSampler over batches of co-batched
+    videos, batched decode, the gather to rank 0, which writes every file."""
     opt = build_parser().parse_args(argv)
     images, videos = check_args(opt)
-    from tweediemix_amd import launch as LA
+    from tweediemix_amd import dist as D, i2vgen as I, launch as LA, video as V
     if opt.gpus > 1 and not LA.launched():
         return LA.self_launch(opt.gpus)
     rank, local, world = LA.rank_env()
-    if len(videos) > 1 or world > 1:
-        return main_batched(opt, images, videos, rank, local, world)
-    from tweediemix_amd import i2vgen as I, video as V
-    cfg = I.TINY if opt.tiny else I.FULL
-    h, w, Fr = opt.height // 8, opt.width // 8, opt.num_frames
-    if Fr != 16:
-        print("note: the reference's injection hook hard-codes 16 frames (video_gen/utils_attn.py:439)")
-    gen = torch.Generator().manual_seed(opt.seed)
-    sd = unet_state_dict(opt, cfg)
-    if opt.synthetic:
-        cond = synthetic_conditioning(cfg, gen, Fr, h, w)
-    else:
-        cond = torch.load(opt.conditioning_path, map_location="cpu") if opt.conditioning_path else {}
-        cond.update(native_conditioning(opt, gen, cond))
-    Wt = I.I2VWeights(cfg, sd)
-    fps = torch.tensor([float(opt.target_fps)] * 2)
-    fe, ctx, ilf = I.conditioning(Wt, fps, cond["image_latents"], cond["image_embeddings"], cond["prompt_embeds"])
-    plan = (I.I2VPlanGroup if opt.streams == 2 else I.I2VPlan)(Wt, 2, Fr, h, w, fe, ctx, ilf, interp=opt.interp_ratio)
-    sch = video_schedule(opt)
-    inj = V.FeatureInjector(sch.injection_schedule(opt.injection_timestep), opt.interp_ratio, clips=2, frames=Fr)
-    x = torch.randn(1, 4, Fr, h, w, generator=gen).cuda()          # latents * init_noise_sigma (= 1 for DDIM)
-    graphs = {}
-
-    def unet(xin, t):                                               # one recorded forward per injection state, replayed as a hipGraph
-        if opt.streams == 2:
-            plan.set_input(xin, t)
-        else:
-            xv = plan.x_in.view(2, Fr, 2 * cfg.in_channels, h, w)
-            xv[:, :, :cfg.in_channels] = xin.permute(0, 2, 1, 3, 4)
-            plan.t_dev.fill_(float(t))
-        if opt.no_graphs:
-            plan.run()
-        else:
-            g = graphs.get(plan.inject)
-            if g is None:
-                plan.run(); torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    plan.run()
-                graphs[plan.inject] = g
-            g.replay()
-        return plan.eps.view(2, Fr, cfg.out_channels, h, w).permute(0, 2, 1, 3, 4).contiguous()
-
-    unet.plan = plan
-    lat = V.sample_loop(unet, x, sch, opt.guidance_scale, inj)
-    os.makedirs(opt.output_dir, exist_ok=True)
-    stem = os.path.join(opt.output_dir, output_stem(opt.image_path, opt.seed, False))
-    out = stem + ".latent.pt"
-    torch.save(lat.cpu(), out)
-    print("saved", out)
-    if opt.vae_path:
-        from tweediemix_amd import vae as VA
-        vcfg, vsd = vae_decoder(opt)
-        dec = VA.VAEDecoderPlan(vcfg, vsd, 1, h, w, 1 / 0.18215, "cuda")
-        frames = []
-        for f in range(Fr):                                         # pipeline decode_latents: 1/scaling_factor, per frame
-            frames.append(dec(lat[:, :, f].contiguous())[0].clamp(0, 1))
-        gif = stem + ".gif"
-        save_gif(frames, gif, opt.target_fps)
-        print("saved", gif)
-    return lat
-
-
-def main_batched(opt, images, videos, rank, local, world):
-    """several videos (and / or several ranks): conditioning batched over the images, VideoSampler over batches of co-batched
-    videos, batched decode, the gather to rank 0, which writes every file."""
-    from tweediemix_amd import dist as D, i2vgen as I, video as V
     if world > 1:
         single = bool(os.environ.get("TMIX_SINGLE_GPU_DIST_TEST"))      # tests: all ranks on GPU 0, gloo
         device = torch.device("cuda:0" if single else f"cuda:{local}")
@@ -315,11 +232,15 @@ def main_batched(opt, images, videos, rank, local, world):
         say("note: the reference's injection hook hard-codes 16 frames (video_gen/utils_attn.py:439)")
     mine = D.seed_shard(videos, rank, world)
     sd = unet_state_dict(opt, cfg)
-    # per video, from its own generator in the single run's order: (synthetic conditioning | latent_dist noise), then x_T
+    # what I2VGenXLPipeline.__call__ computes before its loop (video_gen/pipeline_i2vgen_xl.py:604-639): the --conditioning_path entries
+    # (one video only) are used as given, only the missing ones are computed, each tower once, batched over the images
+    given = torch.load(opt.conditioning_path, map_location="cpu") if opt.conditioning_path and not opt.synthetic else {}
     if not opt.synthetic and mine:
-        pe = encode_prompt(opt)
+        pe = given["prompt_embeds"] if "prompt_embeds" in given else encode_prompt(opt)
         distinct = sorted(set(im for im, _s in mine), key=images.index)
-        enc = encode_images(opt, distinct, ("image_embeddings", "image_latents"))
+        need = [k for k in ("image_embeddings", "image_latents") if k not in given]
+        enc = encode_images(opt, distinct, need) if need else {}
+    # per video, from its own generator in this order: (synthetic conditioning | latent_dist noise, when image_latents is computed), then x_T
     conds, xs = [], []
     for im, seed in mine:
         gen = torch.Generator().manual_seed(seed)
@@ -327,12 +248,15 @@ def main_batched(opt, images, videos, rank, local, world):
             c = synthetic_conditioning(cfg, gen, Fr, h, w)
         else:
             k = distinct.index(im)
-            emb = enc["image_embeddings"][k:k + 1]
-            mean, logvar = enc["moments"]
-            c = {"prompt_embeds": pe, "image_embeddings": torch.cat([torch.zeros_like(emb), emb]),
-                 "image_latents": image_latents(mean[k:k + 1], logvar[k:k + 1], gen, Fr, enc["scaling_factor"])}
+            c = dict(given, prompt_embeds=pe)
+            if "image_embeddings" in enc:
+                emb = enc["image_embeddings"][k:k + 1]
+                c["image_embeddings"] = torch.cat([torch.zeros_like(emb), emb])
+            if "moments" in enc:
+                mean, logvar = enc["moments"]
+                c["image_latents"] = image_latents(mean[k:k + 1], logvar[k:k + 1], gen, Fr, enc["scaling_factor"])
         conds.append(c)
-        xs.append(torch.randn(1, 4, Fr, h, w, generator=gen))
+        xs.append(torch.randn(1, 4, Fr, h, w, generator=gen))          # latents * init_noise_sigma (= 1 for DDIM)
     Wt = I.I2VWeights(cfg, sd)
     sch = video_schedule(opt)
     per = opt.seeds_per_batch or min(max(len(mine), 1), 4)
@@ -351,12 +275,12 @@ def main_batched(opt, images, videos, rank, local, world):
     smp = plan = None
     lat = torch.cat(lats) if lats else torch.zeros(0, 4, Fr, h, w, device=dev)
     img = None
-    if opt.vae_path:                                                 # decode_latents in batches of frames, not one B = 1 decode per frame
+    if opt.vae_path:                                                 # decode_latents (1 / scaling_factor) in batches of frames
         from tweediemix_amd import vae as VA
         vae, plans = vae_decoder(opt), {}
         img = torch.stack([VA.decode_in_groups(vae, v.permute(1, 0, 2, 3).contiguous(), 1 / 0.18215, plans, dev).float().clamp(0, 1)
                            for v in lat]) if len(lat) else torch.zeros(0, Fr, 3, opt.height, opt.width, device=dev)
-    if world > 1:                                                    # the result gather: the only collective of this path
+    if world > 1:                                                    # the result gather: the only collective of a run
         import torch.distributed as dist
         lat = D.gather_latents(lat.contiguous(), len(videos), rank, world)
         if img is not None:

@@ -1,6 +1,7 @@
 """GPU: many videos per UNet call (tweediemix_amd.video.VideoSampler, i2vgen.I2VVideoPlan, run_video.py's batched path).
-The two step kernels against tmix_vpred_step and a torch permute / copy, the sampler at S = 1 against the legacy loop, co-batched
-videos against their own single runs, and the CLI (ragged batch, two images, two ranks) against single-video runs -- bit for bit."""
+The two step kernels against tmix_vpred_step and a torch permute / copy, the sampler at S = 1 against the host loop, co-batched
+videos against their own single runs, and the CLI (ragged batch, two images, two ranks) against single-video runs -- bit for bit --
+plus the one-video run's --conditioning_path."""
 import importlib.util
 import os
 import subprocess
@@ -127,15 +128,18 @@ def _batched(Wt, vids, streams, graphs=True, autotune=False):
     return out.cpu()
 
 
-def _legacy(Wt, vid, streams, graphs=True):
-    """run_video.py's single-video loop: V.sample_loop over I2VPlanGroup(clips=2) / I2VPlan(clips=2)."""
+def _host_loop(Wt, vid, streams, graphs=True):
+    """the reference-shaped host loop: V.sample_loop over I2VPlanGroup(clips=2) / I2VPlan(clips=2), one recorded graph per injection state."""
     from tweediemix_amd import i2vgen as I, video as V
     c, x = vid
     fe, ctx, ilf = I.conditioning(Wt, torch.tensor([8.0, 8.0]), c["il"], c["ie"], c["pe"])
     plan = (I.I2VPlanGroup if streams == 2 else I.I2VPlan)(Wt, 2, FR, H, W, fe, ctx, ilf, autotune=False)
+    sch = _schedule()
+    inj = V.FeatureInjector(sch.injection_schedule(0.2), 0.7, clips=2, frames=FR)
     cache = {}
 
     def unet(xin, t):
+        plan.inject, plan.interp = V.injection_active(t, inj.schedule), inj.interp     # the plan carries the injection as ops of its forward
         if streams == 2:
             plan.set_input(xin, t)
         else:
@@ -154,21 +158,19 @@ def _legacy(Wt, vid, streams, graphs=True):
             gr.replay()
         return plan.eps.view(2, FR, 4, H, W).permute(0, 2, 1, 3, 4).contiguous()
 
-    unet.plan = plan
-    sch = _schedule()
-    return V.sample_loop(unet, x.cuda(), sch, 9.0, V.FeatureInjector(sch.injection_schedule(0.2), 0.7, clips=2, frames=FR)).cpu()
+    return V.sample_loop(unet, x.cuda(), sch, 9.0, inj).cpu()
 
 
 @pytest.mark.timeout(120)
 @pytest.mark.parametrize("streams", [2, 1])
-def test_sampler_one_video_equals_legacy_loop(streams):
+def test_sampler_one_video_equals_host_loop(streams):
     """10 steps, injection on the first two: the new sampler at S = 1 is V.sample_loop bit for bit, with and without graphs."""
     torch.manual_seed(0)
     Wt = _weights()
     vid = _video(3)
     for graphs in (True, False):
         a = _batched(Wt, [vid], streams, graphs)
-        b = _legacy(Wt, vid, streams, graphs)
+        b = _host_loop(Wt, vid, streams, graphs)
         assert torch.equal(a, b), (graphs, float((a - b).abs().max()))
 
 
@@ -241,8 +243,8 @@ def _i2v_folder(tmp_path, golden_dir):
 
 @pytest.mark.timeout(180)
 def test_cli_two_images_equal_single_image_runs(tmp_path, monkeypatch, golden_dir):
-    """--image_path a.png+b.png with --vae_path: per image, the latent equals the single-image run's and the 16-frame GIF (batched
-    decode) matches that run's GIF (per-frame decode) to within 1 of 255."""
+    """--image_path a.png+b.png with --vae_path: per image, the latent and the 16-frame GIF equal the single-image run's (both runs
+    decode in batches of frames)."""
     from PIL import Image
     monkeypatch.setenv("TMIX_FORCE_TILE", "1")
     ck = _i2v_folder(tmp_path, golden_dir)
@@ -265,7 +267,49 @@ def test_cli_two_images_equal_single_image_runs(tmp_path, monkeypatch, golden_di
         for f in range(16):
             ga.seek(f); gb.seek(f)
             fa, fb = np.asarray(ga.convert("RGB"), np.int16), np.asarray(gb.convert("RGB"), np.int16)
-            assert np.abs(fa - fb).max() <= 1, (i, f)
+            assert np.array_equal(fa, fb), (i, f, int(np.abs(fa - fb).max()))
+
+
+@pytest.mark.timeout(180)
+def test_cli_conditioning_path_one_video(tmp_path, monkeypatch, golden_dir):
+    """--conditioning_path on the one-video run: a file holding only the prompt embeddings the run computes gives the no-file latent
+    bit for bit (the merge and the generator's draw order) without computing them; a file holding all three keys runs neither the
+    text tower nor the image towers."""
+    from PIL import Image
+    monkeypatch.setenv("TMIX_FORCE_TILE", "1")
+    ck = _i2v_folder(tmp_path, golden_dir)
+    img = tmp_path / "img.png"
+    Image.fromarray(np.random.RandomState(0).randint(0, 256, (200, 300, 3), dtype=np.uint8)).save(img)
+    rv = _cli("run_video_batch_cli7")
+    common = ["--i2v_path", str(ck), "--image_path", str(img), "--tiny", "--height", "64", "--width", "128", "--num_inference_steps", "4",
+              "--seed", "5", "--prompt", "a cat and a dog running", "--negative_prompt", "blurry"]
+    seen = {}
+
+    def spy(name):
+        fn = getattr(rv, name)
+        def wrapped(*a, **k):
+            seen[name] = fn(*a, **k)
+            return seen[name]
+        monkeypatch.setattr(rv, name, wrapped)
+
+    def refuse(*a, **k):
+        raise AssertionError("computed what the --conditioning_path file holds")
+
+    for name in ("encode_prompt", "encode_images", "image_latents"):
+        spy(name)
+    want = rv.main(common + ["--output_dir", str(tmp_path / "plain")]).cpu()
+    torch.save({"prompt_embeds": seen["encode_prompt"]}, tmp_path / "pe.pt")
+    monkeypatch.setattr(rv, "encode_prompt", refuse)
+    got = rv.main(common + ["--conditioning_path", str(tmp_path / "pe.pt"), "--output_dir", str(tmp_path / "pe")]).cpu()
+    assert torch.equal(got, want), float((got - want).abs().max())
+    assert torch.equal(torch.load(tmp_path / "pe" / "output_i2v_seed_5.latent.pt"), torch.load(tmp_path / "plain" / "output_i2v_seed_5.latent.pt"))
+    emb = seen["encode_images"]["image_embeddings"]
+    torch.save({"prompt_embeds": seen["encode_prompt"], "image_embeddings": torch.cat([torch.zeros_like(emb), emb]),
+                "image_latents": seen["image_latents"]}, tmp_path / "all.pt")
+    for name in ("encode_images", "image_latents"):
+        monkeypatch.setattr(rv, name, refuse)
+    lat = rv.main(common + ["--conditioning_path", str(tmp_path / "all.pt"), "--output_dir", str(tmp_path / "all")]).cpu()
+    assert lat.shape == (1, 4, 16, 8, 16) and torch.isfinite(lat).all()
 
 
 @pytest.mark.timeout(240)

@@ -19,7 +19,7 @@ import torch
 
 from . import lib as L
 from . import ops
-from .unet import UNetPlan, _Arena, BF16, F32, refine_group, SHARED as U_SHARED
+from .unet import UNetPlan, BF16, F32, refine_group, run_chains, SHARED as U_SHARED
 from .weights import fold_layernorm, interleave_geglu
 
 
@@ -221,32 +221,20 @@ class I2VPlan(UNetPlan):
     def __init__(self, W: I2VWeights, clips: int, frames: int, h: int, w: int, fps_emb, context, il_feat, autotune: bool = True,
                  interp: float = 0.7, shared: bool = False):
         cfg = W.cfg
-        self.tune_ctx = U_SHARED if shared else ""
+        B = clips * frames                               # spatial layers see every frame as one image
+        # weight hints name whole tensors (a clip's launches last 50 - 800 us), at every size: not hint_policy()'s 8 MB heads for small calls
+        self._init_emit_state(W, B, h, w, (int(float(os.environ.get("TMIX_PF_CAP_MB", "0")) * (1 << 20)),
+                                           int(float(os.environ.get("TMIX_PF_CAP_OVER_MB", "20")) * (1 << 20))))
+        self.clips, self.frames = clips, frames
         self.inject, self.interp = False, interp         # raised per step by the sampling loop (FeatureInjector schedule)
-        self.W, self.cfg, self.clips, self.frames, self.h, self.w = W, cfg, clips, frames, h, w
-        self.B = B = clips * frames                     # spatial layers see every frame as one image
-        self.row_sets, self.routed, self._rows_cache = list(range(B)), False, {}
-        self.lowrank, self._sets_dev = False, None       # (no LoRA routing in the video UNet; UNetPlan's emitters ask -- tests/test_plan_attrs_cpu.py keeps this list honest)
-        self.fp8_chain_ff = False
-        self.fp8_attn_out = False
-        self.fp8_tile = 0
-        self.fp8_conv, self.fp8_conv_tile = False, 0
-        # GroupNorm statistics from the producers' column partials (UNetPlan._colstats) where 32-row blocks fit the normalised image: the per-frame norms of the
-        # first two levels (5376 / 1344 pixels) and the clip-wide norms of TemporalConvLayer / TransformerTemporalModel up to CLIP_COLSTATS_MAX rows (16 frames x HW is
-        # always a multiple of 32: every level since round 5); per-frame norms of 336 / 84 pixels and the injection sites keep the statistics kernel
-        self._gn_fused = not os.environ.get("TMIX_GN_STATS_KERNEL")
-        self._sc_fused = not os.environ.get("TMIX_SHORTCUT_GEMM")      # conv_shortcut in conv2's launch, no concat launches (UNetPlan._resnet)
-        self.lib, self.dev = L.load(), W.device
+        self.tune_ctx = U_SHARED if shared else ""
+        # what the image UNet has and this one does not: fp8 projections (wired for the image UNet only), LoRA routing (merged or
+        # low-rank), attn2.to_q + cross-attention as one launch
+        self.fp8 = self.fp8_chain_ff = self.fp8_attn_out = self.fp8_conv = False
+        self.fp8_tile = self.fp8_conv_tile = 0
+        self.row_sets, self.routed, self.lowrank, self._sets_dev = list(range(B)), False, False, None
+        self._qattn = False
         dev = self.dev
-        self.ops, self.keep, self.arena = [], [], _Arena(dev)
-        self.flops = self.gemm_flops = 0
-        self.launches = {"gemm": [], "conv": [], "attn": []}
-        self.op_meta = {}
-        self.fp8 = False                                 # (the fp8 projections are wired for the image UNet only)
-        self._tunable, self._ln_links, self._vt = [], [], {}
-        self._pf_prev, self._pf_on = None, not os.environ.get("TMIX_NO_PREFETCH")      # next-launch weight prefetch hints (UNetPlan._hint_weights)
-        self._pf_cap = int(float(os.environ.get("TMIX_PF_CAP_MB", "0")) * (1 << 20))    # (whole tensors: a clip's launches last 50 - 800 us, UNetPlan.__init__)
-        self._pf_cap_over = int(float(os.environ.get("TMIX_PF_CAP_OVER_MB", "20")) * (1 << 20))
         self.kv = _KV(W, context, frames)
         self.x_in = torch.zeros(B, 2 * cfg.in_channels, h, w, device=dev, dtype=F32)
         self.x_in.view(clips, frames, 2 * cfg.in_channels, h, w)[:, :, cfg.in_channels:] = il_feat.to(dev, F32).permute(0, 2, 1, 3, 4)
@@ -277,7 +265,10 @@ class I2VPlan(UNetPlan):
     CLIP_COLSTATS_MAX = int(os.environ.get("TMIX_CLIP_COLSTATS_MAX", "131072"))
 
     def _colstats(self, owner, rows, HW, Cc):
-        """as UNetPlan._colstats, for two kinds of readers: per-frame norms (HW pixels per image) and clip-wide norms (frames x HW rows per image)"""
+        """as UNetPlan._colstats, for two kinds of readers: per-frame norms (HW pixels per image) and clip-wide norms (frames x HW rows per image).
+        Where 32-row blocks fit the normalised image: the per-frame norms of the first two levels (5376 / 1344 pixels) and the clip-wide norms of
+        TemporalConvLayer / TransformerTemporalModel up to CLIP_COLSTATS_MAX rows (16 frames x HW is always a multiple of 32); per-frame norms of
+        336 / 84 pixels and the injection sites keep the statistics kernel."""
         R = ops.COLSTATS_ROWS
         chw = self.frames * HW
         ok = (HW % R == 0 and HW <= ops.COLSTATS_MAX_HW) or (chw % R == 0 and chw <= self.CLIP_COLSTATS_MAX)
@@ -467,66 +458,13 @@ class I2VPlan(UNetPlan):
         return self.eps.view(self.clips, self.frames, cfg.out_channels, self.h, self.w).permute(0, 2, 1, 3, 4)
 
 
-class I2VPlanGroup:
-    """the clips of one UNet call (the unconditional and the text row of the CFG pair) as independent launch chains on their own
-    HIP streams -- the same trick as the image sampler's PlanGroup: a dependent chain leaves the chip idle at every kernel
-    boundary, the other clip's chain fills the holes (measured 103 -> 97 ms per step at 16 x 768 x 448).  Interface of I2VPlan."""
-
-    def __init__(self, W: I2VWeights, clips: int, frames: int, h: int, w: int, fps_emb, context, il_feat, autotune: bool = True,
-                 interp: float = 0.7):
-        self.cfg, self.clips, self.frames, self.h, self.w = W.cfg, clips, frames, h, w
-        self.plans = [I2VPlan(W, 1, frames, h, w, fps_emb[i:i + 1], context[i:i + 1], il_feat[i:i + 1], autotune=autotune, interp=interp, shared=clips > 1)
-                      for i in range(clips)]
-        self.streams = [None] + [torch.cuda.Stream(device=W.device) for _ in range(clips - 1)]
-        self.eps = torch.zeros(clips * frames, W.cfg.out_channels, h, w, device=W.device, dtype=F32)
-        self.flops = sum(p.flops for p in self.plans)
-        self.ops = [op for p in self.plans for op in p.ops]
-
-    inject = property(lambda self: self.plans[0].inject, lambda self, v: [setattr(p, "inject", v) for p in self.plans])
-    interp = property(lambda self: self.plans[0].interp, lambda self, v: [setattr(p, "interp", v) for p in self.plans])
-
-    def refine(self, **kw):
-        return refine_group(self, **kw)
-
-    def set_input(self, sample, t):
-        """sample [clips,4,F,h,w] (or [1,...] broadcast to every clip)."""
-        c = self.cfg.in_channels
-        for i, p in enumerate(self.plans):
-            s = sample[i if sample.shape[0] > 1 else 0]
-            p.x_in.view(self.frames, 2 * c, self.h, self.w)[:, :c] = s.to(p.dev, F32).permute(1, 0, 2, 3)
-            p.t_dev.fill_(float(t))
-
-    def run(self):
-        main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        joins = []
-        for p, st in zip(self.plans[1:], self.streams[1:]):
-            st.wait_event(fork)
-            with torch.cuda.stream(st):
-                p.run()
-                ev = torch.cuda.Event()
-                ev.record(st)
-                joins.append(ev)
-        self.plans[0].run()
-        for ev in joins:
-            main.wait_event(ev)
-        n = self.frames
-        for i, p in enumerate(self.plans):
-            self.eps[i * n:(i + 1) * n].copy_(p.eps)
-
-    def __call__(self, sample, t):
-        self.set_input(sample, t)
-        self.run()
-        return self.eps.view(self.clips, self.frames, self.cfg.out_channels, self.h, self.w).permute(0, 2, 1, 3, 4)
-
-
 class I2VVideoPlan:
     """S videos in one UNet call, for tweediemix_amd.video.VideoSampler.  Conditioning rows [2S]: the S unconditional clips, then the
     S text clips (conditioning() of both halves in one call).  streams=2: two chains, I2VPlan(clips=S) per CFG half, each on its own
-    HIP stream (I2VPlanGroup's trick at S clips per chain); streams=1: one I2VPlan(clips=2S).  `halves` are the (input rows, timestep
-    input, prediction rows) of the unconditional and the text half; the sampler's kernels read and write them in place, so no copy
-    or permute sits between the chains and the step."""
+    HIP stream -- a dependent chain leaves the chip idle at every kernel boundary, the other half's chain fills the holes (as the image
+    sampler's PlanGroup; measured 103 -> 97 ms per step at one 16 x 768 x 448 video); streams=1: one I2VPlan(clips=2S).  `halves` are
+    the (input rows, timestep input, prediction rows) of the unconditional and the text half; the sampler's kernels read and write them
+    in place, so no copy or permute sits between the chains and the step."""
 
     def __init__(self, W: I2VWeights, videos: int, frames: int, h: int, w: int, fps_emb, context, il_feat, streams: int = 2,
                  autotune: bool = True, interp: float = 0.7):
@@ -552,17 +490,33 @@ class I2VVideoPlan:
         return refine_group(self, **kw)
 
     def run(self):
-        if len(self.plans) == 1:
-            self.plans[0].run()
-            return
-        main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        st = self.streams[1]
-        st.wait_event(fork)
-        with torch.cuda.stream(st):
-            self.plans[1].run()
-            join = torch.cuda.Event()
-            join.record(st)
-        self.plans[0].run()
-        main.wait_event(join)
+        run_chains(self.plans, self.streams)
+
+
+class I2VPlanGroup(I2VVideoPlan):
+    """the CFG pair of ONE video as two launch chains, I2VVideoPlan(videos=1, streams=2), with I2VPlan's interface: set_input /
+    __call__, and eps [2F, C, h, w] (unconditional clip first) gathered from the two chains at the end of every run."""
+
+    def __init__(self, W: I2VWeights, clips: int, frames: int, h: int, w: int, fps_emb, context, il_feat, autotune=True, interp=0.7):
+        assert clips == 2, "the CFG pair of one video"
+        super().__init__(W, 1, frames, h, w, fps_emb, context, il_feat, streams=2, autotune=autotune, interp=interp)
+        self.clips = clips
+        self.eps = torch.zeros(clips * frames, W.cfg.out_channels, h, w, device=W.device, dtype=F32)
+
+    def set_input(self, sample, t):
+        """sample [clips,4,F,h,w] (or [1,...] broadcast to every clip)."""
+        c = self.cfg.in_channels
+        for i, p in enumerate(self.plans):
+            s = sample[i if sample.shape[0] > 1 else 0]
+            p.x_in.view(self.frames, 2 * c, self.h, self.w)[:, :c] = s.to(p.dev, F32).permute(1, 0, 2, 3)
+            p.t_dev.fill_(float(t))
+
+    def run(self):
+        super().run()
+        for i, p in enumerate(self.plans):
+            self.eps[i * self.frames:(i + 1) * self.frames].copy_(p.eps)
+
+    def __call__(self, sample, t):
+        self.set_input(sample, t)
+        self.run()
+        return self.eps.view(self.clips, self.frames, self.cfg.out_channels, self.h, self.w).permute(0, 2, 1, 3, 4)

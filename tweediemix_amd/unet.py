@@ -431,7 +431,11 @@ class UNetPlan:
     def __init__(self, W: UNetWeights, B: int, h: int, w: int, kv: KVCache, pooled: torch.Tensor,
                  time_ids: torch.Tensor, routed: bool = False, autotune: bool = True, row_sets=None,
                  latent=None, eps=None, shared: bool = False, t_dev=None, fp8: bool = False, token_maps: TokenMapSpec | None = None):
-        self.W, self.cfg, self.B, self.h, self.w = W, W.cfg, B, h, w
+        # How much of a LARGE weight tensor a hint names (round 6, profiles/r6_experiments/weight_hint_cap_*.txt): a launch of a single-seed call lasts 20 - 90 us, and
+        # touching the 39 MB of a routed q/k/v weight (or FF1's 26 MB) inside it costs the hinting launch more than the hinted one gains -- tensors over 20 MB
+        # are named by their first 8 MB there (1 MB ... 12 MB measure the same; 13 MB tensors want all of themselves: capping those loses 0.5 - 1 ms).  The co-batched
+        # calls (launches of 0.2 - 1 ms) keep whole-tensor hints.  TMIX_PF_CAP_MB / TMIX_PF_CAP_OVER_MB override (cap 0: whole tensors everywhere).
+        self._init_emit_state(W, B, h, w, hint_policy(B, h, w))
         # fp8: the attn1 q/k/v, FF up- and down-projections run as tmix_gemm_fp8 (e4m3 operands, per-row power-of-two scales);
         # their A operand is quantised by one tmix_quantize_fp8_rows launch in front of the GEMM
         self.fp8 = bool(fp8)
@@ -453,16 +457,6 @@ class UNetPlan:
             assert not self.fp8, "low-rank LoRA runs the bf16 projections only"
             self.routed = False
             self._sets_dev = torch.tensor(self.row_sets, device=W.device, dtype=torch.int32)
-        self._rows_cache = {}
-        self.lib = L.load()
-        self.dev = W.device
-        self.ops = []
-        self.keep = []                      # descriptors / tensors that must outlive the plan
-        self.arena = _Arena(self.dev)
-        self.flops = 0
-        self.gemm_flops = 0
-        self.launches = {"gemm": [], "conv": [], "attn": []}
-        self.op_meta = {}                   # index into self.ops -> (class, flops, shape key) of the instrumented launches
         cfg = self.cfg
         assert kv.B == B
         dev = self.dev
@@ -478,7 +472,6 @@ class UNetPlan:
         self.aug = ops.linear_small(hid, W["add_embedding.linear_2.weight"], W["add_embedding.linear_2.bias"])
         torch.cuda.synchronize()
         self._gn_ws = ops.groupnorm_ws(B, 4096, cfg.norm_groups, dev)
-        self._vt = {}
         # LayerNorm row statistics travel from the GEMM that writes the hidden state to the GEMM behind the norm as
         # per-column-tile partial sums [parts][B*S][2]; launches on one stream are ordered, so all sites share one buffer
         nb = len(cfg.block_out_channels)
@@ -487,21 +480,6 @@ class UNetPlan:
             lvl = nb - 1 if pfx.startswith("mid") else int(pfx.split(".")[1]) if pfx.startswith("down") else nb - 1 - int(pfx.split(".")[1])
             need = max(need, ((cc + 127) // 128) * B * (h >> lvl) * (w >> lvl) * 2)
         self._ln_buf = torch.zeros(need, device=dev, dtype=F32)
-        # every GEMM / conv launch is preceded by a tmix_gemm_prefetch_next hint naming the weights of the launch AFTER it (patched in
-        # when that launch is planned): the chain otherwise meets every weight cold from HBM (TMIX_NO_PREFETCH=1 switches it off)
-        self._pf_prev = None
-        self._pf_on = not os.environ.get("TMIX_NO_PREFETCH")
-        # How much of a LARGE weight tensor a hint names (round 6, profiles/r6_experiments/weight_hint_cap_*.txt): a launch of a single-seed call lasts 20 - 90 us, and
-        # touching the 39 MB of a routed q/k/v weight (or FF1's 26 MB) inside it costs the hinting launch more than the hinted one gains -- tensors over 20 MB
-        # are named by their first 8 MB there (1 MB ... 12 MB measure the same; 13 MB tensors want all of themselves: capping those loses 0.5 - 1 ms).  The co-batched
-        # calls (launches of 0.2 - 1 ms) keep whole-tensor hints.  TMIX_PF_CAP_MB / TMIX_PF_CAP_OVER_MB override (cap 0: whole tensors everywhere).
-        self._pf_cap, self._pf_cap_over = hint_policy(B, h, w)
-        # GroupNorm statistics come from the launch that WRITES the normalised tensor (col_stats_out of the conv / proj_out epilogue), so a
-        # norm is two launches (combine partials, apply) and one pass over x instead of three and two (TMIX_GN_STATS_KERNEL=1: the old form)
-        self._gn_fused = not os.environ.get("TMIX_GN_STATS_KERNEL")
-        # conv_shortcut rides in conv2's K loop (tmix_conv_desc.S1 / S2): no shortcut GEMM, and the up-blocks' concatenations are never written
-        # (TMIX_SHORTCUT_GEMM=1: the separate GEMM + concat launches)
-        self._sc_fused = not os.environ.get("TMIX_SHORTCUT_GEMM")
         # attn2.to_q and the 77-key cross-attention behind it as ONE launch (tmix_gemm_q_cross_attn: no q round trip, 70 launches fewer per call); bf16 plans
         # with the merged / shared weights, five-head tiles (C % 320 == 0), <= 80 cached keys (TMIX_NO_QATTN=1: the two-launch form)
         self._qattn = not os.environ.get("TMIX_NO_QATTN") and not self.fp8 and not self.lowrank and kv.Lk <= 80 and kv.ld == 80
@@ -517,14 +495,42 @@ class UNetPlan:
             self._tok_arr = ops.token_array(tok)
             for l in lv:
                 self.token_maps[l] = torch.zeros(token_maps.n_rows, len(tok), (h >> l) * (w >> l), device=self.dev, dtype=F32)
-        self._tunable = []                  # (index into self.ops, kind, descriptor) of every GEMM / conv launch
-        self._ln_links = []                 # (producer desc, [consumer descs]): ln_parts follows the producer's tiling
         self._build()
         self._link_ln()
         if autotune:
             self.autotune()
         for m in self.token_maps.values():      # the tuner ran the forward (map launches included) on its own inputs
             m.zero_()
+
+    def _init_emit_state(self, W, B: int, h: int, w: int, hints):
+        """the state the op emitters below keep while a plan is recorded, for this plan and i2vgen.I2VPlan alike: op list, buffer arena,
+        launch bookkeeping, the tuner's lists, caches, weight-prefetch hints (hints = (cap, over) bytes, see hint_policy) and the feature
+        switches both networks share.  What differs between the two (fp8, LoRA routing, attn2 in one launch, tile-table context) each
+        constructor sets itself."""
+        self.W, self.cfg, self.B, self.h, self.w = W, W.cfg, B, h, w
+        self.lib = L.load()
+        self.dev = W.device
+        self.ops = []
+        self.keep = []                      # descriptors / tensors that must outlive the plan
+        self.arena = _Arena(self.dev)
+        self.flops = 0
+        self.gemm_flops = 0
+        self.launches = {"gemm": [], "conv": [], "attn": []}
+        self.op_meta = {}                   # index into self.ops -> (class, flops, shape key) of the instrumented launches
+        self._tunable = []                  # (index into self.ops, kind, descriptor) of every GEMM / conv launch
+        self._ln_links = []                 # (producer desc, [consumer descs]): ln_parts follows the producer's tiling
+        self._vt, self._rows_cache, self._attn_ws = {}, {}, {}      # V^T buffers, per-row weight sets, key-split workspaces (_attn)
+        # every GEMM / conv launch is preceded by a tmix_gemm_prefetch_next hint naming the weights of the launch AFTER it (patched in
+        # when that launch is planned): the chain otherwise meets every weight cold from HBM (TMIX_NO_PREFETCH=1 switches it off)
+        self._pf_prev = None
+        self._pf_on = not os.environ.get("TMIX_NO_PREFETCH")
+        self._pf_cap, self._pf_cap_over = hints
+        # GroupNorm statistics come from the launch that WRITES the normalised tensor (col_stats_out of the conv / proj_out epilogue), so a
+        # norm is two launches (combine partials, apply) and one pass over x instead of three and two (TMIX_GN_STATS_KERNEL=1: the old form)
+        self._gn_fused = not os.environ.get("TMIX_GN_STATS_KERNEL")
+        # conv_shortcut rides in conv2's K loop (tmix_conv_desc.S1 / S2): no shortcut GEMM, and the up-blocks' concatenations are never written
+        # (TMIX_SHORTCUT_GEMM=1: the separate GEMM + concat launches)
+        self._sc_fused = not os.environ.get("TMIX_SHORTCUT_GEMM")
 
     @staticmethod
     def _tune_key(kind, d):
@@ -550,7 +556,7 @@ class UNetPlan:
             self._link_ln()
             return
         keys = [self._tune_key(kind, d) for _i, kind, d in tun]
-        ctx = getattr(self, "tune_ctx", "")
+        ctx = self.tune_ctx
         lookup = lambda k: tune_lookup(ctx, k)
         if any(lookup(k) is None for k in keys):
             idx = {i: n for n, (i, _k, _d) in enumerate(tun)}
@@ -608,7 +614,7 @@ class UNetPlan:
     def _colstats(self, owner, rows, HW, Cc):
         """column-partials buffer [rows/32, 2, Cc] for the launch that writes `owner` ([B, HW, Cc]); it travels with the tensor (owner._cs, released
         with it) and _gn picks it up.  None when the geometry does not allow it (32-row blocks must not straddle images)."""
-        if not getattr(self, "_gn_fused", False) or HW % ops.COLSTATS_ROWS or HW > ops.COLSTATS_MAX_HW or rows % ops.COLSTATS_ROWS or Cc % 8:
+        if not self._gn_fused or HW % ops.COLSTATS_ROWS or HW > ops.COLSTATS_MAX_HW or rows % ops.COLSTATS_ROWS or Cc % 8:
             return None
         cs = self.arena.get(rows // ops.COLSTATS_ROWS, 2, Cc, dtype=F32)
         owner._cs = ((cs, Cc),)
@@ -617,7 +623,7 @@ class UNetPlan:
     def _gn_f8_ok(self, x, Cc, HW, x2=None):
         """can the GroupNorm over x (| x2) leave its result as e4m3 + row-major MX scales for tmix_conv3x3_nhwc_fp8?  fp8 plans, Cc % 128 == 0, and the
         statistics must come from the producers (the e4m3 output exists for tmix_groupnorm_nhwc_pre only)"""
-        if not (self.fp8 and getattr(self, "fp8_conv", False)) or Cc % 128 or HW % 32:
+        if not (self.fp8 and self.fp8_conv) or Cc % 128 or HW % 32:
             return False
         parts = getattr(x, "_cs", None)
         if x2 is not None:
@@ -827,14 +833,10 @@ class UNetPlan:
         # launch shape of this chain (launches of a chain are serial on its stream)
         ws = None
         if os.environ.get("TMIX_ATTN_SPLIT"):
-            wss = getattr(self, "_attn_ws", None)
-            if wss is None:
-                wss = {}
-                setattr(self, "_attn_ws", wss)
             wkey = (self.B, H, Sq, Skv)
-            if wkey not in wss:
-                wss[wkey] = ops.attention_split_ws(*wkey, q.device)
-            ws = wss[wkey]
+            if wkey not in self._attn_ws:
+                self._attn_ws[wkey] = ops.attention_split_ws(*wkey, q.device)
+            ws = self._attn_ws[wkey]
         wsa = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
         if f8_out is not None:
             args = (q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
@@ -883,7 +885,7 @@ class UNetPlan:
         return temb, 1
 
     def _sc_ok(self, Ci, Co, c1, c2=0):
-        return getattr(self, "_sc_fused", False) and Ci != Co and c1 % 64 == 0 and c2 % 64 == 0
+        return self._sc_fused and Ci != Co and c1 % 64 == 0 and c2 % 64 == 0
 
     def _resnet(self, x, Ci, Co, Hh, Ww, name, emb, x2=None):
         """x2: the block's input is the channel-concatenation [x | x2] (up-blocks; Ci counts both), which is never written: norm1 reads the two
@@ -1027,7 +1029,7 @@ class UNetPlan:
             # 64 x 320 per image = the 1024^2 latent's 32 x 32 level; the B = 2 calls there fill half the chip (128 tiles: 24.2 us against 23.1 + a kernel
             # boundary for the pair), smaller images (512^2: 32 / 16 tiles per image) keep the pair at every batch.
             lvl = self._probe_level(Hh)
-            if lvl is None and getattr(self, "_qattn", False) and Cc % 320 == 0 and S % 64 == 0 and (S // 64) * (Cc // 320) >= 64:
+            if lvl is None and self._qattn and Cc % 320 == 0 and S % 64 == 0 and (S // 64) * (Cc // 320) >= 64:
                 ao = A.get(B, S, Cc)
                 self._q_attn(h, a2 + ".q", self.kv.k[a2], self.kv.vt[a2], ao, S, Cc, st)
                 self._proj(ao, a2 + ".out", h, S, Cc, bias=W[a2 + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8, a_full=ao)
@@ -1086,7 +1088,7 @@ class UNetPlan:
         self._emit(self.lib.tmix_concat_channels, x1.data_ptr(), C1, x2.data_ptr(), C2, out.data_ptr(), self.B * HW)
         # the concatenation's column partials are those of its two sources: they move to it (and are released with it, not with x1 / x2)
         p1, p2 = getattr(x1, "_cs", None), getattr(x2, "_cs", None)
-        if getattr(self, "_gn_fused", False) and p1 and p2 and len(p1) == 1 and len(p2) == 1:
+        if self._gn_fused and p1 and p2 and len(p1) == 1 and len(p2) == 1:
             out._cs = (p1[0], p2[0])
             x1._cs = x2._cs = None
         return out
@@ -1302,7 +1304,7 @@ def refine_group(self, top=14, reps=9, verbose=False, cands=None, only_kind=None
             p._link_ln()
         if verbose:
             print(f"  refine {k}: {cur} -> {best}  ({base:.3f} -> {best_t:.3f} ms)", flush=True)
-        _TUNE_CACHE[getattr(members[k][0][0], "tune_ctx", "") + k] = best
+        _TUNE_CACHE[members[k][0][0].tune_ctx + k] = best
         base = best_t
     return base
 
@@ -1343,7 +1345,7 @@ def tilings_follow_table(plan):
     for p in _plans_of(plan):
         for _i, kind, d in p._tunable:
             k = p._tune_key(kind, d)
-            want = shipped(getattr(p, "tune_ctx", ""), k)
+            want = shipped(p.tune_ctx, k)
             if kind == "gemm" and (d.reserved0 & L.F8_COPY_OUT):
                 want = L.F8COPY_TILE_ALT.get(want, want)
             if want != d.tile_cfg:
@@ -1393,17 +1395,27 @@ class PlanGroup:
         return [m for p in self.plans[1:] + self.plans[:1] for m in p.issued_meta()]
 
     def run(self):
-        main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        joins = []
-        for p, st in zip(self.plans[1:], self.streams[1:]):
-            st.wait_event(fork)
-            with torch.cuda.stream(st):
-                p.run()
-                ev = torch.cuda.Event()
-                ev.record(st)
-                joins.append(ev)
-        self.plans[0].run()
-        for ev in joins:
-            main.wait_event(ev)
+        run_chains(self.plans, self.streams)
+
+
+def run_chains(plans, streams):
+    """enqueue independent launch chains: plans[i] for i >= 1 on streams[i], forked from and joined back into torch's current stream,
+    which runs plans[0].  Issue order: the side chains first, the main chain last, then the joins (PlanGroup.issued_meta and the
+    captured graphs follow it).  One plan: its chain alone, no fork and no events."""
+    if len(plans) == 1:
+        plans[0].run()
+        return
+    main = torch.cuda.current_stream()
+    fork = torch.cuda.Event()
+    fork.record(main)
+    joins = []
+    for p, st in zip(plans[1:], streams[1:]):
+        st.wait_event(fork)
+        with torch.cuda.stream(st):
+            p.run()
+            ev = torch.cuda.Event()
+            ev.record(st)
+            joins.append(ev)
+    plans[0].run()
+    for ev in joins:
+        main.wait_event(ev)

@@ -1,8 +1,9 @@
 """Host side of the video sampler's per-step path (BASELINE config #5): the denoising loop of
 video_gen/pipeline_i2vgen_xl.py:647-719 and the feature-injection schedule of video_gen/utils_attn.py:14-23,389-474, over
 the HIP kernels `tmix_vpred_step` and `tmix_frame_inject`.  The I2VGen-XL UNet itself (diffusers `I2VGenXLUNet`, not in
-/root/reference) is built natively in tweediemix_amd/i2vgen.py (I2VPlan / I2VPlanGroup); the loop here takes the network as a
-callable, so that plan (as run_video.py wires it) or any other module plugs in.
+the reference) is built natively in tweediemix_amd/i2vgen.py.  Two loops: `sample_loop`, the reference-shaped host loop, takes
+the network as a callable (any module plugs in; the tests check it against the oracle's loop), and `VideoSampler`, the loop
+run_video.py runs for one video or many, keeps the whole step of S videos on the device over an i2vgen.I2VVideoPlan.
 
 Quirks kept: alpha(t) indexes the UN-shifted alphas_cumprod (unlike the image sampler) and falls back to
 final_alpha_cumprod below 0 (:480-482); skip = 1000 // n (:647); the injection schedule is the first int(n * ratio)
@@ -92,14 +93,12 @@ class FeatureInjector:
 @torch.no_grad()
 def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None):
     """pipeline_i2vgen_xl.py:680-719.  unet(latent_model_input [2B,C,F,H,W], t) -> v-prediction of the same shape (the
-    caller closes over prompt/image conditioning); latents [B,C,F,H,W] on the GPU in the model dtype."""
+    caller closes over prompt/image conditioning; an i2vgen plan behind it needs its `inject` flag set for t, from
+    injection_active); latents [B,C,F,H,W] on the GPU in the model dtype."""
     x = latents.contiguous()
     for t in schedule.timesteps:
         if injector is not None:
             injector.register_time(t)
-            plan = getattr(unet, "plan", None)             # a native I2VPlan carries the injection as ops of its forward
-            if plan is not None:
-                plan.inject, plan.interp = injection_active(int(t), injector.schedule), injector.interp
         v = unet(torch.cat([x, x]), int(t)).contiguous()
         x = ops.vpred_step(x, v, guidance_scale, schedule.alpha(int(t)), schedule.alpha(int(t) - schedule.skip))
     return x
