@@ -139,13 +139,9 @@ enum { TMIX_TILE_AUTO = 0, TMIX_TILE_128x128_S2 = 1, TMIX_TILE_256x128_S3 = 2, T
        TMIX_TILE_128x160_S4_LW2 = 20 /* tiling 12 plus TWO loader waves (each issues every other LDS-DMA instruction of a K-tile) */,
        TMIX_TILE_128x160_S4_LW4 = 21 /* tiling 12 plus FOUR loader waves: one per SIMD, nine LDS-DMA instructions of a K-tile each */,
        TMIX_TILE_256x320_PH = 22 /* 256x320 with the phase-offset mainloop (eight waves of 64x160): bf16 GEMM, no transposed region */,
-       TMIX_TILE_128x160_W22 = 23 /* 128x160 over 2 x 2 math waves of 64x80 (16x16x32 MFMA) + four loader waves: 72 KB instead of 96 KB of LDS fragment reads per K-tile;
-                                      plain staged bf16 epilogue (bias, folded LayerNorm, residual, row statistics) -- other launches run as tiling 21 */,
-       /* ids 24 and 25 are RESERVED: two measured-and-rejected experiments (256x320 on persistent workgroups; tiling 23 with an L2 prefetcher wave) that only dev
-          builds contain (make EXPERIMENTAL=1, tools/build_variant.sh); the shipped library runs them as tilings 14 and 23, whose bits they reproduce */
-       TMIX_TILE_CONV_HALO = 26 /* tmix_conv3x3_nhwc only: stride-1 3x3 convolution on 4 x 32 pixel tiles with the (4 + 2) x (32 + 2) input patch of every 64-channel chunk resident
-                                   in LDS -- the nine taps are shifted fragment reads, the input travels L2 -> LDS 1.6 x instead of 9 x.  W %% 32 == 0, H %% 4 == 0, Cout %% 160 == 0, no shortcut
-                                   taps; other launches run as tiling 20 (a GEMM: 21).  Channel-chunk-major accumulation order (the other tilings: tap-major) */,
+       TMIX_TILE_128x160_W22 = 23 /* 128x160 over 2 x 2 math waves of 64x80 (16x16x32 MFMA) + four loader waves: plain staged bf16 epilogue, other launches run as tiling 21 */,
+       /* ids 24 and 25 are RESERVED (dev builds only: make EXPERIMENTAL=1); the shipped library runs them as tilings 14 and 23, whose bits they reproduce */
+       TMIX_TILE_CONV_HALO = 26 /* tmix_conv3x3_nhwc only: stride-1 3x3 convolution with the input halo patch in LDS; launches it cannot run go to tiling 20 (a GEMM: 21) -- tmix_conv_resolve_tile tells */,
        TMIX_TILE_COUNT = 26 };
 typedef struct {
     const void* A;  int64_t lda, strideA;        /* bf16 [batch][M][lda]                          */
@@ -188,6 +184,12 @@ typedef struct {
     int32_t w_period, reserved1;
 } tmix_gemm_desc;
 int tmix_gemm_bf16(const tmix_gemm_desc* d, void* stream);
+/* The tiling (1..TMIX_TILE_COUNT) of the kernel that tmix_gemm_bf16(d) -- fp8_operands != 0: tmix_gemm_fp8(d) with valid scale arrays -- would run: d->tile_cfg
+ * after AUTO, the retired / reserved ids and every substitution for what this launch needs (csrc/gemm_tilings.h).  The same validation and the same resolver
+ * as the launch itself; negative TMIX_E* where the launch would refuse.  Never touches the device.  tmix_conv_resolve_tile: the same for tmix_conv3x3_nhwc[_fp8]. */
+int tmix_gemm_resolve_tile(const tmix_gemm_desc* d, int fp8_operands);
+/* the tiling that runs tile_cfg for a bf16 GEMM that leaves an e4m3 copy (TMIX_F8_COPY_OUT), by the id alone; TMIX_EINVAL outside 1..TMIX_TILE_COUNT */
+int tmix_gemm_f8copy_tile(int tile_cfg);
 /* Hint for the NEXT tmix_gemm_bf16 / tmix_conv3x3_nhwc launch issued by this host thread (consumed and cleared by it): while its
  * workgroups wait for their own first operands they touch [next_weights, next_weights + bytes) -- one 4-byte load per 128-byte line, the
  * range split evenly over the grid -- so that the weights of the launch that FOLLOWS it are in the memory-side (Infinity) cache when that
@@ -270,6 +272,7 @@ int tmix_conv3x3_nhwc(const tmix_conv_desc* d, void* stream);
  * E8M0 scale per output channel (tmix_quantize_fp8_rows over the weight rows).  Cin %% 128 == 0 (a K-tile is 128 channels of one tap), no shortcut taps;
  * Y, bias, batch_bias, residual, col_stats_out as in tmix_conv3x3_nhwc.  tile_cfg: 12 or 20 (128x160 without / with two loader waves). */
 int tmix_conv3x3_nhwc_fp8(const tmix_conv_desc* d, const uint8_t* scale_x, const uint8_t* scale_w, void* stream);
+int tmix_conv_resolve_tile(const tmix_conv_desc* d, int fp8_operands);       /* see tmix_gemm_resolve_tile */
 
 /* conv_in: fp32 NCHW latent [B,4,H,W] -> bf16 NHWC [B,H,W,Cout] (Cout % 32 == 0); weights fp32 OHWI. */
 int tmix_conv_in(const float* x_nchw, const float* w_ohwi, const float* bias, void* y_nhwc,

@@ -219,6 +219,32 @@ def test_gemm_plain(ops, M, N, K, cfg):
     close(out, a.float() @ w.float().T)
 
 
+def test_every_tiling_runs_the_kernel_the_query_reports(ops):
+    """tmix_gemm_resolve_tile / tmix_conv_resolve_tile name the kernel a launch runs: for every id 1..26 (retired and reserved ones included) the launch under the
+    requested id and the launch under the reported id leave the same bits.  256 x 320 x 128 and 8 x 32 pixels x 160 channels: more than one tile of the 128-wide
+    tilings, whole tiles of the halo-patch kernel."""
+    import ctypes as C
+    from tweediemix_amd import lib as L
+    l = L.load()
+    a, w = rnd(256, 128, seed=71), rnd(320, 128, seed=72, scale=128 ** -0.5)
+    ref = a.float() @ w.float().T
+    x, wc = rnd(1, 8, 32, 64, seed=73), rnd(160, 3, 3, 64, seed=74, scale=(9 * 64) ** -0.5)
+    refc = F.conv2d(x.float().permute(0, 3, 1, 2), wc.float().permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1)
+    for cfg in range(1, L.TILE_COUNT + 1):
+        out = ops.gemm(a, w, tile_cfg=cfg)
+        d = ops.make_gemm_desc(a, w, out, tile_cfg=cfg)
+        runs = l.tmix_gemm_resolve_tile(C.byref(d), 0)
+        d.tile_cfg = runs
+        assert 1 <= runs <= L.TILE_COUNT and l.tmix_gemm_resolve_tile(C.byref(d), 0) == runs, (cfg, runs)
+        assert torch.equal(out, ops.gemm(a, w, tile_cfg=runs)), (cfg, runs)
+        close(out, ref)
+        y = ops.conv3x3(x, wc, tile_cfg=cfg)
+        runs = ops.conv_runs_as(ops.make_conv_desc(x, wc, y), cfg)
+        assert 1 <= runs <= L.TILE_COUNT and ops.conv_runs_as(ops.make_conv_desc(x, wc, y), runs) == runs, (cfg, runs)
+        assert torch.equal(y, ops.conv3x3(x, wc, tile_cfg=runs)), (cfg, runs)
+        close(y, refc)
+
+
 @pytest.mark.parametrize("cfg", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23])
 def test_gemm_epilogues(ops, cfg):
     M, N, K = 384, 640, 256

@@ -1,112 +1,128 @@
 // gemm_conv.hip -- host entry points of the bf16 / fp8 MFMA GEMM and the 3x3 NHWC implicit-GEMM convolution: argument
-// validation, descriptor -> kernel parameters, tiling switch.  The kernel lives in gemm_kernel.h and is instantiated per group
+// validation, descriptor -> kernel parameters, the resolver over the tilings of gemm_tilings.h, dispatch.  The kernel lives in gemm_kernel.h and is instantiated per group
 // of tilings in gemm_inst_*.hip.
 #include "gemm_kernel.h"
+#include "gemm_tilings.h"
 #include <stdlib.h>
 
 using namespace tmix_gemm;
 
-namespace {
+namespace tmix_gemm {
 
-int pick_cfg(const Params& p, int batch) {
-    // heuristic default (the plan builder can override per shape after timing the candidates):
-    // 256x128 when it still yields >= 3/4 of a CU wave, else 128x128.
-    const int64_t t2 = (int64_t)((p.M + 255) / 256) * ((p.N + 127) / 128) * batch;
-    return t2 >= 192 ? 2 : 1;
+bool f8_lockstep(int tile_cfg, int K, bool f8out) {
+    // rows of 128 K values; not for the e4m3 GEGLU output: its MX blocks of 32 output columns need wave tiles that are multiples of 64 weight rows wide -- the
+    // phase-offset tilings' 128 x 64; a 160-wide tile ends in the middle of a block
+    return tile_cfg >= 1 && tile_cfg <= NUM_CFG && tile_has(tile_cfg, CAP_F8_LOCKSTEP) && K % 128 == 0 && !f8out;
 }
 
-int launch(int conv, Params& p, int batch, int cfg, hipStream_t st) {
-    if (cfg <= 0 || cfg > NUM_CFG) cfg = pick_cfg(p, batch);
-    if (cfg == 8) cfg = 19; else if (cfg == 9) cfg = 2; else if (cfg == 10) cfg = 1; else if (cfg == 11) cfg = 4;   // round-1 loader-wave tilings, retired (3 waves / SIMD register budget: they spilled)
-    // 23 = 128x160 over 2 x 2 math waves of 64x80 (v_mfma_f32_16x16x32_bf16) + four loader waves (gemm_w22.hip): the staged plain bf16 epilogue only
-    // 26 = the halo-patch convolution (gemm_convh.hip): stride 1, bf16, 4 x 32 pixel tiles; anything it does not carry runs as the loader-wave tilings 20 (conv) / 21 (GEMM)
-    if (cfg == 26) { if (convh_eligible(p, conv, p.scaleA != nullptr)) return launch_convh(p, st); cfg = conv ? 20 : 21; }
-#ifdef TMIX_EXPERIMENTAL_TILINGS      // dev variants (make EXPERIMENTAL=1): 24 = 256x320 on persistent workgroups (gemm_ff1p.hip), 25 = tiling 23 with an L2 prefetcher wave,
-    // 27 (asked for as tile_cfg 27 through the 13 slot: TMIX_TILE13_NS2) = 64x160 over five waves with a TWO-deep ring, two workgroups per CU (VERDICT r5 item 6 i)
-    if (cfg == 23 || cfg == 25) { if (w22_eligible(p, conv, 0)) return launch_w22(p, batch, st, cfg == 25); cfg = conv ? 12 : 21; }
-    if (cfg == 24) { if (ff1p_eligible(p, conv, 0, batch)) return launch_ff1p(p, st); cfg = 14; }
-#else                                 // the shipped library: ids 24 / 25 are reserved and run as the tilings they were variants of (same bits)
-    if (cfg == 24) cfg = 14; else if (cfg == 25) cfg = 23;
-    if (cfg == 23) { if (w22_eligible(p, conv, 0)) return launch_w22(p, batch, st, 0); cfg = conv ? 12 : 21; }
-#endif
-    if (cfg == 6) cfg = 4;      // 256x256 over four waves (128x128 wave tiles) is retired: it spilled and lost everywhere; same tile shape over eight waves
-    if (p.n_trans_begin >= 0) {
-        int bm = 0, bn = 0;
-        tmix_gemm_tile_shape(cfg, &bm, &bn);
-        if (p.n_trans_begin % bn) cfg = 2;                                     // the boundary must fall on a tile edge (N = 3 x 320: 640)
-        if (!(p.wide & 4)) {                                                   // narrow (unstaged) transposed stores need square wave tiles
-            if (cfg == 4 || cfg == 5 || cfg == 7 || cfg >= 12) cfg = 2;      // (18 included)
-        }
+int f8copy_tile(int tile_cfg) {
+    if (tile_cfg < 1 || tile_cfg > NUM_CFG) TMIX_FAIL(TMIX_EINVAL, "gemm_f8copy_tile: tile_cfg=%d", tile_cfg);
+    // (every substitute keeps the tile width, and with it the number of row-statistics partials, except 256x320 -> 128x160)
+    int cfg = TILINGS[tile_cfg].runs_as;
+    while (!tile_has(cfg, CAP_F8C)) cfg = TILINGS[cfg].fb;
+    return cfg;
+}
+
+#define TMIX_REFUSE(code, ...) do { tmix_set_error(__VA_ARGS__); return TileChoice{0, 0, (code)}; } while (0)
+
+// Which kernel runs a launch with traits t that asks for tiling cfg.  The rules run in this order; each sees the id the ones before it left.
+TileChoice resolve_tile(const TileTraits& t, int cfg) {
+    const bool staged = t.n_trans_begin < 0 && (t.epilogue == TMIX_EPI_GEGLU ? (t.wide & 2) : (t.wide & 1));      // the staged plain / GEGLU epilogue, no transposed region
+    if (cfg <= 0 || cfg > NUM_CFG)        // AUTO: 256x128 when it still yields >= 3/4 of a CU wave, else 128x128
+        cfg = (int64_t)((t.M + 255) / 256) * ((t.N + 127) / 128) * t.batch >= 192 ? 2 : 1;
+    cfg = TILINGS[cfg].runs_as;           // retired and reserved ids
+    if (TILINGS[cfg].loop == OWN_KERNEL) {
+        if (cfg == 26 ? t.convh_ok : cfg == 24 ? t.ff1p_ok : t.w22_ok) return {cfg, 0, TMIX_OK};
+        cfg = t.conv ? TILINGS[cfg].fb_conv : TILINGS[cfg].fb;
     }
-    if (p.f8copy) {                // the e4m3 copy of C is compiled into the tilings that have registers to spare for it (F8C)
-        static const int alt[NUM_CFG + 1] = {0, 1, 2, 3, 4, 5, 4, 7, 7, 2, 1, 4, 12, 13, 12, 15, 16, 17, 18, 12, 12, 12, 12, 12, 12, 12, 12};
-        // (every substitute keeps the tile width, and with it the number of row-statistics partials, except 256x320 -> 128x160)
-        if (cfg == 14 && p.stats_out) TMIX_FAIL(TMIX_EINVAL, "gemm: the e4m3 copy is not compiled into tiling 14; with row_stats_out pick another tiling (the partial count depends on it)");
-        if (!((cfg == 19 || cfg == 20 || cfg == 21) && !conv && p.scaleA && p.K % 128 == 0)) cfg = alt[cfg];      // (the loader-wave tilings on e4m3 operands carry the copy themselves)
+    if (t.n_trans_begin >= 0) {
+        if (t.n_trans_begin % TILINGS[cfg].bn) cfg = 2;                        // the boundary must fall on a tile edge (N = 3 x 320: 640)
+        if (!(t.wide & 4) && !tile_has(cfg, CAP_NARROW_T)) cfg = 2;                // narrow (unstaged) transposed stores need square wave tiles
+    }
+    if (t.f8copy) {
+        if (cfg == 14 && t.stats_out) TMIX_REFUSE(TMIX_EINVAL, "gemm: the e4m3 copy is not compiled into tiling 14; with row_stats_out pick another tiling (the partial count depends on it)");
+        if (!(t.fp8 && !t.conv && TILINGS[cfg].lw && f8_lockstep(cfg, t.K, t.f8out))) cfg = f8copy_tile(cfg);      // (the loader-wave tilings on e4m3 operands carry the copy themselves)
     }
     int f8 = 0;
-    if (!conv && p.scaleA) {     // fp8 operands (tmix_gemm_fp8): the phase-offset loop only; 256x128 tiles for narrow N
-        f8 = p.ldScaleA ? 2 : 1;
+    if (!t.conv && t.fp8) {     // fp8 operands (tmix_gemm_fp8): a lock-step loop where asked for and possible, else the phase-offset loop -- 256x128 tiles for narrow N
+        f8 = t.fp8;
         const int asked = cfg;
-        // the lock-step loops on e4m3 operands (128 x 160 with / without loader waves, 256 x 320): rows of 128 K values
-        // (not for the e4m3 GEGLU output: its MX blocks of 32 output columns need wave tiles that are multiples of 64 weight rows wide -- the
-        // phase-offset tilings' 128 x 64; a 160-wide tile ends in the middle of a block)
-        if ((cfg == 12 || cfg == 19 || cfg == 20 || cfg == 21) && p.K % 128 == 0 && !p.f8out) {
+        if (f8_lockstep(cfg, t.K, t.f8out)) {
             f8 += 2;
             // the loader-wave instantiation at the 256-register limit of two waves per SIMD holds the staged plain / GEGLU epilogues only (the transposed and
             // narrow forms spill there, and scratch traffic would break the counted vmcnt): those launches run without loader waves
-            const bool staged = p.n_trans_begin < 0 && (p.epilogue == TMIX_EPI_GEGLU ? (p.wide & 2) : (p.wide & 1));
-            const bool lw = cfg != 12;
-            if (lw && !staged) cfg = 12;
+            if (TILINGS[cfg].lw && !staged) cfg = 12;
             // ... and the e4m3 copy of C in its straight-line form only (epilogue family 4: bf16 output, no activation, no row-group bias)
-            if (lw && p.f8copy && (p.epilogue != TMIX_EPI_NONE || p.rgb)) cfg = 12;
+            if (TILINGS[cfg].lw && t.f8copy && (t.epilogue != TMIX_EPI_NONE || t.rowgroup_bias)) cfg = 12;
         } else
-        cfg = (cfg == 17 || (cfg != 16 && (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256) * batch < 160)) ? 17 : 16;
-        if (f8 == 2 && cfg == 16 && p.K / 32 > f8_block_cap(256)) cfg = 17;    // the tile's block scales stay in LDS beside the ring
+        cfg = (cfg == 17 || (cfg != 16 && (int64_t)((t.M + 255) / 256) * ((t.N + 255) / 256) * t.batch < 160)) ? 17 : 16;
+        if (f8 == 2 && cfg == 16 && t.K / 32 > f8_block_cap(256)) cfg = 17;    // the tile's block scales stay in LDS beside the ring
         // the consumers of row_stats_out were told the partial count of the REQUESTED tiling (tmix_gemm_stats_parts): never change the width under them
-        int abm = 0, abn = 0, cbm = 0, cbn = 0;
-        tmix_gemm_tile_shape(asked, &abm, &abn); tmix_gemm_tile_shape(cfg, &cbm, &cbn);
-        if (p.stats_out && abn != cbn) TMIX_FAIL(TMIX_EINVAL, "gemm_fp8: tile_cfg %d cannot run this launch (K / 32 = %d block scales per row exceed the 256x256 tile's LDS budget); "
-                                                                "with row_stats_out request tile_cfg 17 explicitly", asked, p.K / 32);
+        if (t.stats_out && TILINGS[asked].bn != TILINGS[cfg].bn)
+            TMIX_REFUSE(TMIX_EINVAL, "gemm_fp8: tile_cfg %d cannot run this launch (K / 32 = %d block scales per row exceed the 256x256 tile's LDS budget); "
+                                     "with row_stats_out request tile_cfg 17 explicitly", asked, t.K / 32);
     }
-    if (conv && p.scaleA) {     // convolution on e4m3 operands: the 128 x 160 lock-step tilings, with two loader waves (20) or without (12)
+    if (t.conv && t.fp8) {      // convolution on e4m3 operands: the 128 x 160 lock-step tilings, with two loader waves (20) or without (12)
         f8 = 4;
-        cfg = (cfg == 20 || cfg == 21 || cfg == 19) ? 20 : 12;
-    } else
-    if (conv) {
-        // the phase-offset and loader-wave mainloops exist for the plain GEMM only (the im2col gather's per-row offset tables do
-        // not fit a loader wave's register budget, and the conv mainloop already runs at 0.8-1.0 PFLOP/s): nearest plain tiling
-        // (tiling 20 -- 128 x 160 plus TWO loader waves -- also exists for the convolution since the kernels are instantiated per epilogue family:
-        // 244 VGPRs, no scratch; not with shortcut taps, whose source switch lives in the staging path of the math waves' kernel)
-        if (cfg == 16) cfg = 4;
-        else if (cfg == 17) cfg = 2;
-        else if (cfg == 22) cfg = 14;
-        else if (cfg >= 18 && cfg != 20) cfg = 12;
-    } else if (cfg == 16 && !f8 && (p.K % 32)) cfg = 4;
+        cfg = (tile_has(cfg, CAP_F8_LOCKSTEP) && TILINGS[cfg].lw) ? 20 : 12;
+    } else if (t.conv) {
+        if (!tile_has(cfg, CAP_CONV)) cfg = TILINGS[cfg].fb_conv;                  // GEMM-only mainloops: the nearest plain tiling
+    } else if (cfg == 16 && !f8 && (t.K % 32)) cfg = 4;
     // 256x320 phase-offset: bf16, staged GEGLU / plain epilogues only (the transposed and narrow forms spill at its register count)
-    if (!conv && cfg == 22 && (f8 || p.n_trans_begin >= 0 || !(p.epilogue == TMIX_EPI_GEGLU ? (p.wide & 2) : (p.wide & 1)))) cfg = f8 ? 16 : 14;
-    // column statistics (cs_out) are compiled for the lock-step tilings only: the phase-offset ones run as their nearest plain tiling
-    if (p.cs_out) { if (cfg == 16) cfg = 4; else if (cfg == 17) cfg = 2; else if (cfg == 22) cfg = 14; }
-    int rc = f8 >= 3 ? -999 : launch_group0(cfg, conv, f8, p, batch, st);
-    if (rc == -999 && f8 < 3) rc = launch_group1(cfg, conv, f8, p, batch, st);
-    if (rc == -999 && f8 < 3) rc = launch_group2(cfg, conv, f8, p, batch, st);
-    if (rc == -999 && f8 < 3) rc = launch_group3(cfg, conv, f8, p, batch, st);
-    if (rc == -999) rc = launch_group4(cfg, conv, f8, p, batch, st);
-    if (rc == -999) rc = launch_group5(cfg, conv, f8, p, batch, st);
-    if (rc == -999) TMIX_FAIL(TMIX_EINVAL, "gemm: no kernel for tile_cfg %d", cfg);
-    return rc;
+    if (!t.conv && cfg == 22 && (f8 || !staged)) cfg = f8 ? 16 : 14;
+    // column statistics are compiled for the lock-step tilings only: the phase-offset ones run as their nearest plain tiling
+    if (t.cs_out && !tile_has(cfg, CAP_CS)) cfg = TILINGS[cfg].fb;
+    return {cfg, f8, TMIX_OK};
+}
+
+}  // namespace tmix_gemm
+
+namespace {
+
+TileTraits traits_of(int conv, const Params& p, int batch) {
+    TileTraits t = {};
+    t.conv = conv; t.fp8 = p.scaleA ? (p.ldScaleA ? 2 : 1) : 0;
+    t.n_trans_begin = p.n_trans_begin; t.wide = p.wide; t.epilogue = p.epilogue;
+    t.f8copy = p.f8copy; t.f8out = p.f8out; t.stats_out = p.stats_out; t.cs_out = p.cs_out; t.rowgroup_bias = p.rgb;
+    t.M = p.M; t.N = p.N; t.K = p.K; t.batch = batch;
+    t.w22_ok = w22_eligible(p, conv, 0); t.convh_ok = convh_eligible(p, conv, p.scaleA != nullptr);
+#ifdef TMIX_EXPERIMENTAL_TILINGS
+    t.ff1p_ok = ff1p_eligible(p, conv, 0, batch);
+#endif
+    return t;
+}
+
+int launch(int conv, Params& p, int batch, int tile_cfg, hipStream_t st) {
+    const TileChoice r = resolve_tile(traits_of(conv, p, batch), tile_cfg);
+    if (r.err) return r.err;
+    switch (r.cfg) {
+    case 23: return launch_w22(p, batch, st, 0);
+    case 26: return launch_convh(p, st);
+#ifdef TMIX_EXPERIMENTAL_TILINGS
+    case 24: return launch_ff1p(p, st);
+    case 25: return launch_w22(p, batch, st, 1);
+#endif
+    }
+    switch (r.f8 >= 3 ? 5 : TILINGS[r.cfg].group) {       // (group 5: the e4m3 lock-step forms of the CAP_F8_LOCKSTEP tilings)
+    case 0: return launch_group0(r.cfg, conv, r.f8, p, batch, st);
+    case 1: return launch_group1(r.cfg, conv, r.f8, p, batch, st);
+    case 2: return launch_group2(r.cfg, conv, r.f8, p, batch, st);
+    case 3: return launch_group3(r.cfg, conv, r.f8, p, batch, st);
+    case 4: return launch_group4(r.cfg, conv, r.f8, p, batch, st);
+    case 5: return launch_group5(r.cfg, conv, r.f8, p, batch, st);
+    }
+    return no_kernel(r.cfg);
 }
 
 }  // namespace
 
 extern "C" int tmix_gemm_tile_shape(int tile_cfg, int* bm, int* bn) {
-    static const int shape[NUM_CFG + 1][2] = {{0, 0}, {128, 128}, {256, 128}, {128, 128}, {256, 256}, {256, 128}, {256, 256}, {128, 160},
-                                              {128, 160}, {256, 128}, {128, 128}, {256, 256}, {128, 160}, {64, 160}, {256, 320}, {32, 160},
-                                              {256, 256}, {256, 128}, {128, 160}, {128, 160}, {128, 160}, {128, 160}, {256, 320}, {128, 160}, {256, 320}, {128, 160}, {128, 160}};
     if (tile_cfg < 1 || tile_cfg > NUM_CFG || !bm || !bn) TMIX_FAIL(TMIX_EINVAL, "gemm_tile_shape: tile_cfg=%d", tile_cfg);
-    *bm = shape[tile_cfg][0]; *bn = shape[tile_cfg][1];
+    *bm = TILINGS[tile_cfg].bm; *bn = TILINGS[tile_cfg].bn;
     return TMIX_OK;
 }
+
+extern "C" int tmix_gemm_f8copy_tile(int tile_cfg) { return f8copy_tile(tile_cfg); }
 
 extern "C" int tmix_gemm_stats_parts(int N, int tile_cfg) {
     int bm, bn;
@@ -114,8 +130,10 @@ extern "C" int tmix_gemm_stats_parts(int N, int tile_cfg) {
     return (N + bn - 1) / bn;
 }
 
-// fp8 = true: A / W hold OCP e4m3 bytes with one E8M0 scale per row (tmix_gemm_fp8); everything behind the main loop is shared
-static int gemm_entry(const tmix_gemm_desc* d, bool fp8, const uint8_t* scaleA, const uint8_t* scaleW, void* stream, const QAExtra* qa = nullptr) {
+// argument validation and descriptor -> kernel parameters, shared by the launch entry points and tmix_gemm_resolve_tile (which passes any aligned non-null
+// scale pointers: they are not dereferenced here).  fp8 = true: A / W hold OCP e4m3 bytes with one E8M0 scale per row (tmix_gemm_fp8); everything behind the
+// main loop is shared.  qa: the launch is tmix_gemm_q_cross_attn (C may be NULL)
+static int gemm_params(const tmix_gemm_desc* d, bool fp8, const uint8_t* scaleA, const uint8_t* scaleW, bool qa, Params& p) {
     if (!d || !d->A || !d->W) TMIX_FAIL(TMIX_EINVAL, "gemm: null descriptor/operand");
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0) TMIX_FAIL(TMIX_ESHAPE, "gemm: empty problem M=%d N=%d K=%d batch=%d", d->M, d->N, d->K, d->batch);
     if (d->K % BK) TMIX_FAIL(TMIX_ESHAPE, "gemm: K=%d must be a multiple of %d", d->K, BK);
@@ -137,7 +155,7 @@ static int gemm_entry(const tmix_gemm_desc* d, bool fp8, const uint8_t* scaleA, 
     if (d->epilogue == TMIX_EPI_F32OUT && (has_trans || (((uintptr_t)d->C) & 15))) TMIX_FAIL(TMIX_EINVAL, "gemm: fp32 output needs a 16-byte aligned C and no transposed region");
     if ((int64_t)d->M * d->lda >= (1ll << 31) || (int64_t)d->N * d->ldw >= (1ll << 31)) TMIX_FAIL(TMIX_ESHAPE, "gemm: operand extent exceeds 32-bit element offsets");
     if (d->w_period < 0 || (d->w_period > 0 && (d->batch % d->w_period))) TMIX_FAIL(TMIX_ESHAPE, "gemm: w_period=%d must divide batch=%d", d->w_period, d->batch);
-    Params p = {};
+    p = {};
     p.A = (const bf16_t*)d->A; p.lda = d->lda; p.strideA = d->strideA;
     // (w_period == batch is "every slice its own set": the plain strideW walk -- one group would make the magic divisor wrap to 1)
     const int wper = (d->w_period > 0 && d->w_period < d->batch) ? d->w_period : 0;
@@ -156,7 +174,7 @@ static int gemm_entry(const tmix_gemm_desc* d, bool fp8, const uint8_t* scaleA, 
     p.bytesA = (unsigned)(((int64_t)(d->M - 1) * d->lda + d->K) * el);
     p.bytesW = (unsigned)(((int64_t)(d->N - 1) * d->ldw + d->K) * el);
     if (fp8) {
-        const bool lockstep = (d->tile_cfg == 12 || (d->tile_cfg >= 19 && d->tile_cfg <= 21)) && d->K % 128 == 0 && !(d->reserved0 & TMIX_F8_GEGLU_OUT);
+        const bool lockstep = f8_lockstep(d->tile_cfg, d->K, d->reserved0 & TMIX_F8_GEGLU_OUT);
         if (d->tile_cfg != TMIX_TILE_AUTO && d->tile_cfg != 16 && d->tile_cfg != 17 && !lockstep)
             TMIX_FAIL(TMIX_EINVAL, "gemm_fp8: tile_cfg must be AUTO, 16 (256x256), 17 (256x128) or -- K %% 128 == 0, no e4m3 GEGLU output -- 12 / 19 / 20 / 21 (128x160 without / with one, two, four loader waves)");
         p.scaleA = scaleA; p.scaleW = scaleW; p.strideScaleA = d->strideA ? d->M : 0; p.strideScaleW = d->strideW ? d->N : 0;
@@ -208,8 +226,24 @@ static int gemm_entry(const tmix_gemm_desc* d, bool fp8, const uint8_t* scaleA, 
     if (p.f8out && !(p.wide & 2)) TMIX_FAIL(TMIX_EINVAL, "gemm_fp8: e4m3 GEGLU output needs the staged epilogue");
     if (p.f8copy && !(p.wide & 1)) TMIX_FAIL(TMIX_EALIGN, "gemm: the e4m3 copy needs the staged epilogue (16-byte aligned C / residual rows, N %% 8 == 0)");
     if (fp8 && has_trans && !(p.wide & 4)) TMIX_FAIL(TMIX_EALIGN, "gemm_fp8: the transposed region needs a 16-byte aligned Ct with ldct %% 8 == 0");
+    return TMIX_OK;
+}
+
+static int gemm_entry(const tmix_gemm_desc* d, bool fp8, const uint8_t* scaleA, const uint8_t* scaleW, void* stream, const QAExtra* qa = nullptr) {
+    Params p;
+    if (const int rc = gemm_params(d, fp8, scaleA, scaleW, qa != nullptr, p)) return rc;
     if (qa) return launch_qattn(p, *qa, d->batch, (hipStream_t)stream);
     return launch(0, p, d->batch, d->tile_cfg, (hipStream_t)stream);
+}
+
+// scale arrays of the tile queries: never read
+alignas(16) static const uint8_t NO_SCALES[16] = {};
+
+extern "C" int tmix_gemm_resolve_tile(const tmix_gemm_desc* d, int fp8_operands) {
+    Params p;
+    if (const int rc = gemm_params(d, fp8_operands != 0, fp8_operands ? NO_SCALES : nullptr, fp8_operands ? NO_SCALES : nullptr, false, p)) return rc;
+    const TileChoice r = resolve_tile(traits_of(0, p, d->batch), d->tile_cfg);
+    return r.err ? r.err : r.cfg;
 }
 
 // attn2.to_q (the projection described by d: A = hidden state rows, W = to_q weight, bias / folded LayerNorm as in tmix_gemm_bf16; d->C is not written) and
@@ -230,7 +264,7 @@ extern "C" int tmix_gemm_fp8(const tmix_gemm_desc* d, const uint8_t* scale_a, co
     return gemm_entry(d, true, scale_a, scale_w, stream);
 }
 
-static int conv_entry(const tmix_conv_desc* d, const uint8_t* scale_x, const uint8_t* scale_w, void* stream) {
+static int conv_params(const tmix_conv_desc* d, const uint8_t* scale_x, const uint8_t* scale_w, Params& p) {
     const bool fp8 = scale_x != nullptr;
     if (!d || !d->X || !d->Wt || !d->Y) TMIX_FAIL(TMIX_EINVAL, "conv3x3: null descriptor/operand");
     if (fp8 && (!scale_w || (d->Cin % 128) || d->S1 || d->S2 || (((uintptr_t)scale_x) & 3)))
@@ -242,7 +276,7 @@ static int conv_entry(const tmix_conv_desc* d, const uint8_t* scale_x, const uin
     if ((d->mode == TMIX_CONV_S2 || d->mode == TMIX_CONV_S2A) && ((d->H | d->W) & 1)) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: stride-2 needs even H,W");
     if (!aligned16(d->X) || !aligned16(d->Wt) || (((uintptr_t)d->Y) & 7)) TMIX_FAIL(TMIX_EALIGN, "conv3x3: pointer alignment");
     if ((d->bias && (((uintptr_t)d->bias) & 15)) || (d->batch_bias && (((uintptr_t)d->batch_bias) & 15))) TMIX_FAIL(TMIX_EALIGN, "conv3x3: bias alignment");
-    Params p = {};
+    p = {};
     p.H = d->H; p.Wd = d->W; p.Cin = d->Cin; p.mode = d->mode;
     p.ntaps = d->mode == TMIX_CONV_T3 ? 3 : 9;
     const bool half = d->mode == TMIX_CONV_S2 || d->mode == TMIX_CONV_S2A;
@@ -280,7 +314,20 @@ static int conv_entry(const tmix_conv_desc* d, const uint8_t* scale_x, const uin
             TMIX_FAIL(TMIX_EINVAL, "conv3x3: col_stats_out needs B*Ho*Wo %% 32 == 0, Cout %% 8 == 0 and 16-byte aligned Y / residual");
         p.cs_out = d->col_stats_out;
     }
+    return TMIX_OK;
+}
+
+static int conv_entry(const tmix_conv_desc* d, const uint8_t* scale_x, const uint8_t* scale_w, void* stream) {
+    Params p;
+    if (const int rc = conv_params(d, scale_x, scale_w, p)) return rc;
     return launch(1, p, 1, d->tile_cfg, (hipStream_t)stream);
+}
+
+extern "C" int tmix_conv_resolve_tile(const tmix_conv_desc* d, int fp8_operands) {
+    Params p;
+    if (const int rc = conv_params(d, fp8_operands ? NO_SCALES : nullptr, fp8_operands ? NO_SCALES : nullptr, p)) return rc;
+    const TileChoice r = resolve_tile(traits_of(1, p, 1), d->tile_cfg);
+    return r.err ? r.err : r.cfg;
 }
 
 extern "C" int tmix_conv3x3_nhwc(const tmix_conv_desc* d, void* stream) { return conv_entry(d, nullptr, nullptr, stream); }

@@ -12,7 +12,7 @@ int launch_group2(int cfg, int conv, int f8, Params& p, int batch, hipStream_t s
     if (cfg == 13) return conv ? launch_cs<64, 160, 1, 5, 4, 1>(p, batch, st) : launch_cs<64, 160, 1, 5, 4, 0>(p, batch, st);
 #endif
     if (!conv && cfg == 18) return launch_cs<128, 160, 4, 1, 4, 0, 0, 0, 2>(p, batch, st);     // tiling 12 + in-workgroup split-K
-    return -999;
+    return no_kernel(cfg);
 }
 
 }  // namespace tmix_gemm

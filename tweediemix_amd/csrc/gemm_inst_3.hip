@@ -10,7 +10,7 @@ int launch_group3(int cfg, int conv, int f8, Params& p, int batch, hipStream_t s
     if (!conv && cfg == 19) return launch_cs<128, 160, 4, 1, 3, 0, 1>(p, batch, st);
     if (cfg == 20) return conv ? launch_cs<128, 160, 4, 1, 4, 1, 2>(p, batch, st) : launch_cs<128, 160, 4, 1, 4, 0, 2>(p, batch, st);
     if (!conv && cfg == 21) return launch_cs<128, 160, 4, 1, 4, 0, 4>(p, batch, st);     // one loader per SIMD
-    return -999;
+    return no_kernel(cfg);
 }
 
 }  // namespace tmix_gemm

@@ -1605,37 +1605,7 @@ gemm_conv_kernel(const Params p) {
 }
 
 // ------------------------------------------------------------------------------------------- launch
-struct TileCfg { int bm, bn; };
-// cfg ids (tmix.h TMIX_TILE_*): 1 = 128x128 (4 waves, 2 stages, 2 WG/CU), 2 = 256x128 (8 waves, 3 stages),
-// 3 = 128x128 (4 waves, 4 stages, 1 WG/CU), 4 = 256x256 (8 waves, 2 stages)
-// 5 = 256x128 (4 waves of 128x64, 3 stages, 1 WG/CU), 6 = 256x256 (4 waves of 128x128, 2 stages, 1 WG/CU):
-// one wave per SIMD with a large register tile -- on this chip instructions of co-resident waves do not overlap on a
-// SIMD, so MFMA utilisation is set by MFMAs per non-MFMA instruction, i.e. by the wave tile.
-// 7 = 128x160 (4 waves of 32x160, 2 stages): N = 1280 / 640 split into 160-wide tiles gives exactly 256 / 512 tiles
-// for this path's M = 4096 / 16384 GEMMs, i.e. whole rounds on 256 CUs instead of 1.25 / 2.5.
-// 8..11 = tilings 7, 2, 1, 4 with one extra LOADER wave (wave specialisation, see gemm_conv_kernel); the 4-wave tilings
-// with 128-wide wave tiles (5, 6) have no registers for a fifth wave on one of the SIMDs
-// 12 = tiling 7 (128x160) with a 4-deep ring (one workgroup per CU, three K-tiles in flight: the in-sequence loop is bound by
-// memory latency x bytes in flight, and 160-wide tiles divide N = 1280 / 640 exactly)
-// 13 = 64x160 over FIVE waves (each 64x32), 4-deep ring: 2048 x 1280 -- the half-batch launches of the 32x32 level -- is
-// exactly 256 tiles, one per CU, where 128x128 leaves 96 CUs idle (160 tiles) and 128x160 half of them
-// 14 = 256x320 over eight waves (wave tile 64x160): the GEGLU up-projection 2048 x 10240 is exactly 256 tiles, where
-// 256x256 runs 320 (a quarter-full second round); 128x320 over four waves was tried and lost to 128x160 everywhere
-// 15 = 32x160 over five waves (each 32x32): 1024 x 1280 -- one batch row per chain, the CFG-pair calls -- is 256 tiles
-// (a 5-deep ring for 13 measured the same as the 4-deep one)
-// 16 = 256x256, 17 = 256x128 with the PHASE-OFFSET mainloop (PH: eight waves, K slices of 32 through a four-slot ring, the
-// second wave of every SIMD one barrier behind the first; GEMM only, no transposed region)
-// 18 = tiling 12 (128x160, 4-deep ring) with in-workgroup split-K over two wave groups (KS = 2): eight waves stage, GEMM only
-// 19 / 20 / 21 = tiling 12 (128x160, 4-deep ring) with one / two / FOUR LOADER waves next to the four math waves (GEMM only); with four
-// every SIMD hosts one math wave and one loader, and a K-tile's 36 LDS-DMA instructions are nine per loader
-// 22 = 256x320 with the PHASE-OFFSET mainloop (eight waves of 64x160; bf16 GEMM only): the lock-step 256x320 loop (14) stops all eight waves at every
-// K-tile hand-over -- 79 % of the MFMA rate with the LDS-DMA ablated -- where this one keeps one wave of every SIMD in its MFMA segment
-// 23 = 128x160 over 2 x 2 math waves of 64x80 on v_mfma_f32_16x16x32_bf16 + four loader waves (its own kernel: gemm_w22.hip)
-// 24 = 256x320 (tiling 14's tile and arithmetic) on PERSISTENT workgroups: one per CU walks its tiles, the next tile's first K-tile requested under the last one (gemm_ff1p.hip)
-// 25 = tiling 23 with the fourth loader wave as an L2 PREFETCHER (touches the tile's operand lines eight K-tiles ahead of the ring)
-// 26 = 3x3 stride-1 convolution with the input halo patch resident in LDS (4 x 32 pixel tiles, channel-chunk-major K loop; its own kernel: gemm_convh.hip)
-constexpr int NUM_CFG = 26;
-
+// (the tilings -- ids, tile shapes, what each is compiled for -- are described in gemm_tilings.h)
 template <int BM, int BN, int WM, int WN, int NS, int CONV, int LW = 0, int PH = 0, int KS = 1, int CS = 0, int EK = 0, int SC = 0>
 int launch_cfg(Params& p, int batch, hipStream_t st) {
     static_assert(KS == 1 || BM * BN * 4 <= NS * (BM + BN) * 128, "the split-K hand-over must fit in the staging ring");
@@ -1674,14 +1644,15 @@ int launch_cs(Params& p, int batch, hipStream_t st) {
         if (p.S1) return p.cs_out ? launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 1, 2, 1>(p, batch, st) : launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 0, 2, 1>(p, batch, st);
     }
     if constexpr (CSOK) { if (p.cs_out) return launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 1, 2>(p, batch, st); }         // (validated: plain staged epilogue)
-    if constexpr (LW && PH >= 4) { if (p.f8copy) return launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 0, 4>(p, batch, st); }   // (gemm_conv.hip:launch sends only straight-line launches here)
+    if constexpr (LW && PH >= 4) { if (p.f8copy) return launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 0, 4>(p, batch, st); }   // (gemm_conv.hip resolve_tile sends only straight-line launches here)
     if constexpr (!CONV) { if (no_trans && p.epilogue == TMIX_EPI_GEGLU && (p.wide & 2)) return launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 0, 1>(p, batch, st); }
     if (no_trans && p.epilogue != TMIX_EPI_GEGLU && (p.wide & 1)) return launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 0, 2>(p, batch, st);
     if constexpr (!CONV) { if (!no_trans && p.epilogue != TMIX_EPI_GEGLU && (p.wide & 1) && (p.wide & 4)) return launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 0, 3>(p, batch, st); }
     return launch_cfg<BM, BN, WM, WN, NS, CONV, LW, PH, KS, 0, 0>(p, batch, st);
 }
 
-// one launcher per group of tilings (defined in gemm_inst_<g>.hip); returns -999 when `cfg` is not in the group
+// one launcher per group of tilings (defined in gemm_inst_<g>.hip; gemm_tilings.h names the group of every tiling)
+inline int no_kernel(int cfg) { TMIX_FAIL(TMIX_EINVAL, "gemm: no kernel for tile_cfg %d", cfg); }
 int launch_group0(int cfg, int conv, int f8, Params& p, int batch, hipStream_t st);
 int launch_group1(int cfg, int conv, int f8, Params& p, int batch, hipStream_t st);
 int launch_group2(int cfg, int conv, int f8, Params& p, int batch, hipStream_t st);

@@ -68,6 +68,22 @@ def stats_parts(N, tile_cfg):
     return n
 
 
+def f8copy_tile(tile_cfg):
+    """the tiling the library runs in place of tile_cfg when a bf16 GEMM also leaves the e4m3 copy of its output (tmix_gemm_f8copy_tile)."""
+    n = L.load().tmix_gemm_f8copy_tile(int(tile_cfg))
+    return n if n > 0 else tile_cfg              # (AUTO and ids out of range pass through: the launch itself deals with them)
+
+
+def conv_runs_as(d, tile_cfg):
+    """the tiling of the kernel the bf16 convolution d (a ConvDesc) would run if it asked for tile_cfg (tmix_conv_resolve_tile); another id: tile_cfg is an alias."""
+    asked, d.tile_cfg = d.tile_cfg, int(tile_cfg)
+    n = L.load().tmix_conv_resolve_tile(C.byref(d), 0)
+    d.tile_cfg = asked
+    if n < 0:
+        L.check(n, "tmix_conv_resolve_tile")
+    return n
+
+
 def make_gemm_desc(a, w, out, bias=None, residual=None, rowgroup_bias=None, rows_per_group=0, geglu=False,
                    out_t=None, n_trans_begin=-1, tile_cfg=0, row_stats_out=None, ln_stats=None, ln_colsum=None,
                    ln_eps=1e-5, ln_parts=0, act=None, out_f32=None, ln_k=None, col_stats_out=None):

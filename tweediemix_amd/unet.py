@@ -563,11 +563,10 @@ class UNetPlan:
             st = torch.cuda.current_stream().cuda_stream
             best_t = {}                                             # (key, cfg) -> min over reps of the summed launch times
             cands = list(L.TILE_CANDIDATES)                         # (16 / 17 and the loader-wave tilings 19 / 20 exist for the plain GEMM only)
-            conv_alias = {16: 4, 17: 2, 18: 12, 19: 12, 21: 12, 22: 14, 23: 12, 24: 14, 25: 12}    # what gemm_conv.hip runs for a convolution: timed once, under the live id
             for _rep in range(reps):
                 for cfg in cands:
                     for _i, kind, d in tun:
-                        d.tile_cfg = cfg if kind == "gemm" else conv_alias.get(cfg, cfg)
+                        d.tile_cfg = cfg if kind == "gemm" else ops.conv_runs_as(d, cfg)      # (an alias is timed once, under the live id)
                     self._link_ln()
                     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in tun]
                     for i, (fn, args) in enumerate(self.ops):
@@ -585,8 +584,11 @@ class UNetPlan:
                         tot[k] = tot.get(k, 0.0) + ev[n][0].elapsed_time(ev[n][1])
                     for k, t in tot.items():
                         best_t[(k, cfg)] = min(best_t.get((k, cfg), float("inf")), t)
+            first = {}                                              # key -> one descriptor of that shape
+            for (_i, _kind, d), k in zip(tun, keys):
+                first.setdefault(k, d)
             for k in set(keys):
-                ok = [c for c in cands if k.startswith("('gemm'") or c not in conv_alias]
+                ok = [c for c in cands if k.startswith("('gemm'") or ops.conv_runs_as(first[k], c) == c]
                 if k not in _TUNE_CACHE:
                     _TUNE_CACHE[k] = min(ok, key=lambda c: best_t[(k, c)])
                 if SHARED + k not in _TUNE_CACHE:     # starting point for chains that share the chip (refine_group re-ranks under load)
@@ -796,9 +798,11 @@ class UNetPlan:
         return self._ln_buf[:pm * self.B * S * 2].view(pm, self.B * S, 2)
 
     def _link_ln(self):
-        for _i, kind, d in self._tunable:       # the tiling the library would substitute for a GEMM that leaves an e4m3 copy
+        # the tiling the library substitutes for a GEMM that leaves an e4m3 copy goes into the DESCRIPTOR, so the number of row-statistics partials
+        # the consumers are told is that of the kernel that really runs (and the library never meets tiling 14 with row_stats_out, which it refuses)
+        for _i, kind, d in self._tunable:
             if kind == "gemm" and (d.reserved0 & L.F8_COPY_OUT):
-                d.tile_cfg = L.F8COPY_TILE_ALT.get(d.tile_cfg, d.tile_cfg)
+                d.tile_cfg = ops.f8copy_tile(d.tile_cfg)
         for prod, cons in self._ln_links:
             parts = ops.stats_parts(prod.N, prod.tile_cfg)
             for c in cons:
@@ -1283,12 +1287,13 @@ def refine_group(self, top=14, reps=9, verbose=False, cands=None, only_kind=None
         cur = members[k][0][2].tile_cfg
         best, best_t = cur, base
         for cfg in (cands or L.TILE_CANDIDATES):
-            if cfg == cur or (cfg in L.TILE_EXCLUSIVE and len(plans) > 1) or (members[k][0][1] == "conv" and cfg in (16, 17, 18, 19, 21, 22, 23, 24, 25)):
+            _p0, kind0, d0 = members[k][0]
+            if cfg == cur or (cfg in L.TILE_EXCLUSIVE and len(plans) > 1):
                 continue
-            if cfg == L.TILE_CONV_HALO:               # the halo-patch kernel: convolutions it can run only (anything else would be timed under an alias of 20 / 21)
-                d0 = members[k][0][2]
-                if members[k][0][1] != "conv" or d0.mode != L.CONV_S1 or d0.S1_channels or d0.W % 32 or d0.H % 4 or d0.Cout % 160:
-                    continue
+            if kind0 == "conv" and ops.conv_runs_as(d0, cfg) != cfg:       # an alias: it would be timed under another id's kernel
+                continue
+            if cfg == L.TILE_CONV_HALO and (kind0 != "conv" or d0.S1_channels):      # policy: conv launches only, and not tried on convolutions with shortcut taps (the kernel runs them)
+                continue
             for p, _kind, d in members[k]:
                 d.tile_cfg = cfg
             for p in plans:
@@ -1316,7 +1321,7 @@ def _plans_of(plan):
 
 def used_tilings(plan):
     """{"gemm:<TMIX_TILE id>": launches, "conv:<id>": launches} of a UNetPlan / PlanGroup as it will be launched (descriptor
-    values; fp8 launches and the F8-copy substitutions of gemm_conv.hip:launch are resolved by the library, the descriptor
+    values; fp8 launches and the other substitutions of the resolver in gemm_conv.hip are made by the library, the descriptor
     holds the request).  bench.py prints it; the parity tests assert it for the plan they check against the oracle."""
     out = {}
     for p in _plans_of(plan):
@@ -1346,8 +1351,8 @@ def tilings_follow_table(plan):
         for _i, kind, d in p._tunable:
             k = p._tune_key(kind, d)
             want = shipped(p.tune_ctx, k)
-            if kind == "gemm" and (d.reserved0 & L.F8_COPY_OUT):
-                want = L.F8COPY_TILE_ALT.get(want, want)
+            if kind == "gemm" and (d.reserved0 & L.F8_COPY_OUT) and want is not None:
+                want = ops.f8copy_tile(want)
             if want != d.tile_cfg:
                 bad.append((k, d.tile_cfg, want))
     return not bad, bad
