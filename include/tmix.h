@@ -119,6 +119,8 @@ int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_fra
  * per-row concept weights of utils_custom.py:64-83 / utils_lora.py:65-79,113-119 (batch with
  * strideW != 0 selects one weight set per batch row).
  * Requirements: K % 64 == 0, lda/ldw % 8 == 0, 16-byte aligned pointers.
+ * Rows of A behind M (the next slice's rows, a neighbouring tensor) and the columns [K, lda) / [K, ldw) may hold any bit pattern, NaN included: the loads of
+ * a slice are bounded by its own extent ((M - 1) * lda + K elements), and nothing behind it reaches a result.
  */
 enum { TMIX_EPI_NONE = 0, TMIX_EPI_GEGLU = 1, TMIX_EPI_F32OUT = 2 /* C is fp32 [M][ldc] (attention scores of the VAE) */,
        TMIX_EPI_GELU = 3 /* gelu(acc + bias), erf form (OpenCLIP-bigG MLP) */,
@@ -294,6 +296,8 @@ int tmix_conv_out(const void* x_nhwc, const void* w_ohwi, const float* bias, flo
  *   Vt [B][H*64][ldvt] V TRANSPOSED (row = h*64+d, column = key); ldvt >= Skv rounded up to 8 and
  *                      the padding columns must hold finite values
  *   O  [B][Sq][ldo]
+ * Rows of K behind Skv and rows of Q behind Sq of a slice may hold any bit pattern, NaN included: key and query indices past the last real row are clamped to
+ * it (or not loaded at all) and what they give is masked by selection (the same holds for tmix_gemm_q_cross_attn and tmix_xattn_token_maps).
  */
 int tmix_attn_fwd(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK,
                   const void* Vt, int64_t ldvt, int64_t strideVt, void* O, int64_t ldo, int64_t strideO,
