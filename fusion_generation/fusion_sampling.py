@@ -23,6 +23,13 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          there is no tokenizer; --attn_mask_threshold, --save_attention_maps (raw maps as .npy).  Each rank
                          writes the masks it used as '<seg_concept>.jpg' into its side-car directory.  --mask_paths and
                          --random_masks still win over it
+  --keep_latents FILE    hold an earlier result while the loop samples only the --reroll regions anew: FILE is the '.latent.pt' a run
+                         wrote ([1,4,h,w] of this resolution).  Needs --mask_paths (the regions must be known before the first step) and
+                         --reroll; everything outside the regions comes back bit for bit in the final latent.  With --num_seeds N every
+                         seed re-rolls the same regions of the same image, sharing every UNet launch
+  --keep_image FILE      the same with an RGB image of exactly resolution_w x resolution_h: kept is the VAE encoder's mean times the scaling
+                         factor (nothing is drawn).  Excludes --keep_latents
+  --reroll LIST          the regions sampled anew: '+'-separated --seg_concepts phrases or 0-based indices into them ('a dog', '1', '0+a dog')
   --num_seeds N          N trajectories, seeds seed..seed+N-1 (trajectory i is exactly what `--seed seed+i` alone produces: its
                          x_T comes from its own generator), co-batched --seeds_per_batch at a time
   --gpus G               shard those seeds round-robin over G GPUs of this node: the script starts one process per GPU itself
@@ -86,6 +93,9 @@ def build_parser():
     p.add_argument('--mask_token_ids', type=str, default='',
                    help="token positions per foreground concept, '+' between concepts, ',' within one (e.g. '4+7')")
     p.add_argument('--save_attention_maps', action='store_true')
+    p.add_argument('--keep_latents', type=str, default='', help="'.latent.pt' of an earlier run: kept outside the --reroll regions")
+    p.add_argument('--keep_image', type=str, default='', help='RGB image of resolution_w x resolution_h: its VAE encoding is kept outside the --reroll regions')
+    p.add_argument('--reroll', type=str, default='', help="regions sampled anew: '+'-separated --seg_concepts phrases or 0-based indices into them")
     p.add_argument('--num_seeds', type=int, default=1, help='trajectories to sample: seeds seed..seed+n-1')
     p.add_argument('--seeds_per_batch', type=int, default=0, help='seeds co-batched into every UNet launch (0: all of this rank\'s seeds, at most 4)')
     p.add_argument('--gpus', type=int, default=1, help='shard the seeds over this many GPUs (one process per GPU, started by this script)')
@@ -152,6 +162,92 @@ def noise_for_seed(seed, h, w):
     return torch.randn(1, 4, h, w, generator=torch.Generator().manual_seed(int(seed)))
 
 
+def keep_noise_for_seed(seed, h, w):
+    """the fixed noise of a seed's kept region: the SECOND tensor of that seed's generator, behind its x_T (noise_for_seed), so that a
+    seed's x_T is what it is without a keep region"""
+    g = torch.Generator().manual_seed(int(seed))
+    torch.randn(1, 4, h, w, generator=g)
+    return torch.randn(1, 4, h, w, generator=g)
+
+
+def parse_reroll(spec, seg_concepts):
+    """'a dog+0' with --seg_concepts 'a cat+a dog' -> [0, 1]: every entry is one of the phrases or a 0-based index into them"""
+    names = [c for c in seg_concepts.split('+') if c]
+    out = []
+    for e in (e.strip() for e in spec.split('+')):
+        if e in names and e:
+            i = names.index(e)
+        elif e.isdigit() and int(e) < len(names):
+            i = int(e)
+        else:
+            raise SystemExit(f"--reroll {spec!r}: {e!r} is neither one of the --seg_concepts phrases {names} nor an index below {len(names)}")
+        if i in out:
+            raise SystemExit(f"--reroll {spec!r}: region {i} ({names[i]!r}) is named twice")
+        out.append(i)
+    return sorted(out)
+
+
+def keep_weight(masks, reroll):
+    """[1,1,h,w] weight of the KEPT part from the blend masks [K,1,h,w] (masks.build_masks: foreground masks, then the background):
+    1 - min(1, sum of the re-rolled regions' foreground masks)"""
+    return (1.0 - masks[list(reroll)].sum(dim=0, keepdim=True).clamp(max=1.0)).contiguous()
+
+
+def check_keep_args(opt):
+    """None for a run without a keep region, else dict(reroll=[indices], latent=[1,4,h,w] or None, image=PIL RGB or None); refuses what
+    such a run cannot do (before anything touches the GPU)."""
+    if not (opt.keep_latents or opt.keep_image):
+        if opt.reroll:
+            raise SystemExit('--reroll names the regions to sample anew inside a kept image: it needs --keep_latents or --keep_image')
+        return None
+    if opt.keep_latents and opt.keep_image:
+        raise SystemExit('--keep_latents and --keep_image are mutually exclusive: one kept image per run')
+    flag = '--keep_latents' if opt.keep_latents else '--keep_image'
+    if not opt.mask_paths:
+        raise SystemExit(f'{flag} needs --mask_paths: the kept region must be known before the first step '
+                         f'(masks acquired during the run -- side-car, --mask_source attention, --random_masks -- come too late)')
+    if not opt.reroll:
+        raise SystemExit(f"{flag} needs --reroll: which of the --seg_concepts regions to sample anew (e.g. --reroll 1)")
+    reroll = parse_reroll(opt.reroll, opt.seg_concepts)
+    n_masks = len(opt.mask_paths.split('+'))
+    if max(reroll) >= n_masks:
+        raise SystemExit(f'--reroll {opt.reroll!r}: region {max(reroll)} has no mask, --mask_paths holds {n_masks}')
+    path = opt.keep_latents or opt.keep_image
+    if not os.path.isfile(path):
+        raise SystemExit(f'{flag} {path!r}: no such file')
+    h, w = opt.resolution_h // 8, opt.resolution_w // 8
+    keep = dict(reroll=reroll, latent=None, image=None)
+    if opt.keep_latents:
+        lat = torch.load(path, map_location='cpu')
+        if not (torch.is_tensor(lat) and tuple(lat.shape) == (1, 4, h, w)):
+            got = tuple(lat.shape) if torch.is_tensor(lat) else type(lat).__name__
+            raise SystemExit(f'--keep_latents {path!r} holds {got}; this run (resolution {opt.resolution_w} x {opt.resolution_h}) needs a [1, 4, {h}, {w}] latent')
+        keep['latent'] = lat.float()
+    else:
+        if not (opt.vae_path or (opt.sd_path and os.path.isdir(os.path.join(opt.sd_path, 'vae'))) or (opt.synthetic and opt.tiny)):
+            raise SystemExit('--keep_image needs the VAE encoder: give --vae_path (or --sd_path with a vae/ folder)')
+        from PIL import Image
+        im = Image.open(path)
+        if im.size != (opt.resolution_w, opt.resolution_h):
+            raise SystemExit(f'--keep_image {path!r} is {im.size[0]} x {im.size[1]}; it must be exactly resolution_w x resolution_h = '
+                             f'{opt.resolution_w} x {opt.resolution_h}')
+        keep['image'] = im.convert('RGB')
+    return keep
+
+
+def encode_keep_image(image, vae, scaling_factor, device, synthetic=False):
+    """the kept latent of --keep_image: the VAE encoder's MEAN times the factor decode_final divides by (deterministic: no sample is drawn)"""
+    from tweediemix_amd import vae as V, video as VI
+    vcfg, sd = vae
+    if 'encoder.conv_in.weight' not in sd:
+        if not synthetic:
+            raise SystemExit('--keep_image: the VAE weights hold no encoder (encoder.* / quant_conv.*)')
+        sd = V.synthetic_state_dict(vcfg, encoder=True)
+    plan = V.VAEEncoderPlan(vcfg, sd, 1, image.size[1], image.size[0], device)
+    mean, _logvar = plan(VI.vae_pixel_values(image).to(device))
+    return mean * scaling_factor
+
+
 def parse_token_ids(spec):
     """'4,5+7' -> [[4, 5], [7]]"""
     try:
@@ -181,6 +277,7 @@ def main(argv=None):
     opt = build_parser().parse_args(argv)
     if opt.dtype == 'fp8' and opt.lora_mode == 'lowrank':
         raise SystemExit('--dtype fp8 quantises the merged per-concept projection weights: use --lora_mode merged')
+    keep = check_keep_args(opt)
     from tweediemix_amd import dist as D, launch as LA, masks as M, sampler as S, unet as U, weights as Wt
     if opt.gpus > 1 and not LA.launched():
         return LA.self_launch(opt.gpus)
@@ -289,11 +386,17 @@ def main(argv=None):
         # read the masks back; without one the mask files must already be there
         tw.mask_provider = M.SidecarMaskProvider(tw, side_dir, opt.seg_concepts, seg_gpu=side_gpu,
                                                  cmd_template=os.environ.get('TMIX_SEG_CMD'))
+    if keep is not None:                                  # one kept latent and one weight, shared by every seed of every batch
+        keep_x0 = keep['latent'] if keep['latent'] is not None else \
+            encode_keep_image(keep['image'], vae, tw.vae_scaling_factor, opt.device, synthetic=opt.synthetic)
+        keep_w = keep_weight(M.build_masks(fg, h, w, opt.device), keep['reroll'])
     lats, imgs = [], []
     for b0 in range(0, len(seeds), per):
         batch = seeds[b0:b0 + per]
         ids = (batch + batch * per)[:per]                # a ragged last batch is padded with repeats and trimmed below
         current["ids"], current["turn"] = ids, 0
+        if keep is not None:
+            tw.set_keep(keep_x0, keep_w, torch.cat([keep_noise_for_seed(sd_, h, w) for sd_ in ids]))
         lat_b = tw.run_fusion(torch.cat([noise_for_seed(sd_, h, w) for sd_ in ids]))
         lats.append(lat_b[:len(batch)])
         if attn is not None:

@@ -81,6 +81,23 @@ int tmix_fused_tweedie_step(const float* x, const void* eps, int eps_dtype, cons
 int tmix_fused_tweedie_step_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
                                 int64_t mask_seed_stride, float* out_x, float* out_x0, int K, int channels,
                                 int64_t hw, int mode, int rows, int seeds, const float* params, void* stream);
+/* tmix_fused_tweedie_step_dev with a KEEP REGION (no reference counterpart: the reference can only re-sample a whole image): part of the
+ * latent is held at a given clean latent while the loop runs on the rest -- re-roll one concept of a finished image, or sample concepts
+ * into a template image.  Everything tmix_fused_tweedie_step_dev takes, same order, same meaning, then per seed
+ *   keep_x0  [n]   fp32 clean latent to hold        keep_eps [n] fp32 its fixed noise        keep_w [hw] fp32 weight of the kept part in [0, 1]
+ *   (broadcast over the channels); seed s reads each array at s * its seed stride, 0 = one array shared by all seeds, otherwise >= n (hw).
+ * After x0 and moved = sa_next*x0 + s1_next*e0 of the mode (unchanged), per element i with w = keep_w[i % hw]:
+ *   kept   = is_last ? keep_x0[i] : sa_next*keep_x0[i] + s1_next*keep_eps[i]        new = is_last ? x0 : moved
+ *   out_x  = w*kept + (1 - w)*new                 out_x0 = w*keep_x0[i] + (1 - w)*x0
+ * in fp32, two products and one sum each, not contracted: w = 0 gives exactly new (tmix_fused_tweedie_step_dev's result), w = 1 exactly
+ * kept.  The kept part is thus always at the noise level of the state it is written into (sa_next / s1_next come from params: one captured
+ * launch serves every timestep).  x may alias out_x; the keep arrays alias no output.  TMIX_EINVAL on a null keep pointer, TMIX_ESHAPE on
+ * a non-zero seed stride shorter than its extent; otherwise the checks of tmix_fused_tweedie_step_dev. */
+int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                     int64_t mask_seed_stride, float* out_x, float* out_x0, int K, int channels,
+                                     int64_t hw, int mode, int rows, int seeds, const float* params,
+                                     const float* keep_x0, int64_t keep_x0_seed_stride, const float* keep_eps,
+                                     int64_t keep_eps_seed_stride, const float* keep_w, int64_t keep_w_seed_stride, void* stream);
 /* Head of the captured step (fusion_sampling.py:324-327, `latent_model_input = torch.cat([x] * rows)`, and the timestep
  * argument of the UNet call :340): latent[(s*rows + r)][n] = x[s][n] for every row r, t_dev[s*rows + r] = params[0]. */
 int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,

@@ -31,17 +31,30 @@ template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float
 // DEV = 1: the step coefficients come from a device buffer prm = {t, sa, s1, sa_next, s1_next, is_last, g} (so ONE captured
 // launch serves every timestep of a hipGraph replay) and blockIdx.y walks co-batched seeds (x / out: [seeds][n], eps:
 // [seeds][rows][n], masks: [seeds][K][hw] or shared).  x may alias out_x: element i is read before it is written.
-template <int DT, int MODE, int DEV = 0>
+// KEEP (with DEV): a region of the latent is held at a given clean latent kp.x0 re-noised with its own fixed noise kp.eps to the level
+// of the state the step writes; kp.w [hw] (broadcast over the channels) is the weight of the held part.  Seed sd reads its arrays at
+// sd * stride (0: shared by all seeds).  The mode's x0 / moved are computed exactly as without it.  The flag is the presence of ONE
+// trailing KeepArgs kernel argument (the pack KeepT is empty or {KeepArgs}): without it the kernel has the arguments, and compiles to
+// the instructions, it had before the keep region existed.
+struct KeepArgs { const float* x0; const float* eps; const float* w; int64_t x0_stride, eps_stride, w_stride; };
+__device__ __forceinline__ KeepArgs keep_args(const KeepArgs& k) { return k; }
+
+template <int DT, int MODE, int DEV = 0, typename... KeepT>
 __global__ void __launch_bounds__(256)
 tweedie_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
                     const float* __restrict__ masks, float* out_x, float* __restrict__ out_x0,
                     int K, int64_t n, int64_t hw, float g, float sa, float s1, float sa_n, float s1_n, int is_last,
-                    const float* __restrict__ prm = nullptr, int rows = 0, int64_t mask_seed_stride = 0) {
+                    const float* __restrict__ prm = nullptr, int rows = 0, int64_t mask_seed_stride = 0, KeepT... keep) {
+    constexpr bool KEEP = sizeof...(KeepT) != 0;
+    static_assert(!KEEP || DEV, "the keep region exists in the device-parameter form only");
+    KeepArgs kp = {};
+    if constexpr (KEEP) kp = keep_args(keep...);
     if constexpr (DEV) {
         sa = prm[1]; s1 = prm[2]; sa_n = prm[3]; s1_n = prm[4]; is_last = prm[5] != 0.0f; g = prm[6];
         const int64_t sd = blockIdx.y;
         x += sd * n; out_x += sd * n; eps += sd * rows * n; masks += sd * mask_seed_stride;
         if (out_x0) out_x0 += sd * n;
+        if constexpr (KEEP) { kp.x0 += sd * kp.x0_stride; kp.eps += sd * kp.eps_stride; kp.w += sd * kp.w_stride; }
     }
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -68,8 +81,16 @@ tweedie_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps
             }
         }
         const float moved = sa_n * x0 + rnd<DT>(s1_n * eu);
-        out_x[i] = is_last ? x0 : moved;
-        if (out_x0) out_x0[i] = x0;
+        if constexpr (KEEP) {   // fp32, two products and one sum each (-ffp-contract=off); w in {0, 1} gives exactly kept or exactly new
+            const float kx = kp.x0[i], w = kp.w[i % hw];
+            const float kept = is_last ? kx : sa_n * kx + s1_n * kp.eps[i];
+            const float nw = is_last ? x0 : moved;
+            out_x[i] = w * kept + (1.0f - w) * nw;
+            if (out_x0) out_x0[i] = w * kx + (1.0f - w) * x0;
+        } else {
+            out_x[i] = is_last ? x0 : moved;
+            if (out_x0) out_x0[i] = x0;
+        }
     }
 }
 
@@ -107,6 +128,25 @@ int launch_dev(const float* x, const void* eps, const float* masks, int64_t mss,
         tweedie_step_kernel<DT, TMIX_STEP_PLAIN, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss); break;
     default:
         tweedie_step_kernel<DT, TMIX_STEP_RESAMPLE, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss); break;
+    }
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+template <int DT>
+int launch_keep(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, int K, int64_t n,
+                int64_t hw, int mode, int rows, int seeds, const float* prm, const KeepArgs& kp, hipStream_t st) {
+    typedef typename EpsT<DT>::T T;
+    int64_t bx = (n + 255) / 256; if (bx > 2048) bx = 2048;
+    const dim3 grid((unsigned)bx, (unsigned)seeds);
+    const T* e = (const T*)eps;
+    switch (mode) {
+    case TMIX_STEP_FUSION:
+        tweedie_step_kernel<DT, TMIX_STEP_FUSION, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss, kp); break;
+    case TMIX_STEP_PLAIN:
+        tweedie_step_kernel<DT, TMIX_STEP_PLAIN, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss, kp); break;
+    default:
+        tweedie_step_kernel<DT, TMIX_STEP_RESAMPLE, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss, kp); break;
     }
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
@@ -296,6 +336,34 @@ extern "C" int tmix_fused_tweedie_step_dev(const float* x, const void* eps, int 
     case TMIX_BF16: return launch_dev<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, st);
     }
     TMIX_FAIL(TMIX_EINVAL, "tweedie_step_dev: bad eps dtype %d", eps_dtype);
+}
+
+extern "C" int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                                int64_t mask_seed_stride, float* out_x, float* out_x0, int K, int channels,
+                                                int64_t hw, int mode, int rows, int seeds, const float* params,
+                                                const float* keep_x0, int64_t keep_x0_seed_stride, const float* keep_eps,
+                                                int64_t keep_eps_seed_stride, const float* keep_w, int64_t keep_w_seed_stride, void* stream) {
+    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: null pointer");
+    if (!keep_x0 || !keep_eps || !keep_w) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: null keep pointer");
+    if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: bad mode %d", mode);
+    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: FUSION needs masks and K>=1");
+    if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: RESAMPLE needs K>=1");
+    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_keep_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
+    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
+    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_keep_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
+    const int64_t n = (int64_t)channels * hw;
+    if ((keep_x0_seed_stride != 0 && keep_x0_seed_stride < n) || (keep_eps_seed_stride != 0 && keep_eps_seed_stride < n) ||
+        (keep_w_seed_stride != 0 && keep_w_seed_stride < hw))
+        TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_keep_dev: keep seed strides %lld / %lld / %lld: 0 (shared) or >= %lld / %lld / %lld floats",
+                  (long long)keep_x0_seed_stride, (long long)keep_eps_seed_stride, (long long)keep_w_seed_stride, (long long)n, (long long)n, (long long)hw);
+    const KeepArgs kp = {keep_x0, keep_eps, keep_w, keep_x0_seed_stride, keep_eps_seed_stride, keep_w_seed_stride};
+    hipStream_t st = (hipStream_t)stream;
+    switch (eps_dtype) {
+    case TMIX_F32:  return launch_keep<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
+    case TMIX_F16:  return launch_keep<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
+    case TMIX_BF16: return launch_keep<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
+    }
+    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: bad eps dtype %d", eps_dtype);
 }
 
 extern "C" int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,

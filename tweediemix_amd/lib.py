@@ -62,6 +62,8 @@ SIGNATURES = {
                                           f32, f32, f32, f32, f32, C.c_int, vp]),
     "tmix_fused_tweedie_step_dev": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int,
                                               C.c_int, vp, vp]),
+    "tmix_fused_tweedie_step_keep_dev": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int,
+                                                   C.c_int, vp, vp, i64, vp, i64, vp, i64, vp]),
     "tmix_step_prologue": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, i64, vp]),
     "tmix_gemm_bf16": (C.c_int, [C.POINTER(GemmDesc), vp]),
     "tmix_gemm_prefetch_next": (C.c_int, [vp, i64, vp]),

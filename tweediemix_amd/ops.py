@@ -61,6 +61,35 @@ def fused_tweedie_step(x, eps, masks, mode, K, g, at, at_next, is_last=False, ou
     return out_x
 
 
+def _seed_stride(t, seeds, extent, what):
+    """seed stride of a keep array [1 or seeds, ..., extent floats]: 0 when one array is shared by all seeds"""
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] in (1, seeds) and t.numel() == t.shape[0] * extent, (what, tuple(t.shape))
+    return 0 if t.shape[0] == 1 else extent
+
+
+def fused_tweedie_step_keep_dev(x, eps, masks, mode, K, params, keep_x0, keep_eps, keep_w, out_x=None, out_x0=None):
+    """tmix_fused_tweedie_step_keep_dev: x [S,C,h,w] fp32, eps [S*rows,C,h,w] f32|f16|bf16, masks [K,1,h,w] or [S,K,1,h,w] (FUSION),
+    params the device buffer {t, sa, s1, sa_next, s1_next, is_last, g, -}; keep_x0 [1|S,C,h,w], keep_eps [1|S,C,h,w], keep_w [1|S,1,h,w]
+    (first axis 1: shared by all seeds).  out_x may be x itself (in place).  Returns out_x."""
+    _need_cuda(x, eps, masks, params, keep_x0, keep_eps, keep_w)
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and params.dtype == torch.float32 and params.numel() >= 8
+    S, Cc, h, w = x.shape
+    n, hw = Cc * h * w, h * w
+    assert eps.shape[0] % S == 0
+    rows = eps.shape[0] // S
+    mss = 0
+    if mode == L.STEP_FUSION:
+        assert masks is not None and masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() in (K * hw, S * K * hw)
+        mss = 0 if masks.numel() == K * hw else K * hw
+    if out_x is None:
+        out_x = torch.empty_like(x)
+    L.check(L.load().tmix_fused_tweedie_step_keep_dev(
+        _p(x), _p(eps), _EPS_DT[eps.dtype], _p(masks), mss, _p(out_x), _p(out_x0), K, Cc, hw, mode, rows, S, _p(params),
+        _p(keep_x0), _seed_stride(keep_x0, S, n, "keep_x0"), _p(keep_eps), _seed_stride(keep_eps, S, n, "keep_eps"),
+        _p(keep_w), _seed_stride(keep_w, S, hw, "keep_w"), _stream()), "tmix_fused_tweedie_step_keep_dev")
+    return out_x
+
+
 def stats_parts(N, tile_cfg):
     """number of row-statistics partials a GEMM of width N writes with tiling tile_cfg (tmix_gemm_stats_parts)."""
     n = L.load().tmix_gemm_stats_parts(int(N), int(tile_cfg))

@@ -10,6 +10,8 @@ Same method names, argument meaning and step semantics as fusion_generation/fusi
   cache,
 * CFG + Tweedie + blend + DDIM done by ONE kernel (tmix_fused_tweedie_step_dev) that updates the latent
   state in place,
+* optionally a KEEP REGION (set_keep / clear_keep): part of the latent held at a given clean latent, re-noised inside the same kernel
+  (tmix_fused_tweedie_step_keep_dev) to the level of every state the loop writes,
 * ONE hipGraph per (call kind, step mode) holding the whole step -- latent broadcast + timestep
   (tmix_step_prologue), the UNet launch chains, the fused step for all co-batched seeds: a timestep is one 32-byte
   parameter upload and one graph replay.
@@ -136,6 +138,7 @@ class Tweediemix:
         self.x0_state = torch.zeros_like(self.x_state)
         self._x_backup = torch.zeros_like(self.x_state)
         self.step_params = torch.zeros(8, device=self.device, dtype=F32)      # {t, sa, s1, sa_next, s1_next, is_last, g, -}
+        self._keep = self._keep_bufs = None    # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
         # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it
         # has completed (the host runs ahead of the device by whole steps)
         self._hp = torch.zeros(64, 8, dtype=F32)
@@ -144,6 +147,39 @@ class Tweediemix:
         self._hp_ev = [None] * self._hp.shape[0]
         self._hp_i = 0
         self._mask_buf = None            # fixed-address copy of self.masks that the captured fusion step reads
+
+    # ------------------------------------------------------------------ keep region
+    def set_keep(self, x0, weight, eps):
+        """Hold part of the latent while the loop samples the rest (re-roll one concept of a finished image, or sample into a template image).
+        x0 [1 or S,4,h,w] the clean latent to hold, weight [1 or S,1,h,w] in [0, 1] the weight of the kept part (1: held, 0: sampled), eps [S,4,h,w]
+        the fixed noise of every seed's kept part.  From the next run_fusion / sample_loop on every step writes
+        weight * (sa' x0 + s1' eps) + (1 - weight) * (its own result), with sa' / s1' of the state it writes (tmix_fused_tweedie_step_keep_dev),
+        x_T is composited the same way once, and the final latent holds x0 itself.  The tensors are copied: captured steps read these buffers."""
+        S = self.n_seeds
+        want = (("x0", x0, 4), ("weight", weight, 1), ("eps", eps, 4))
+        for name, t, c in want:
+            lead = (S,) if name == "eps" else (1, S)
+            if t.dim() != 4 or t.shape[0] not in lead or tuple(t.shape[1:]) != (c, self.h, self.w):
+                raise ValueError(f"set_keep: {name} is {tuple(t.shape)}, expected [{' or '.join(map(str, lead))}, {c}, {self.h}, {self.w}]")
+        new = [t.to(self.device, F32).contiguous() for _n, t, _c in want]
+        if self._keep_bufs is not None and all(a.shape == b.shape for a, b in zip(self._keep_bufs, new)):
+            for a, b in zip(self._keep_bufs, new):
+                a.copy_(b)
+        else:                            # other shapes (shared <-> per seed): new buffers, and the steps captured on the old ones go
+            for k in [k for k in self.graphs if len(k) == 3]:
+                del self.graphs[k]
+            self._keep_bufs = [t.clone() for t in new]
+        self._keep = tuple(self._keep_bufs)
+
+    def clear_keep(self):
+        """back to plain sampling: the plain steps (and their graphs) are used again; the buffers stay for the next set_keep"""
+        self._keep = None
+
+    def _composite_keep(self, t):
+        """x_state <- w (sa x0 + s1 eps) + (1 - w) x_state at the noise level of timestep t: once, on x_T"""
+        kx, kw, ke = self._keep
+        sa, s1, _, _ = ops.step_coeffs(self.alpha(t), self.alpha(t))
+        self.x_state.copy_(kw * (sa * kx + s1 * ke) + (1.0 - kw) * self.x_state)
 
     # ------------------------------------------------------------------ schedule
     def alpha(self, t):
@@ -235,12 +271,22 @@ class Tweediemix:
         L.check(lib.tmix_step_prologue(self.x_state.data_ptr(), p.latent.data_ptr(), p.t_dev.data_ptr(),
                                        self.step_params.data_ptr(), S, rows, n, st), "tmix_step_prologue")
         p.run()
+        self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st)
+
+    def _fused_step(self, eps_ptr, eps_dt, rows, mode, st):
+        """the fused step for every seed, in place on x_state; with a keep region set (set_keep) through the entry that holds it"""
+        lib = L.load()
         m = self._mask_buf if mode == L.STEP_FUSION else None
         mss = 0 if (m is None or m.dim() == 4) else self.concept_num * self.h * self.w
-        L.check(lib.tmix_fused_tweedie_step_dev(self.x_state.data_ptr(), p.eps.data_ptr(), L.F32, None if m is None else m.data_ptr(),
-                                                mss, self.x_state.data_ptr(), self.x0_state.data_ptr(), self.concept_num, 4,
-                                                self.h * self.w, mode, rows, S, self.step_params.data_ptr(), st),
-                "tmix_fused_tweedie_step_dev")
+        hw = self.h * self.w
+        head = (self.x_state.data_ptr(), eps_ptr, eps_dt, None if m is None else m.data_ptr(), mss, self.x_state.data_ptr(),
+                self.x0_state.data_ptr(), self.concept_num, 4, hw, mode, rows, self.n_seeds, self.step_params.data_ptr())
+        if self._keep is None:
+            L.check(lib.tmix_fused_tweedie_step_dev(*head, st), "tmix_fused_tweedie_step_dev")
+            return
+        kx, kw, ke = self._keep
+        L.check(lib.tmix_fused_tweedie_step_keep_dev(*head, kx.data_ptr(), 0 if kx.shape[0] == 1 else 4 * hw, ke.data_ptr(), 4 * hw,
+                                                     kw.data_ptr(), 0 if kw.shape[0] == 1 else hw, st), "tmix_fused_tweedie_step_keep_dev")
 
     def _run_step(self, kind, mode, t, at, at_next, is_last=False):
         """x_state <- step(x_state) for every seed; x0_state <- the Tweedie estimate.  Host work per step: eight floats."""
@@ -264,18 +310,15 @@ class Tweediemix:
             # a stand-in UNet was attached to this instance (tests replay recorded eps; a caller may plug the reference's own
             # module in): the same fused step, eagerly, on whatever eps dtype the stand-in returns
             eps = self._unet(kind, self.x_state, t).contiguous()
-            S = self.n_seeds
-            m = self._mask_buf if mode == L.STEP_FUSION else None
-            mss = 0 if (m is None or m.dim() == 4) else self.concept_num * self.h * self.w
-            L.check(L.load().tmix_fused_tweedie_step_dev(
-                self.x_state.data_ptr(), eps.data_ptr(), ops._EPS_DT[eps.dtype], None if m is None else m.data_ptr(), mss,
-                self.x_state.data_ptr(), self.x0_state.data_ptr(), self.concept_num, 4, self.h * self.w, mode, eps.shape[0] // S, S,
-                self.step_params.data_ptr(), torch.cuda.current_stream().cuda_stream), "tmix_fused_tweedie_step_dev")
+            self._fused_step(eps.data_ptr(), ops._EPS_DT[eps.dtype], eps.shape[0] // self.n_seeds, mode,
+                             torch.cuda.current_stream().cuda_stream)
             return
         if not self.use_graphs:
             self._enqueue_step(kind, mode)
             return
-        g = self.graphs.get((kind, mode))
+        # a step captured with a keep region is another graph (another kernel, three more pointers): the ones captured without it stay valid
+        gkey = (kind, mode) if self._keep is None else (kind, mode, "keep")
+        g = self.graphs.get(gkey)
         if g is None:
             self._enqueue_step(kind, mode)                # warm-up outside capture (kernel attributes, lazy module load);
             torch.cuda.synchronize()                      # it has already performed this step, so no replay now
@@ -284,7 +327,7 @@ class Tweediemix:
             with torch.cuda.graph(g):
                 self._enqueue_step(kind, mode)
             self.x_state.copy_(keep)                      # capture does not execute, but keep the state explicit
-            self.graphs[(kind, mode)] = g
+            self.graphs[gkey] = g
             return
         g.replay()
 
@@ -428,6 +471,8 @@ class Tweediemix:
         """runs every scheduler timestep; returns the final latent, or the decoded image [n,3,H,W] in [0,1] when
         decode=True and VAE weights were given (fusion_sampling.py:496-528)."""
         self.x_state.copy_(x)
+        if self._keep is not None:
+            self._composite_keep(self.scheduler.timesteps[0])
         for t in self.scheduler.timesteps:
             self._denoise_inplace(t)
         x = self.x_state.clone()
