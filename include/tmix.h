@@ -264,11 +264,20 @@ int tmix_gemm_stats_parts(int N, int tile_cfg);
  * [clips][frames][h*w][Cin] and Wt [Cout][3][Cin] (diffusers TemporalConvLayer's Conv3d of the I2VGen-XL UNet, config #5). */
 /* TMIX_CONV_S2A: stride 2 with the zero padding on the right / bottom edge only (diffusers Downsample2D(padding=0) of the VAE ENCODER:
  * F.pad(x, (0,1,0,1)) then a stride-2 conv), out[y][x] = sum w[ky][kx] in[2y+ky][2x+kx]. */
-enum { TMIX_CONV_S1 = 0, TMIX_CONV_S2 = 1, TMIX_CONV_UP2 = 2, TMIX_CONV_T3 = 3, TMIX_CONV_S2A = 4 };
+/* TMIX_CONV_UP2F: TMIX_CONV_UP2 with the nearest x2 upsampling FOLDED into the weights.  The three rows a 3x3 window touches on the upsampled image come
+ * from two source rows (output row 2 sy + fy reads source rows sy-1, sy, sy for fy = 0 and sy, sy, sy+1 for fy = 1; columns alike), so each of the four
+ * output phases (fy, fx) is a 2x2 convolution of the SOURCE image whose weights are sums of 1, 2 or 4 of the 3x3 taps: K = 4 Cin instead of 9 Cin, and the
+ * zero padding is the same (merged taps lie inside the image, lone taps outside exactly where the upsampled coordinate does).  Wt is
+ * [4][Cout][2][2][Cin], phase = 2 fy + fx major, tap (ky, kx) of phase (fy, fx) reading source pixel (sy - 1 + fy + ky, sx - 1 + fx + kx): row taps
+ * {ky=0}, {ky=1,2} for fy = 0 and {ky=0,1}, {ky=2} for fy = 1 of the 3x3 kernel.  Y is the same dense [B][2H][2W][Cout] tensor; bias, batch_bias and
+ * col_stats_out as for the other modes (col_stats_out blocks are 32 rows of the launch's phase-major row order ((b*4 + phase)*H + sy)*W + sx: an image's
+ * blocks are still its own and contiguous).  H * W must be a multiple of the row count of the tile that runs the launch (TMIX_ESHAPE otherwise:
+ * tmix_conv_resolve_tile says so without launching), W >= 2; no residual, no shortcut taps, bf16 operands only (TMIX_EINVAL). */
+enum { TMIX_CONV_S1 = 0, TMIX_CONV_S2 = 1, TMIX_CONV_UP2 = 2, TMIX_CONV_T3 = 3, TMIX_CONV_S2A = 4, TMIX_CONV_UP2F = 5 };
 typedef struct {
     const void* X;   /* bf16 [B][H][W][Cin]                                   */
-    const void* Wt;  /* bf16 [Cout][3][3][Cin]  ([Cout][3][Cin] for T3)       */
-    void*       Y;   /* bf16 [B][Ho][Wo][Cout]  Ho = H (S1), H/2 (S2), 2H (UP2) */
+    const void* Wt;  /* bf16 [Cout][3][3][Cin]  ([Cout][3][Cin] for T3, [4][Cout][2][2][Cin] for UP2F) */
+    void*       Y;   /* bf16 [B][Ho][Wo][Cout]  Ho = H (S1), H/2 (S2), 2H (UP2, UP2F) */
     const float* bias;           /* fp32 [Cout] or NULL                       */
     const float* batch_bias;     /* fp32 [B][Cout] (time embedding) or NULL   */
     const void* residual;        /* bf16 like Y or NULL                       */

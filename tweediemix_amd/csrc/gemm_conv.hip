@@ -272,16 +272,21 @@ static int conv_params(const tmix_conv_desc* d, const uint8_t* scale_x, const ui
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: empty problem");
     if (d->Cin % BK) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: Cin=%d must be a multiple of %d", d->Cin, BK);
     if (d->Cout % 4) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: Cout=%d must be a multiple of 4", d->Cout);
-    if (d->mode < TMIX_CONV_S1 || d->mode > TMIX_CONV_S2A) TMIX_FAIL(TMIX_EINVAL, "conv3x3: bad mode %d", d->mode);
+    if (d->mode < TMIX_CONV_S1 || d->mode > TMIX_CONV_UP2F) TMIX_FAIL(TMIX_EINVAL, "conv3x3: bad mode %d", d->mode);
+    const bool fold = d->mode == TMIX_CONV_UP2F;      // nearest x2 folded into four 2x2 phase convolutions: Wt [4][Cout][2][2][Cin], K = 4 Cin
+    if (fold && (fp8 || d->residual || d->S1 || d->S2)) TMIX_FAIL(TMIX_EINVAL, "conv3x3: the folded upsampling mode takes bf16 operands, no residual and no shortcut taps");
+    if (fold && (d->W < 2 || (int64_t)d->H * d->W * d->W >= (1ll << 32))) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: the folded upsampling mode needs W >= 2 and H * W * W < 2^32");
     if ((d->mode == TMIX_CONV_S2 || d->mode == TMIX_CONV_S2A) && ((d->H | d->W) & 1)) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: stride-2 needs even H,W");
     if (!aligned16(d->X) || !aligned16(d->Wt) || (((uintptr_t)d->Y) & 7)) TMIX_FAIL(TMIX_EALIGN, "conv3x3: pointer alignment");
     if ((d->bias && (((uintptr_t)d->bias) & 15)) || (d->batch_bias && (((uintptr_t)d->batch_bias) & 15))) TMIX_FAIL(TMIX_EALIGN, "conv3x3: bias alignment");
     p = {};
     p.H = d->H; p.Wd = d->W; p.Cin = d->Cin; p.mode = d->mode;
-    p.ntaps = d->mode == TMIX_CONV_T3 ? 3 : 9;
+    p.ntaps = d->mode == TMIX_CONV_T3 ? 3 : (fold ? 4 : 9);
+    if (fold) { p.up_hw = d->H * d->W; p.up_magic = (unsigned)((1ull << 32) / (unsigned)d->W) + 1u; }
     const bool half = d->mode == TMIX_CONV_S2 || d->mode == TMIX_CONV_S2A;
-    p.Ho = half ? d->H / 2 : (d->mode == TMIX_CONV_UP2 ? d->H * 2 : d->H);
-    p.Wo = half ? d->W / 2 : (d->mode == TMIX_CONV_UP2 ? d->W * 2 : d->W);
+    const bool up = d->mode == TMIX_CONV_UP2 || fold;
+    p.Ho = half ? d->H / 2 : (up ? d->H * 2 : d->H);
+    p.Wo = half ? d->W / 2 : (up ? d->W * 2 : d->W);
     const int64_t M = (int64_t)d->B * p.Ho * p.Wo;
     if (M > 0x7fffffff / 4) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: too many output pixels");
     if ((int64_t)d->B * d->H * d->W * d->Cin >= (1ll << 30) || (int64_t)d->Cout * 9 * d->Cin >= (1ll << 30)) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: operand larger than 2 GiB");
@@ -317,17 +322,30 @@ static int conv_params(const tmix_conv_desc* d, const uint8_t* scale_x, const ui
     return TMIX_OK;
 }
 
+// TMIX_CONV_UP2F: a tile of the kernel that runs the launch must lie inside one (image, phase) -- the phase's weight set and the store row are wave-uniform
+static int conv_resolve(const Params& p, int tile_cfg, int& cfg) {
+    const TileChoice r = resolve_tile(traits_of(1, p, 1), tile_cfg);
+    if (r.err) return r.err;
+    if (p.mode == TMIX_CONV_UP2F && (p.up_hw % TILINGS[r.cfg].bm))
+        TMIX_FAIL(TMIX_ESHAPE, "conv3x3: the folded upsampling mode needs H * W = %d to be a multiple of the %d rows of tiling %d (use TMIX_CONV_UP2)", p.up_hw, TILINGS[r.cfg].bm, r.cfg);
+    cfg = r.cfg;
+    return TMIX_OK;
+}
+
 static int conv_entry(const tmix_conv_desc* d, const uint8_t* scale_x, const uint8_t* scale_w, void* stream) {
     Params p;
     if (const int rc = conv_params(d, scale_x, scale_w, p)) return rc;
+    int cfg;
+    if (const int rc = conv_resolve(p, d->tile_cfg, cfg)) return rc;
     return launch(1, p, 1, d->tile_cfg, (hipStream_t)stream);
 }
 
 extern "C" int tmix_conv_resolve_tile(const tmix_conv_desc* d, int fp8_operands) {
     Params p;
     if (const int rc = conv_params(d, fp8_operands ? NO_SCALES : nullptr, fp8_operands ? NO_SCALES : nullptr, p)) return rc;
-    const TileChoice r = resolve_tile(traits_of(1, p, 1), d->tile_cfg);
-    return r.err ? r.err : r.cfg;
+    int cfg;
+    if (const int rc = conv_resolve(p, d->tile_cfg, cfg)) return rc;
+    return cfg;
 }
 
 extern "C" int tmix_conv3x3_nhwc(const tmix_conv_desc* d, void* stream) { return conv_entry(d, nullptr, nullptr, stream); }

@@ -82,6 +82,7 @@ struct Params {
     float ln_inv_c, ln_eps; int ln_parts;
     // convolution geometry (CONV only)
     int H, Wd, Cin, Ho, Wo, mode, ntaps;
+    int up_hw; unsigned up_magic;     // TMIX_CONV_UP2F: H * Wd (rows of one (image, phase)) and floor(2^32 / Wd) + 1 (l / Wd as a multiply-high, exact for l < H * Wd)
     unsigned long long* prof; int prof_detail;   // in-situ timing slot (common.h) or NULL
     int wide;                         // bit 0 / 1 / 2: the C / GEGLU / Ct stores may use the LDS-staged 16-byte form
     const unsigned char* scaleA; const unsigned char* scaleW; int64_t strideScaleA, strideScaleW;   // fp8: E8M0 exponent per A row / W row
@@ -171,6 +172,10 @@ gemm_conv_kernel(const Params p) {
     constexpr bool F8L = PH >= 4;                      // fp8 in the lock-step loops
     constexpr int SCP = (F8L && F8B) ? 1 : 0;          // one scale piece (1 KB slot, 4 * BM bytes used) per stage
     constexpr int EB = F8 ? 1 : 2;                     // bytes per operand element
+    // TMIX_CONV_UP2F (the host sends it to the bf16 convolution without shortcut taps only: the other instantiations do not carry its code -- with it the
+    // 256 x 320 shortcut-tap kernel went from 246 VGPRs to 256 and 576 bytes of scratch per lane)
+    constexpr bool UPF = CONV && !SC && !F8;
+    const bool upf = UPF && p.mode == TMIX_CONV_UP2F;
     constexpr int NW = WM * WN;                        // math waves
     constexpr int TM = BM / WM, TN = BN / WN;          // wave tile
     constexpr int FM = TM / 32, FN = TN / 32;          // 32x32 fragments per wave
@@ -246,6 +251,16 @@ gemm_conv_kernel(const Params p) {
 
     const bf16_t* Ab = (const bf16_t*)((const char*)p.A + (int64_t)bz * p.strideA * EB);      // strides count elements (fp8: bytes)
     const bf16_t* Wb = (const bf16_t*)((const char*)p.W + (int64_t)bzw * p.strideW * EB);
+    // TMIX_CONV_UP2F (nearest x2 folded into four 2x2 phase convolutions of the SOURCE image): GEMM row m = ((image * 4 + phase) * H + sy) * Wd + sx.  A tile lies
+    // inside one (image, phase) -- the host requires H * Wd % BM == 0 -- so the phase is wave-uniform: its weight set [Cout][2][2][Cin] is set `phase` of Wt, and
+    // the epilogue's store row follows from the tile's (image, phase) and the row's (sy, sx) (conv_store_row)
+    int up_q = 0;                                      // image * 4 + phase of this tile
+    if constexpr (CONV) {
+        if (upf) {
+            up_q = __builtin_amdgcn_readfirstlane(m0 / p.up_hw);
+            Wb += (int64_t)(up_q & 3) * p.N * p.ldw;
+        }
+    }
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, p.bytesA, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)Wb, 0, p.bytesW, 0x00020000);
 
@@ -271,7 +286,12 @@ gemm_conv_kernel(const Params p) {
             const int b = m / hw, rem = m - b * hw;
             const int py = rem / p.Wo, px = rem - py * p.Wo;
             int iy0, ix0; unsigned par = 0;
-            if (p.mode == TMIX_CONV_S1 || p.mode == TMIX_CONV_T3) { iy0 = py - 1; ix0 = px - 1; }
+            if (upf) {            // rem = (phase * H + sy) * Wd + sx; tap (ky, kx) of phase (fy, fx) reads source pixel (sy - 1 + fy + ky, sx - 1 + fx + kx)
+                const int ph = rem / p.up_hw, l = rem - ph * p.up_hw;
+                const int sy = l / p.Wd, sx = l - sy * p.Wd;
+                iy0 = sy - 1 + (ph >> 1); ix0 = sx - 1 + (ph & 1);
+            }
+            else if (p.mode == TMIX_CONV_S1 || p.mode == TMIX_CONV_T3) { iy0 = py - 1; ix0 = px - 1; }
             else if (p.mode == TMIX_CONV_S2) { iy0 = 2 * py - 1; ix0 = 2 * px - 1; }
             else if (p.mode == TMIX_CONV_S2A) { iy0 = 2 * py; ix0 = 2 * px; }
             else { iy0 = (py - 1) >> 1; ix0 = (px - 1) >> 1; par = (unsigned)((py - 1) & 1) << 16 | (unsigned)((px - 1) & 1) << 17; }     // nearest x2: source = upsampled coordinate >> 1
@@ -279,7 +299,8 @@ gemm_conv_kernel(const Params p) {
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 if (t >= p.ntaps) break;
-                const int ky = p.mode == TMIX_CONV_T3 ? t : t / 3, kx = p.mode == TMIX_CONV_T3 ? 1 : t - (t / 3) * 3;
+                const int ky = p.mode == TMIX_CONV_T3 ? t : (upf ? t >> 1 : t / 3);
+                const int kx = p.mode == TMIX_CONV_T3 ? 1 : (upf ? t & 1 : t - (t / 3) * 3);
                 bool ok;
                 if (p.mode == TMIX_CONV_UP2) { const int uy = py + ky - 1, ux = px + kx - 1; ok = (uy >= 0) & (uy < 2 * p.H) & (ux >= 0) & (ux < 2 * p.Wd); }
                 else { const int iy = iy0 + ky, ix = ix0 + kx; ok = (iy >= 0) & (iy < p.H) & (ix >= 0) & (ix < p.Wd); }
@@ -393,7 +414,9 @@ gemm_conv_kernel(const Params p) {
             }
         }
         // TMIX_CONV_T3: a (3,1,1) kernel over the first (frame) axis only -- 3 taps, kx fixed at the centre
-        const int ky = p.mode == TMIX_CONV_T3 ? tap : tap / 3, kx = p.mode == TMIX_CONV_T3 ? 1 : tap - ky * 3;
+        // TMIX_CONV_UP2F: the four taps of a 2 x 2 kernel
+        const int ky = p.mode == TMIX_CONV_T3 ? tap : (upf ? tap >> 1 : tap / 3);
+        const int kx = p.mode == TMIX_CONV_T3 ? 1 : (upf ? tap & 1 : tap - ky * 3);
         const unsigned pixb = (unsigned)p.Cin * (unsigned)EB, rowb = (unsigned)p.Wd * pixb;         // bytes of a source pixel / of a source row
         if (p.mode == TMIX_CONV_UP2) {
             // nearest x2: source row = (uy0 + ky) >> 1 = (uy0 >> 1) + {0, parity of uy0, 1}[ky], columns alike
@@ -1147,6 +1170,22 @@ gemm_conv_kernel(const Params p) {
     }
 
     bf16_t* Cb = p.C + (int64_t)bz * p.strideC;
+    // the row of C that GEMM row m is stored to: m itself, except for TMIX_CONV_UP2F, whose rows are phase-major -- the tile's (image, phase (fy, fx)) and the
+    // row's source pixel (sy, sx) give output pixel (2 sy + fy, 2 sx + fx) of the dense [B][2H][2W][Cout] tensor.  Everything else of the epilogue (row-group
+    // bias, column statistics, bounds) keeps counting in GEMM rows: an image's rows are contiguous in both orders
+    int up_mb = 0, up_ob = 0;
+    if constexpr (CONV) {
+        if (upf) { up_mb = up_q * p.up_hw; up_ob = ((up_q >> 2) * p.Ho + ((up_q >> 1) & 1)) * p.Wo + (up_q & 1); }
+    }
+    auto conv_store_row = [&](int m) __attribute__((always_inline)) -> int {
+        if constexpr (CONV) {
+            if (upf) {
+                const unsigned l = (unsigned)(m - up_mb), sy = __umulhi(l, p.up_magic), sx = l - sy * (unsigned)p.Wd;
+                return up_ob + (int)(2u * sy * (unsigned)p.Wo + 2u * sx);
+            }
+        }
+        return m;
+    };
     if (EK == 1 || (EK == 0 && p.epilogue == TMIX_EPI_GEGLU)) {
         // weight rows are interleaved in 16-row groups [value_j | gate_j]: within a 32-row fragment, accumulator
         // register groups g=0,1 (rows 0-15) are the value half and g=2,3 (rows 16-31) the gate half.
@@ -1348,7 +1387,7 @@ gemm_conv_kernel(const Params p) {
                         uint4 v;
                         v.x = pack_bf2(o[0], o[1]); v.y = pack_bf2(o[2], o[3]); v.z = pack_bf2(o[4], o[5]); v.w = pack_bf2(o[6], o[7]);
                         const bool ok = m < p.M && ncok;
-                        if (ok) *(uint4*)(Cb + (int64_t)m * p.ldc + nc) = v;
+                        if (ok) *(uint4*)(Cb + (int64_t)conv_store_row(m) * p.ldc + nc) = v;
                         if constexpr (F8C && (FL & 4) != 0) {           // the e4m3 + MX-block copy of the row AS STORED (as in the generic form)
                             const unsigned u8[4] = {v.x, v.y, v.z, v.w};
                             float f[8], am = 0.f;
@@ -1449,7 +1488,7 @@ gemm_conv_kernel(const Params p) {
                         uint4 v;
                         v.x = pack_bf2(o[0], o[1]); v.y = pack_bf2(o[2], o[3]); v.z = pack_bf2(o[4], o[5]); v.w = pack_bf2(o[6], o[7]);
                         if constexpr (ABL & 32) asm volatile("" :: "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-                        else *(uint4*)(Cb + (int64_t)m * p.ldc + nc) = v;
+                        else *(uint4*)(Cb + (int64_t)conv_store_row(m) * p.ldc + nc) = v;
                         if constexpr (F8C) if (p.f8copy) {
                             // the next GEMM's A operand: the row AS STORED, as e4m3 with one E8M0 scale per 32 columns (MX block = the 4
                             // adjacent lanes of this row; M % 32 == 0 and N % 32 == 0, so a block's lanes are all here)
@@ -1577,7 +1616,7 @@ gemm_conv_kernel(const Params p) {
                     *(float4*)((float*)p.C + (int64_t)bz * p.strideC + (int64_t)m * p.ldc + n) = make_float4(o[0], o[1], o[2], o[3]);
                 } else {
                     uint2 v; v.x = pack_bf2(o[0], o[1]); v.y = pack_bf2(o[2], o[3]);
-                    *(uint2*)(Cb + (int64_t)m * p.ldc + n) = v;
+                    *(uint2*)(Cb + (int64_t)conv_store_row(m) * p.ldc + n) = v;
                     if (sto) {
                         const float r0 = __uint_as_float(v.x << 16), r1 = __uint_as_float(v.x & 0xffff0000u);
                         const float r2 = __uint_as_float(v.y << 16), r3 = __uint_as_float(v.y & 0xffff0000u);

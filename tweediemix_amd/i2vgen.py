@@ -83,6 +83,8 @@ class I2VWeights:
                 t[name] = bf(v.to(dev)[:, :, :, 0, 0].permute(0, 2, 1))
             elif v.dim() == 4 and v.shape[-1] == 3:
                 t[name] = bf(v.to(dev).permute(0, 2, 3, 1))
+                if ".upsamplers." in name:                       # TMIX_CONV_UP2F (grids of a multiple of 256 pixels; the others keep the 9-tap launch)
+                    t[name + ".up2f"] = ops.fold_up2_weight(v.to(dev).permute(0, 2, 3, 1))
             elif v.dim() == 4:                                   # 1x1 conv_shortcut -> Linear
                 t[name] = bf(v.to(dev).reshape(v.shape[0], v.shape[1]))
             elif v.dim() == 2 and ".attn" not in name and ".ff.net.0.proj" not in name:

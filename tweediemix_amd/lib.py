@@ -15,7 +15,7 @@ OK, EINVAL, ESHAPE, EARCH, EALIGN = 0, -1, -2, -3, -4
 F32, F16, BF16 = 0, 1, 2
 STEP_FUSION, STEP_PLAIN, STEP_RESAMPLE = 0, 1, 2
 EPI_NONE, EPI_GEGLU, EPI_F32OUT, EPI_GELU, EPI_QUICKGELU = 0, 1, 2, 3, 4
-CONV_S1, CONV_S2, CONV_UP2, CONV_T3, CONV_S2A = 0, 1, 2, 3, 4
+CONV_S1, CONV_S2, CONV_UP2, CONV_T3, CONV_S2A, CONV_UP2F = 0, 1, 2, 3, 4, 5
 F8_A_BLOCK_SCALES, F8_GEGLU_OUT, F8_COPY_OUT = 1, 2, 4    # tmix_gemm_desc.reserved0 flags (the first two: tmix_gemm_fp8 only)
 TILE_AUTO, TILE_COUNT = 0, 26       # (csrc/gemm_tilings.h describes every id; what a launch really runs: tmix_gemm_resolve_tile / tmix_conv_resolve_tile)
 TILE_CANDIDATES = (1, 2, 3, 4, 5, 7, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22)          # what the autotuner times by default (16, 17: phase-offset mainloop).  NOT 23: its 16x16x32 MFMAs add up a row's products in another order than the 32x32x16 tilings (which are bit-identical among themselves), so a tuner that picked it for one plan and not for its co-batched twin broke test_two_seeds_co_batched_equal_independent_runs; in situ it is level with 21 anyway.  Nor 24 (256x320 on persistent workgroups, same bits as 14): 5 % ahead hot, 5 % behind in situ

@@ -6,6 +6,7 @@ validates on the C side and raises TmixError on failure; there is no eager/CPU f
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -322,11 +323,11 @@ def gemm_fp8(a8, sa, w8, sw, out=None, a_block_scales=False, f8_out=None, f8_cop
 def make_conv_desc(x, w, out, bias=None, batch_bias=None, residual=None, mode=L.CONV_S1, tile_cfg=0, bias_images=1, col_stats_out=None,
                    shortcut=None, _fp8=False):
     """x [B,H,W,Cin] bf16 NHWC contiguous; w [Cout,3,3,Cin] bf16 contiguous ([Cout,3,Cin] for the temporal CONV_T3,
-    where x is [clips, frames, h*w, Cin]).
+    where x is [clips, frames, h*w, Cin]; [4,Cout,2,2,Cin] for CONV_UP2F: fold_up2_weight).
     shortcut: (s1, s2 or None) -- NHWC tensors whose 1x1 conv_shortcut rides in the same K loop; w is then the 2-d [Cout, 9*Cin + C(s1) + C(s2)]
     matrix [conv taps | shortcut weights] (shortcut_weight) and bias the sum of the two biases."""
     B, H, W, Cin = x.shape
-    Cout = w.shape[0]
+    Cout = w.shape[1] if mode == L.CONV_UP2F else w.shape[0]
     dt = torch.uint8 if _fp8 else BF16                  # (e4m3 bytes: tmix_conv3x3_nhwc_fp8)
     assert x.dtype == dt and w.dtype == dt and x.is_contiguous() and w.is_contiguous() and out.is_contiguous()
     if shortcut is not None:
@@ -335,7 +336,7 @@ def make_conv_desc(x, w, out, bias=None, batch_bias=None, residual=None, mode=L.
         assert mode == L.CONV_S1 and tuple(w.shape) == (Cout, 9 * Cin + c1 + c2) and residual is None
         assert s1.dtype == BF16 and s1.is_contiguous() and s1.numel() == B * H * W * c1 and (s2 is None or (s2.dtype == BF16 and s2.is_contiguous() and s2.numel() == B * H * W * c2))
     else:
-        assert tuple(w.shape) == ((Cout, 3, Cin) if mode == L.CONV_T3 else (Cout, 3, 3, Cin))
+        assert tuple(w.shape) == ((Cout, 3, Cin) if mode == L.CONV_T3 else (4, Cout, 2, 2, Cin) if mode == L.CONV_UP2F else (Cout, 3, 3, Cin))
     d = L.ConvDesc()
     d.X, d.Wt, d.Y = x.data_ptr(), w.data_ptr(), out.data_ptr()
     d.bias, d.batch_bias, d.residual = _p(bias), _p(batch_bias), _p(residual)
@@ -360,7 +361,33 @@ def shortcut_weight(w_conv, w_sc):
 
 
 def conv_out_hw(H, W, mode):
-    return (H // 2, W // 2) if mode in (L.CONV_S2, L.CONV_S2A) else ((2 * H, 2 * W) if mode == L.CONV_UP2 else (H, W))
+    return (H // 2, W // 2) if mode in (L.CONV_S2, L.CONV_S2A) else ((2 * H, 2 * W) if mode in (L.CONV_UP2, L.CONV_UP2F) else (H, W))
+
+
+def fold_up2_weight(w_ohwi, dtype=BF16):
+    """the weights of TMIX_CONV_UP2F from those of a 3x3 convolution behind a nearest x2 upsampling: w [Cout,3,3,Cin] (OHWI) -> [4,Cout,2,2,Cin],
+    phase = 2 fy + fx major.  Output row 2 sy + fy touches source rows sy-1, sy, sy (fy = 0) or sy, sy, sy+1 (fy = 1), so the row taps of phase fy are
+    {ky=0}, {ky=1,2} resp. {ky=0,1}, {ky=2}; columns alike.  Summed in fp32 (fp64 input: in fp64) and rounded once to `dtype` (None: not at all)."""
+    assert w_ohwi.dim() == 4 and tuple(w_ohwi.shape[1:3]) == (3, 3)
+    w = w_ohwi.to(torch.float64 if w_ohwi.dtype == torch.float64 else torch.float32)
+    phases = []
+    for fy in (0, 1):
+        wy = torch.stack([w[:, 0], w[:, 1] + w[:, 2]] if fy == 0 else [w[:, 0] + w[:, 1], w[:, 2]], dim=1)                    # [Cout, 2, 3, Cin]
+        for fx in (0, 1):
+            phases.append(torch.stack([wy[:, :, 0], wy[:, :, 1] + wy[:, :, 2]] if fx == 0 else [wy[:, :, 0] + wy[:, :, 1], wy[:, :, 2]], dim=2))
+    out = torch.stack(phases)                                                                                                    # [4, Cout, 2, 2, Cin]
+    return (out if dtype is None else out.to(dtype)).contiguous()
+
+
+def up2_fold_enabled():
+    """the process-wide A/B switch: TMIX_UP2_FOLD=0 makes every plan keep the TMIX_CONV_UP2 launches (9 taps gathered from the upsampled coordinates)"""
+    return os.environ.get("TMIX_UP2_FOLD", "1") != "0"
+
+
+def up2_fold_ok(H, W):
+    """do the plan builders run the upsampler conv over an H x W source as TMIX_CONV_UP2F?  The kernel needs H * W to be a multiple of the row count of the
+    tile that runs it; the builders ask for a multiple of 256 -- the tallest tile -- so that EVERY tiling the tuner may pick accepts the launch."""
+    return up2_fold_enabled() and W >= 2 and (H * W) % 256 == 0
 
 
 def conv3x3_fp8(x8, sx, w8, sw, bias=None, batch_bias=None, residual=None, mode=L.CONV_S1, out=None, tile_cfg=12, col_stats_out=None, bias_images=1):
@@ -385,7 +412,7 @@ def conv3x3(x, w, bias=None, batch_bias=None, residual=None, mode=L.CONV_S1, out
     B, H, W, _ = x.shape
     Ho, Wo = conv_out_hw(H, W, mode)
     if out is None:
-        out = torch.empty(B, Ho, Wo, w.shape[0], device=x.device, dtype=BF16)
+        out = torch.empty(B, Ho, Wo, w.shape[1] if mode == L.CONV_UP2F else w.shape[0], device=x.device, dtype=BF16)
     d = make_conv_desc(x, w, out, bias, batch_bias, residual, mode, tile_cfg, col_stats_out=col_stats_out, shortcut=shortcut)
     L.check(lib.tmix_conv3x3_nhwc(C.byref(d), _stream()), "tmix_conv3x3_nhwc")
     return out

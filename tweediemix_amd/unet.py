@@ -148,6 +148,8 @@ class UNetWeights:
                 continue
             if v.dim() == 4 and v.shape[-1] == 3:
                 t[name] = bf(v.to(dev).permute(0, 2, 3, 1))
+                if ".upsamplers." in name:                       # TMIX_CONV_UP2F: the nearest x2 folded into four 2x2 phase kernels, from the checkpoint's own precision
+                    t[name + ".up2f"] = ops.fold_up2_weight(v.to(dev).permute(0, 2, 3, 1))      # (the 9-tap copy stays: fp8 plans, odd grids, TMIX_UP2_FOLD=0)
             elif v.dim() == 4:                                   # 1x1 conv_shortcut -> Linear
                 t[name] = bf(v.to(dev).reshape(v.shape[0], v.shape[1]))
             elif v.dim() == 2 and ".attn" not in name and ".ff.net.0.proj" not in name:
@@ -773,6 +775,9 @@ class UNetPlan:
             self.op_meta[len(self.ops) - 1] = ("conv_fp8", fl, d)
             return out
         w, bias, sc, csc = self.W[wname + ".weight"], self.W[wname + ".bias"], None, 0
+        taps = 9
+        if mode == L.CONV_UP2 and ops.up2_fold_ok(Hh, Ww):      # the upsampler as four 2x2 phase convolutions of the source grid: 4 Cin MACs per output pixel, not 9
+            mode, w, taps = L.CONV_UP2F, self.W[wname + ".weight.up2f"], 4
         if shortcut is not None:
             w, bias = self.W.conv2_with_shortcut(shortcut[0])
             sc = (shortcut[1], shortcut[2])
@@ -784,7 +789,7 @@ class UNetPlan:
         self.keep.append(d)
         self._hint_weights(w)
         self._emit(self.lib.tmix_conv3x3_nhwc, C.byref(d))
-        fl = 2 * self.B * Ho * Wo * Cout * (9 * Cin + csc)
+        fl = 2 * self.B * Ho * Wo * Cout * (taps * Cin + csc)      # (the flops performed: the folded upsampler counts its 4 taps)
         self.flops += fl
         self.launches["conv"].append((d, fl))
         self._tunable.append((len(self.ops) - 1, "conv", d))
@@ -1277,7 +1282,7 @@ def refine_group(self, top=14, reps=9, verbose=False, cands=None, only_kind=None
     for p in plans:
         for _i, kind, d in p._tunable:
             k = p._tune_key(kind, d)
-            fl = 2.0 * d.M * d.N * d.K * d.batch if kind == "gemm" else 2.0 * d.B * d.H * d.W * d.Cout * (9 * d.Cin + d.S1_channels + d.S2_channels)
+            fl = 2.0 * d.M * d.N * d.K * d.batch if kind == "gemm" else 2.0 * d.B * d.H * d.W * d.Cout * ((4 if d.mode == L.CONV_UP2F else 9) * d.Cin + d.S1_channels + d.S2_channels)
             weight[k] = weight.get(k, 0.0) + fl
             members.setdefault(k, []).append((p, kind, d))
     base = timed()

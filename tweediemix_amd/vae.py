@@ -139,6 +139,8 @@ class VAEDecoderPlan:
                 t[k] = v.to(F32).contiguous()
             elif v.dim() == 4 and v.shape[-1] == 3 and not k.startswith("decoder.conv_in"):
                 t[k] = v.permute(0, 2, 3, 1).to(BF16).contiguous()
+                if ".upsamplers." in k and ops.up2_fold_enabled():
+                    t[k + ".up2f"] = ops.fold_up2_weight(v.permute(0, 2, 3, 1))      # TMIX_CONV_UP2F: four 2x2 phase kernels, folded from the checkpoint's precision
             elif v.dim() == 4 and v.shape[-1] == 1 and not k.startswith("post_quant"):
                 t[k] = v.reshape(v.shape[0], v.shape[1]).to(BF16).contiguous()
             elif v.dim() == 2:
@@ -169,11 +171,14 @@ class VAEDecoderPlan:
     def _conv(self, x, name, Hh, Ww, Ci, Co, mode=L.CONV_S1, residual=None):
         Ho, Wo = ops.conv_out_hw(Hh, Ww, mode)
         out = self.arena.get(self.B, Ho * Wo, Co)
-        d = ops.make_conv_desc(x.view(self.B, Hh, Ww, Ci), self.t[name + ".weight"], out.view(self.B, Ho, Wo, Co),
+        w, taps = self.t[name + ".weight"], 9
+        if mode == L.CONV_UP2 and residual is None and ops.up2_fold_ok(Hh, Ww):      # the upsampler as four 2x2 phase convolutions of the source grid
+            mode, w, taps = L.CONV_UP2F, self.t[name + ".weight.up2f"], 4
+        d = ops.make_conv_desc(x.view(self.B, Hh, Ww, Ci), w, out.view(self.B, Ho, Wo, Co),
                                self.t[name + ".bias"], None, residual, mode)
         self.keep.append(d)
         self._emit(self.lib.tmix_conv3x3_nhwc, C.byref(d))
-        self.flops += 2 * self.B * Ho * Wo * Co * 9 * Ci
+        self.flops += 2 * self.B * Ho * Wo * Co * taps * Ci          # (the flops performed)
         return out
 
     def _gemm(self, a, w, out, **kw):
