@@ -159,7 +159,7 @@ enum { TMIX_TILE_AUTO = 0, TMIX_TILE_128x128_S2 = 1, TMIX_TILE_256x128_S3 = 2, T
        TMIX_TILE_128x160_S4_LW4 = 21 /* tiling 12 plus FOUR loader waves: one per SIMD, nine LDS-DMA instructions of a K-tile each */,
        TMIX_TILE_256x320_PH = 22 /* 256x320 with the phase-offset mainloop (eight waves of 64x160): bf16 GEMM, no transposed region */,
        TMIX_TILE_128x160_W22 = 23 /* 128x160 over 2 x 2 math waves of 64x80 (16x16x32 MFMA) + four loader waves: plain staged bf16 epilogue, other launches run as tiling 21 */,
-       /* ids 24 and 25 are RESERVED (dev builds only: make EXPERIMENTAL=1); the shipped library runs them as tilings 14 and 23, whose bits they reproduce */
+       /* ids 24 and 25 are reserved; run as 14 / 23 */
        TMIX_TILE_CONV_HALO = 26 /* tmix_conv3x3_nhwc only: stride-1 3x3 convolution with the input halo patch in LDS; launches it cannot run go to tiling 20 (a GEMM: 21) -- tmix_conv_resolve_tile tells */,
        TMIX_TILE_COUNT = 26 };
 typedef struct {

@@ -1216,25 +1216,55 @@ def test_gemm_fp8_geglu_output_as_mx_blocks_feeds_the_next_gemm(ops, tile):
     close(out, deq @ ops.dequantize_fp8_rows(w28, sw2).t())
 
 
-@pytest.mark.parametrize("cfg", [7, 12, 16, 18, 20, 21])
+def _hinted_launches_equal_the_plain_one(launch):
+    """launch() under a pending hint and once more behind it, against the un-hinted launch; the hinted tensor is only read"""
+    from tweediemix_amd import lib as L
+    lib = L.load()
+    st = torch.cuda.current_stream().cuda_stream
+    nxt = rnd(3000, 1280, seed=5)                      # 7.7 MB of "next weights" (not a multiple of the grid's share)
+    keep = nxt.clone()
+    ref = launch().clone()
+    L.check(lib.tmix_gemm_prefetch_next(nxt.data_ptr(), nxt.numel() * 2, st))
+    got = launch().clone()
+    again = launch()                                    # no hint pending any more
+    torch.cuda.synchronize()
+    assert torch.equal(got, ref) and torch.equal(again, ref) and torch.equal(nxt, keep)
+    return nxt
+
+
+@pytest.mark.parametrize("cfg", [7, 12, 16, 18, 20, 21, 23])
 def test_prefetch_hint_changes_nothing_but_timing(ops, cfg):
     """tmix_gemm_prefetch_next: the launch that consumes the hint touches another tensor while it waits for its own operands --
-    its C is bit-identical to the un-hinted launch, the hinted range is only read, and the hint is consumed by ONE launch."""
+    its C is bit-identical to the un-hinted launch, the hinted range is only read, and the hint is consumed by ONE launch.
+    Tiling 23 (gemm_w22.hip): 60000 lines over 20 workgroups x 256 loader threads are 12 per thread, more than a thread touches (8): the truncating case."""
     import ctypes as C
     from tweediemix_amd import lib as L
     lib = L.load()
     st = torch.cuda.current_stream().cuda_stream
     a, w = rnd(520, 256, seed=3), rnd(640, 256, seed=4, scale=256 ** -0.5)
-    nxt = rnd(3000, 1280, seed=5)                      # 7.7 MB of "next weights" (not a multiple of the grid's share)
-    keep = nxt.clone()
-    ref = ops.gemm(a, w, tile_cfg=cfg).clone()
-    L.check(lib.tmix_gemm_prefetch_next(nxt.data_ptr(), nxt.numel() * 2, st))
-    got = ops.gemm(a, w, tile_cfg=cfg).clone()
-    again = ops.gemm(a, w, tile_cfg=cfg)                # no hint pending any more
-    torch.cuda.synchronize()
-    assert torch.equal(got, ref) and torch.equal(again, ref) and torch.equal(nxt, keep)
+    if cfg == 23:                                       # (run as its fallback, tiling 21, the case would be vacuous)
+        d = ops.make_gemm_desc(a, w, torch.empty(520, 640, device="cuda", dtype=BF), tile_cfg=cfg)
+        assert lib.tmix_gemm_resolve_tile(C.byref(d), 0) == 23
+    nxt = _hinted_launches_equal_the_plain_one(lambda: ops.gemm(a, w, tile_cfg=cfg))
     assert lib.tmix_gemm_prefetch_next(nxt.data_ptr(), 1 << 40, st) < 0          # larger than 2 GiB: refused
     L.check(lib.tmix_gemm_prefetch_next(None, 0, st))                            # clears
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout", [(1, 4, 32, 128, 160), (2, 8, 32, 64, 320)])
+def test_prefetch_hint_changes_nothing_but_timing_tiling_26(ops, B, H, W, Cin, Cout):
+    """the halo-patch convolution (gemm_convh.hip): one workgroup, and 4 x 2 tiles"""
+    x, wc = rnd(B, H, W, Cin, seed=6), rnd(Cout, 3, 3, Cin, seed=7, scale=(9 * Cin) ** -0.5)
+    y = torch.empty(B, H, W, Cout, device="cuda", dtype=BF)
+    assert ops.conv_runs_as(ops.make_conv_desc(x, wc, y), 26) == 26        # (not its fallback, tiling 20)
+    _hinted_launches_equal_the_plain_one(lambda: ops.conv3x3(x, wc, tile_cfg=26))
+
+
+def test_prefetch_hint_changes_nothing_but_timing_q_cross_attn(ops):
+    """attn2 in one launch (gemm_qattn.hip) at B = 1, S = 128, C = 320 against 80 keys"""
+    S, Cc, Skv = 128, 320, 80
+    a, w = rnd(S, Cc, seed=8), rnd(Cc, Cc, seed=9, scale=Cc ** -0.5)
+    k, vt = rnd(1, Skv, Cc, seed=10), rnd(1, Cc, 80, seed=11)
+    _hinted_launches_equal_the_plain_one(lambda: ops.gemm_q_cross_attn(a, w, k, vt, S, 64 ** -0.5))
 
 
 @pytest.mark.parametrize("P,ln", [(4, False), (12, False), (4, True), (12, True)])
@@ -1388,26 +1418,6 @@ def test_gemm_w22_bias_residual_statistics_and_folded_layernorm(ops, M, N, K, ba
     close(y, F.layer_norm(hf, (N,), gamma, beta, 1e-5) @ w2.float().T + b2, rtol=2 ** -6, atol_frac=4e-3)
 
 
-_EXPERIMENTAL = pytest.mark.skipif(not os.environ.get("TMIX_EXPERIMENTAL_TILINGS"),
-                                   reason="tilings 24 / 25 live in dev variants only (tools/build_variant.sh x EXPERIMENTAL=1; run with TMIX_LIB=<variant> TMIX_EXPERIMENTAL_TILINGS=1): "
-                                          "the shipped library runs those ids as tilings 14 / 23")
-
-
-@_EXPERIMENTAL
-@pytest.mark.parametrize("M,N,K,batch", [(4096, 1280, 5120, 1), (1024, 1280, 1280, 4), (300, 640, 2560, 1), (129, 320, 192, 3), (128, 160, 64, 1)])
-def test_gemm_w22_with_l2_prefetcher_wave_equals_tiling_23_bit_for_bit(ops, M, N, K, batch):
-    """tiling 25 = tiling 23's math waves behind three DMA loaders and one prefetcher wave: the same bits, whatever the K depth (1 to 80 K-tiles)"""
-    shp = (batch, M) if batch > 1 else (M,)
-    a = rnd(*shp, K, seed=421)
-    w = rnd(*((batch,) if batch > 1 else ()), N, K, seed=422, scale=K ** -0.5)
-    bias = rnd(N, seed=423, dtype=torch.float32)
-    res = rnd(*shp, N, seed=424)
-    s23 = torch.zeros(N // 160, batch * M, 2, device="cuda"); s25 = torch.zeros_like(s23)
-    y23 = ops.gemm(a, w, bias=bias, residual=res, row_stats_out=s23, tile_cfg=23)
-    y25 = ops.gemm(a, w, bias=bias, residual=res, row_stats_out=s25, tile_cfg=25)
-    assert torch.equal(y23, y25) and torch.equal(s23, s25)
-
-
 def test_gemm_w22_falls_back_for_launches_it_does_not_carry(ops):
     """GEGLU, a transposed region, an activation, a row-group bias or a width that is not a multiple of 160 run as tiling 21 / 12: same results as asking for those"""
     from tweediemix_amd.weights import interleave_geglu
@@ -1511,35 +1521,6 @@ def test_long_row_quantiser_fallback_uses_the_kernels_scale_arithmetic(ops):
     q2, s2 = ops.quantize_fp8_rows(long_.to(BF).cuda())
     assert torch.equal(s1, s2)
     assert torch.equal(q1, q2[:, :8192])
-
-
-# --------------------------------------------------------------------------- tiling 24 (gemm_ff1p.hip): 256 x 320 on persistent workgroups
-@_EXPERIMENTAL
-@pytest.mark.parametrize("M,N,K,ln", [(4096, 10240, 1280, True), (16384, 5120, 640, True), (2048, 10240, 1280, True), (256, 320, 128, False), (768, 960, 192, True), (512, 20480, 64 * 3, False)])
-def test_gemm_persistent_geglu_equals_tiling_14_bit_for_bit(ops, M, N, K, ln):
-    """the FF up-projection on persistent workgroups (one per CU walking 1, 2, 4 ... tiles: 512 / 1024 / 256 tiles at the SDXL shapes, and grids smaller
-    than the chip): same tile, same MFMA order, same epilogue arithmetic as tiling 14 -> identical bits; and both against the fp32 reference."""
-    from tweediemix_amd.weights import fold_layernorm, interleave_geglu
-    h = rnd(M, K, seed=601) * 1.3 + 0.4
-    w = rnd(N, K, seed=602, scale=K ** -0.5)
-    b = rnd(N, seed=603, dtype=torch.float32)
-    kw = {}
-    if ln:
-        gamma, beta = rnd(K, seed=604, dtype=torch.float32) * 0.2 + 1, rnd(K, seed=605, dtype=torch.float32) * 0.3
-        wp, cs, t = fold_layernorm(w, gamma, beta, b)
-        wi = interleave_geglu(wp, None)[0]
-        csi, ti = interleave_geglu(cs[:, None], t)
-        hf = h.float()
-        stats = torch.stack([hf.sum(-1), (hf ** 2).sum(-1)], -1).view(1, M, 2).contiguous()
-        kw = dict(ln_stats=stats, ln_colsum=csi[:, 0].contiguous())
-        z = F.layer_norm(hf, (K,), gamma, beta, 1e-5) @ w.float().T + b
-    else:
-        wi, ti = interleave_geglu(w, b)
-        z = h.float() @ w.float().T + b
-    y24 = ops.gemm(h, wi, bias=ti, geglu=True, tile_cfg=24, **kw)
-    y14 = ops.gemm(h, wi, bias=ti, geglu=True, tile_cfg=14, **kw)
-    assert torch.equal(y24, y14)
-    close(y24, z[:, :N // 2] * F.gelu(z[:, N // 2:]), rtol=2 ** -6, atol_frac=4e-3)
 
 
 # --------------------------------------------------------------------------- the fp16 rounding points, by the device's own torch

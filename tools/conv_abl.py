@@ -1,5 +1,5 @@
 """time the SDXL-level convolutions per tiling, hot (the launch repeats on the same operands); run once per library build, e.g.
-TMIX_LIB=tools/ab/abl2/libtmix_hip.so python tools/conv_abl.py   (ablation builds: 2 = no MFMAs, 4 = no LDS-DMA in the loop of the non-loader tilings, 6 = neither)"""
+TMIX_LIB=tools/ab/<name>/libtmix_hip.so python tools/conv_abl.py"""
 import os, sys, ctypes as C, torch
 sys.path.insert(0, os.getcwd())
 from tweediemix_amd import ops, lib as L

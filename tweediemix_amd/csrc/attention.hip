@@ -20,13 +20,6 @@
 
 namespace {
 
-// TMIX_ATTN_ABL (dev builds under tools/ab/ only): ablations that locate the bound of the tile loop -- bit 0: no exp2 (a multiply
-// instead), bit 1: no PV / row-sum MFMAs, bit 2: no QK^T MFMAs, bit 3: no LDS-DMA inside the loop (the ring is re-read), bit 4: no maximum test per tile.
-#ifndef TMIX_ATTN_ABL
-#define TMIX_ATTN_ABL 0
-#endif
-constexpr int AABL = TMIX_ATTN_ABL;
-
 typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
@@ -125,9 +118,7 @@ constexpr int NSP = 4;
 constexpr int SMEM_P = NSP * STAGE;
 
 __global__ void __launch_bounds__(256, 2) attn_fwd_pipe_kernel(const AttnParams p) {
-#ifndef TMIX_NO_KERNARG_TOUCH
     kernarg_touch<(int)sizeof(AttnParams)>();
-#endif
     constexpr int LOADS = 4;             // LDS-DMA instructions per wave per tile (16 KiB tile, 1 KiB per instruction)
     constexpr int NR = 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -234,16 +225,15 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_pipe_kernel(const AttnParams 
             // MFMA n: d half n >> 3, key fragment (n >> 1) & 3, query fragment n & 1   (the two d halves of a score are 8 MFMAs apart)
             const int dh = n >> 3, f = (n >> 1) & 3, qi = n & 1;
             if constexpr (CUR) {
-                if constexpr (AABL & 4) { if (dh == 0) sc[f][qi] = negm[qi]; asm volatile("" :: "v"(kf[dh][f])); }
-                else sc[f][qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[dh][f], qf[qi][dh], dh ? sc[f][qi] : negm[qi], 0, 0, 0);
+                sc[f][qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[dh][f], qf[qi][dh], dh ? sc[f][qi] : negm[qi], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (CUR) { if (n < 4) kf[1][n] = *(const frag_ab*)(sKc + (n * 16 + fr) * 128 + swk1); }
             if constexpr (PREV) {
                 // packed word n of P^T(t-1): scores (f, qi, 2 hh) and (f, qi, 2 hh + 1) with f = n >> 2, qi = (n >> 1) & 1, hh = n & 1
                 const int pf = n >> 2, pq = (n >> 1) & 1, hh = n & 1;
-                const float e0 = (AABL & 1) ? sp[pf][pq][2 * hh] * 0.001f : __builtin_amdgcn_exp2f(sp[pf][pq][2 * hh]);
-                const float e1 = (AABL & 1) ? sp[pf][pq][2 * hh + 1] * 0.001f : __builtin_amdgcn_exp2f(sp[pf][pq][2 * hh + 1]);
+                const float e0 = __builtin_amdgcn_exp2f(sp[pf][pq][2 * hh]);
+                const float e1 = __builtin_amdgcn_exp2f(sp[pf][pq][2 * hh + 1]);
                 pb[pq][pf >> 1][(pf & 1) * 2 + hh] = pk_bf16(e0, e1);
                 asm volatile("" : "+v"(pb[pq][pf >> 1][(pf & 1) * 2 + hh]));      // computed HERE (LLVM otherwise sinks it to its first use, behind the barrier)
                 if (n >= 4 && n < 12) { const int m = n - 4; vf[m >> 2][m & 3] = *(const frag_ab*)(sV + ((m & 3) * 16 + fr) * 128 + ((((m >> 2) * 4 + fg) ^ (fr & 7)) << 4)); }
@@ -274,8 +264,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_pipe_kernel(const AttnParams 
                 frag_ab p0, p1;
                 __builtin_memcpy(&p0, pb[0][ps], 16);
                 __builtin_memcpy(&p1, pb[1][ps], 16);
-                if constexpr (AABL & 2) asm volatile("" :: "v"(p0), "v"(p1), "v"(vf[ps][(m >> 1) & 3]));
-                else if (m == 0) lacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, p0, lacc[0], 0, 0, 0);
+                if (m == 0) lacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, p0, lacc[0], 0, 0, 0);
                 else if (m == 1) lacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, p1, lacc[1], 0, 0, 0);
                 else if (m & 1) o[(m - 2) >> 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[ps][(m - 2) >> 1], p1, o[(m - 2) >> 1][1], 0, 0, 0);
                 else o[(m - 2) >> 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[ps][(m - 2) >> 1], p0, o[(m - 2) >> 1][0], 0, 0, 0);
@@ -293,7 +282,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_pipe_kernel(const AttnParams 
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (CUR) {
-            if ((AABL & 16) ? first : (first || __any(im > __float_as_int(THR)))) {
+            if (first || __any(im > __float_as_int(THR))) {
 #pragma unroll
                 for (int qi = 0; qi < 2; ++qi) {
                     float m0 = fmaxf(fmaxf(sc[0][qi][0], sc[0][qi][1]), fmaxf(sc[0][qi][2], sc[0][qi][3]));
@@ -322,7 +311,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_pipe_kernel(const AttnParams 
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" ::: "memory");
-        if (!(AABL & 8) && t + 3 < nt) stage(t + 3);
+        if (t + 3 < nt) stage(t + 3);
     };
 
     f32x4 sA[4][2], sB[4][2];
@@ -452,9 +441,7 @@ constexpr int SQW = 64;              // queries per wave
 // over the 256 CUs (B = 4, 20 heads, 1024 queries: 1280 waves = 256 workgroups of five, one per CU, where 320 workgroups of four ran
 // 1.25 rounds).
 __global__ void __launch_bounds__(320, 2) attn_small_kernel(const AttnParams p) {
-#ifndef TMIX_NO_KERNARG_TOUCH
     kernarg_touch<(int)sizeof(AttnParams)>();
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;

@@ -18,16 +18,9 @@ __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint3
 typedef __bf16 bf16x2_hw __attribute__((ext_vector_type(2)));
 typedef float f32x2_hw __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
-#if defined(TMIX_ABL_SW_BF16)   // dev A/B builds only (tools/build_variant.sh): the integer form this replaced
-    uint32_t a = __float_as_uint(lo), b = __float_as_uint(hi);
-    a = ((a & 0x7fffffffu) > 0x7f800000u) ? ((a >> 16) | 0x40u) : ((a + 0x7fffu + ((a >> 16) & 1u)) >> 16);
-    b = ((b & 0x7fffffffu) > 0x7f800000u) ? ((b >> 16) | 0x40u) : ((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
-    return (a & 0xffffu) | (b << 16);
-#else
     const f32x2_hw f = {lo, hi};
     const bf16x2_hw b = __builtin_convertvector(f, bf16x2_hw);
     return __builtin_bit_cast(uint32_t, b);
-#endif
 }
 __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf2(f, f) & 0xffffu); }
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }

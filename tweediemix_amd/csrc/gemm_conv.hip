@@ -32,7 +32,7 @@ TileChoice resolve_tile(const TileTraits& t, int cfg) {
         cfg = (int64_t)((t.M + 255) / 256) * ((t.N + 127) / 128) * t.batch >= 192 ? 2 : 1;
     cfg = TILINGS[cfg].runs_as;           // retired and reserved ids
     if (TILINGS[cfg].loop == OWN_KERNEL) {
-        if (cfg == 26 ? t.convh_ok : cfg == 24 ? t.ff1p_ok : t.w22_ok) return {cfg, 0, TMIX_OK};
+        if (cfg == 26 ? t.convh_ok : t.w22_ok) return {cfg, 0, TMIX_OK};
         cfg = t.conv ? TILINGS[cfg].fb_conv : TILINGS[cfg].fb;
     }
     if (t.n_trans_begin >= 0) {
@@ -86,9 +86,6 @@ TileTraits traits_of(int conv, const Params& p, int batch) {
     t.f8copy = p.f8copy; t.f8out = p.f8out; t.stats_out = p.stats_out; t.cs_out = p.cs_out; t.rowgroup_bias = p.rgb;
     t.M = p.M; t.N = p.N; t.K = p.K; t.batch = batch;
     t.w22_ok = w22_eligible(p, conv, 0); t.convh_ok = convh_eligible(p, conv, p.scaleA != nullptr);
-#ifdef TMIX_EXPERIMENTAL_TILINGS
-    t.ff1p_ok = ff1p_eligible(p, conv, 0, batch);
-#endif
     return t;
 }
 
@@ -96,12 +93,8 @@ int launch(int conv, Params& p, int batch, int tile_cfg, hipStream_t st) {
     const TileChoice r = resolve_tile(traits_of(conv, p, batch), tile_cfg);
     if (r.err) return r.err;
     switch (r.cfg) {
-    case 23: return launch_w22(p, batch, st, 0);
+    case 23: return launch_w22(p, batch, st);
     case 26: return launch_convh(p, st);
-#ifdef TMIX_EXPERIMENTAL_TILINGS
-    case 24: return launch_ff1p(p, st);
-    case 25: return launch_w22(p, batch, st, 1);
-#endif
     }
     switch (r.f8 >= 3 ? 5 : TILINGS[r.cfg].group) {       // (group 5: the e4m3 lock-step forms of the CAP_F8_LOCKSTEP tilings)
     case 0: return launch_group0(r.cfg, conv, r.f8, p, batch, st);

@@ -48,40 +48,19 @@ static_assert(H_NW * H_STG <= H_NS * H_WT, "epilogue patches fit in the weight r
 
 __global__ void __launch_bounds__((H_NW + H_LW) * 64, 2) conv_halo_kernel(const Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifndef TMIX_NO_KERNARG_TOUCH
     kernarg_touch<(int)sizeof(Params)>();
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = w >= H_NW;
     const bool prof_on = p.prof != nullptr && tid == 0;
     unsigned long long pt0 = 0, pt1 = 0, pt2 = 0;
     if (prof_on) pt0 = prof_enter(p.prof, (blockIdx.x | blockIdx.y) == 0, p.prof_detail);
-    // the NEXT launch's weights (tmix_gemm_prefetch_next): touched by the loader waves in front of their first DMA, whose counted waits cover the loads
-    constexpr int PFU = 8;
-    unsigned pf_keep[PFU];
-#pragma unroll
-    for (int u = 0; u < PFU; ++u) pf_keep[u] = 0;
-    if (p.pf && loader) {
-        const long long nwg = (long long)gridDim.x * gridDim.y, nth = H_LW * 64;
-        const long long lines = (p.pf_bytes + 127) >> 7; const int per = p.pf_per;
-        const long long first = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * nth + (tid - H_NW * 64);
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) {
-            const long long ln = first + (long long)u * nwg * nth;
-            if (u < per && ln < lines) asm volatile("global_load_dword %0, %1, off" : "=v"(pf_keep[u]) : "v"(p.pf + (ln << 7)) : "memory");
-        }
-    }
-    // tile order: gemm_kernel.h's (an XCD owns a compact patch of group_m x (64 / group_m) tiles); m-tiles enumerate (image, tile row, tile column), column fastest,
-    // so the group_m m-tiles of a group are neighbours along an image row and share their halo columns in the XCD's L2
-    int bid, by;
-    xcd_remap_grid(bid, by);
-    const int per_group = p.group_m * p.tiles_n;
-    const int grp = bid / per_group;
-    const int first_m = grp * p.group_m;
-    const int gsize = min(p.tiles_m - first_m, p.group_m);
-    const int rem = bid - grp * per_group;
-    const int tile_n = rem / gsize, tile_m = first_m + (rem - tile_n * gsize);
+    // the NEXT launch's weights: touched by the loader waves in front of their first DMA, whose counted waits cover the loads (gemm_kernel.h TMIX_PF_TOUCH)
+    TMIX_PF_TOUCH(p, pf_keep, loader, H_LW * 64, tid - H_NW * 64);
+    // tile order: gemm_kernel.h's; m-tiles enumerate (image, tile row, tile column), column fastest, so the group_m m-tiles of a group are neighbours along an
+    // image row and share their halo columns in the XCD's L2
+    const TileId tile = tile_of_workgroup(p);
+    const int tile_m = tile.tile_m, tile_n = tile.tile_n;
     const int n0 = tile_n * H_BN;
     const int txn = p.Wo / H_TC, tpi = (p.Ho / H_TR) * txn;          // tiles per image row, per image
     const int img = tile_m / tpi, trem = tile_m - img * tpi;
@@ -138,11 +117,7 @@ __global__ void __launch_bounds__((H_NW + H_LW) * 64, 2) conv_halo_kernel(const 
         // (c == nchunks: shortcut K-tile t -- the shortcut tensors' channels sit behind the nine taps in every weight row)
         auto stage_w = [&](int slot, int c, int t) __attribute__((always_inline)) {
             char* dst = smem + H_OFF_W + slot * H_WT;
-#ifdef TMIX_ABL_WSEQ      // dev A/B builds only (wrong results, timing valid): the weight K-tiles read as if the rows were stored chunk-major, i.e. consecutive 128-byte pieces
-            const unsigned so = (unsigned)(c * 9 + t) * (BK * 2u);
-#else
             const unsigned so = c < nchunks ? (unsigned)(t * p.Cin + c * BK) * 2u : (unsigned)(9 * p.Cin + t * BK) * 2u;
-#endif
 #pragma unroll
             for (int r = 0; r < H_LWI; ++r) blds16(rsW, woff[r], so, dst + (r * H_LW + s) * 1024);
         };
@@ -152,8 +127,7 @@ __global__ void __launch_bounds__((H_NW + H_LW) * 64, 2) conv_halo_kernel(const 
         stage_w(0, 0, 0);
         stage_w(1, 0, 1);
         wait_vmcnt<H_LWI>();
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));
+        pf_keep_alive(pf_keep);
         __builtin_amdgcn_s_barrier();
         stage_w(2, 0, 2);
         // K-tile kt = 9 c + t: weight tile kt + 3 goes to the ring slot the barrier of iteration kt - 1 released; at t == 0 the NEXT chunk's patch goes to the
@@ -252,26 +226,15 @@ __global__ void __launch_bounds__((H_NW + H_LW) * 64, 2) conv_halo_kernel(const 
         for (int j = 0; j < 5; ++j) {
             acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[S][j], fa[S], acc[j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef TMIX_HALO_ABL_LDS      // dev A/B builds only (wrong results): 16 instead of 24 fragment reads per K-tile -- is the loop bound by LDS read bytes?
-            if (j == 0) fa[1 - S] = rd_a(nb, nt, nkk);
-            if (j < 3) fb[1 - S][j] = rd_b(ns, j, nkk); else fb[1 - S][j] = fb[1 - S][j - 3];
-#elif defined(TMIX_HALO_READS_EVEN)     // dev A/B builds: one W fragment behind every MFMA (the first form)
-            if (j == 0) fa[1 - S] = rd_a(nb, nt, nkk);
-            fb[1 - S][j] = rd_b(ns, j, nkk);
-#else
             // the six reads of the next k-step behind the FIRST three MFMAs (two each, as the lock-step loops of gemm_kernel.h deal them): the last one is then two
             // MFMAs old when the K-tile's hand-over waits for lgkmcnt(0), instead of zero
             if (j == 0) { fa[1 - S] = rd_a(nb, nt, nkk); fb[1 - S][0] = rd_b(ns, 0, nkk); }
             else if (j == 1) { fb[1 - S][1] = rd_b(ns, 1, nkk); fb[1 - S][2] = rd_b(ns, 2, nkk); }
             else if (j == 2) { fb[1 - S][3] = rd_b(ns, 3, nkk); fb[1 - S][4] = rd_b(ns, 4, nkk); }
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
     };
     int cur = 0;
-#ifdef TMIX_HALO_PRIO         // dev A/B builds: the math waves above the loader wave of their SIMD in the issue arbiter
-    __builtin_amdgcn_s_setprio(2);
-#endif
     for (int c = 0; c < nchunks; ++c) {
         const int buf = c & 1;
 #pragma unroll
@@ -406,23 +369,9 @@ bool convh_eligible(const Params& p, int conv, int f8) {
 int launch_convh(Params& p, hipStream_t st) {
     constexpr int SMEM = H_MAIN + 2 * H_BN * 4;
     static_assert(SMEM <= 160 * 1024, "LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_halo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) TMIX_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
     p.tiles_m = p.M / 128; p.tiles_n = p.N / H_BN;
     p.group_m = 8;
-    if ((int64_t)p.tiles_m * p.tiles_n > 0x7fffffffLL) TMIX_FAIL(TMIX_ESHAPE, "conv3x3: %lld workgroups exceed the 32-bit linear grid id", (long long)p.tiles_m * p.tiles_n);
-    dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
-    p.prof = tmix_prof_take(&p.prof_detail);
-    tmix_prefetch_take(&p.pf, &p.pf_bytes);
-    { const long long nthr = (long long)grid.x * H_LW * 64, lines = (p.pf_bytes + 127) >> 7;
-      p.pf_per = p.pf ? (int)((lines + nthr - 1) / nthr) : 0; }
-    conv_halo_kernel<<<grid, (H_NW + H_LW) * 64, SMEM, st>>>(p);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
+    return launch_tiles<conv_halo_kernel>(p, p, 1, (H_NW + H_LW) * 64, SMEM, H_LW * 64, st, "conv3x3 (tiling 26)");
 }
 
 }  // namespace tmix_gemm

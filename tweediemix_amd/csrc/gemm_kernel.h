@@ -21,19 +21,11 @@
 #include "common.h"
 #include <type_traits>
 #include <stdlib.h>
+#include <atomic>
 
 // The kernel template is instantiated in gemm_inst_*.hip (one group of tilings per translation unit, built in parallel);
 // gemm_conv.hip holds the host entry points and the tiling switch.
 namespace tmix_gemm {
-
-// TMIX_ABL (dev builds under tools/ab/ only; the shipped library is built without it): ablations that locate the bound of a
-// launch -- bit 0: every workgroup stages tile (0, 0) (operands L2-hot, no fabric traffic), bit 1: no MFMAs (fragments are read
-// and kept alive), bit 2: no LDS-DMA inside the K loop (the prologue's tiles are re-read), bit 3: no epilogue at all; staged plain epilogue only:
-// bit 4: no bias loads, bit 5: no C stores (everything else runs), bit 6: the residual is neither requested nor added.
-#ifndef TMIX_ABL
-#define TMIX_ABL 0
-#endif
-constexpr int ABL = TMIX_ABL;
 
 constexpr int BK = 64;
 typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab;
@@ -108,6 +100,109 @@ static __device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, unsig
 constexpr int f8_block_cap(int bn) { return bn >= 256 ? 88 : 224; }
 
 template <int N> static __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// ---------------------------------------------------------------- the prologue every kernel of the family opens with (gemm_conv_kernel below, gemm_w22.hip,
+// gemm_convh.hip, gemm_qattn.hip) and the launch every host launcher ends with: one copy each
+// The NEXT launch's weights (tmix_gemm_prefetch_next): this workgroup's share, one dword per 128-byte line.  Each kernel requests them in front of the first
+// operands of its own tile -- the prologue waits one memory round trip for those anyway, these loads are older in the queue, so the counted vmcnt waits cover
+// them (round 5 moved the touches behind the first barrier and then spread them over the K loop -- tools/jobs5/r5g_pf.sh, r5h_pf2.sh: the prologue shrinks by
+// what the loop grows, and the step came out 0.1 - 0.3 ms slower both times).  The destinations pf_keep[] (declared here) stay reserved until the operands
+// have landed: pf_keep_alive.
+// `touches`: is this thread one of the nth threads of the workgroup that touch (all of them, or the loader waves: math waves next to loaders never wait on
+// vmcnt, so nothing would cover their loads), idx = its index among them.  A thread touches at most PFU lines: a hint with pf_per > PFU is cut short.
+// (A macro: the same statements as an inlined function reach the back end in another order -- the condition evaluated in front of the branch, the grid size
+// loaded twice -- and that changed the register counts of five gemm_conv_kernel instantiations and moved instructions inside the K loops of four more and of
+// conv_halo_kernel.  Its locals are pf_*_: the arguments are evaluated inside its block -- where the statements they replace had them -- and must not meet
+// a name of the macro's own.)
+constexpr int PFU = 8;
+#define TMIX_PF_TOUCH(p, pf_keep, touches, nth_, idx)                                                                                                     \
+    unsigned pf_keep[PFU];                                                                                                                                \
+    _Pragma("unroll") for (int pf_u_ = 0; pf_u_ < PFU; ++pf_u_) pf_keep[pf_u_] = 0;                                                                       \
+    if ((p).pf && (touches)) {                                                                                                                            \
+        const long long pf_nwg_ = (long long)gridDim.x * gridDim.y, pf_nth_ = (nth_);                                                                     \
+        const long long pf_lines_ = ((p).pf_bytes + 127) >> 7; const int pf_per_ = (p).pf_per;     /* lines per thread */                                 \
+        const long long pf_first_ = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * pf_nth_ + (idx);                                                   \
+        _Pragma("unroll") for (int pf_u_ = 0; pf_u_ < PFU; ++pf_u_) {                                                                                     \
+            const long long pf_ln_ = pf_first_ + (long long)pf_u_ * pf_nwg_ * pf_nth_;                                                                    \
+            if (pf_u_ < pf_per_ && pf_ln_ < pf_lines_)                                                                                                    \
+                asm volatile("global_load_dword %0, %1, off" : "=v"(pf_keep[pf_u_]) : "v"((p).pf + (pf_ln_ << 7)) : "memory");                            \
+        }                                                                                                                                                 \
+    }
+static __device__ __forceinline__ void pf_keep_alive(const unsigned (&pf_keep)[PFU]) {
+#pragma unroll
+    for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));
+}
+
+// Tile order: each XCD (private 4 MiB L2) owns a contiguous range of logical ids (xcd_remap_grid), and ids sweep group_m tile-rows per tile-column, so the
+// ~64 tiles resident on an XCD at any time form a compact group_m x (64 / group_m) patch that shares group_m A-panels and 64 / group_m W-panels instead of
+// streaming one W-panel per tile through the L2.  by = the grid's slice.
+struct TileId { int tile_m, tile_n, by; };
+static __device__ __forceinline__ TileId tile_of_workgroup(const Params& p) {
+    int bid, by;
+    xcd_remap_grid(bid, by);
+    const int per_group = p.group_m * p.tiles_n;
+    const int grp = bid / per_group;
+    const int first_m = grp * p.group_m;
+    const int gsize = min(p.tiles_m - first_m, p.group_m);
+    const int rem = bid - grp * per_group;
+    const int tile_n = rem / gsize, tile_m = first_m + (rem - tile_n * gsize);
+    return {tile_m, tile_n, by};
+}
+// periodic weight sets (co-batched seeds: rows [seed][concept] share the concept's weights): slices that read the same W are issued back to back -- grid
+// slice by is batch slice bz with weight set bzw = bz % w_period
+// (by / w_groups as a multiply-high by the host's reciprocal: scalar instructions only, exact for by, w_groups < 65536)
+struct BatchSlice { int bz, bzw; };
+static __device__ __forceinline__ BatchSlice slice_of_workgroup(const Params& p, int by) {
+    const int bzw = p.w_period > 0 ? (int)__umulhi((unsigned)by, p.w_magic) : by;
+    const int bz = p.w_period > 0 ? (by - bzw * p.w_groups) * p.w_period + bzw : by;
+    return {bz, bzw};
+}
+
+// fused LayerNorm (consumer side): the rank-1 term -mean_m * colsum_n as one more MFMA k-step needs both factors as bf16 operands without losing fp32 bits.
+// x = x1 + x2 + x3 (bf16 pieces by truncation, exact residuals): operand halves {x1,x1,x2,0 | x1,x3,x2,0} for -mean and {x1,x2,x1,0 | x3,x1,x2,0} for
+// colsum pair up to the six products x_a * y_b with a + b <= 4 (~24 bits)
+struct Bf16Pieces { unsigned x1, x2, x3; };              // each piece in the HIGH half of its word
+static __device__ __forceinline__ Bf16Pieces bf16_pieces(float x) {
+    Bf16Pieces s;
+    s.x1 = __float_as_uint(x) & 0xffff0000u;
+    const float r1 = x - __uint_as_float(s.x1);
+    s.x2 = __float_as_uint(r1) & 0xffff0000u;
+    s.x3 = __float_as_uint(r1 - __uint_as_float(s.x2)) & 0xffff0000u;
+    return s;
+}
+static __device__ __forceinline__ uint4 ln_mean_operand(float neg_mean) {
+    const Bf16Pieces s = bf16_pieces(neg_mean);
+    return make_uint4((s.x1 >> 16) | s.x1, s.x2 >> 16, (s.x1 >> 16) | s.x3, s.x2 >> 16);
+}
+static __device__ __forceinline__ uint4 ln_colsum_operand(float colsum) {
+    const Bf16Pieces s = bf16_pieces(colsum);
+    return make_uint4((s.x1 >> 16) | s.x2, s.x1 >> 16, (s.x3 >> 16) | s.x1, s.x2 >> 16);
+}
+
+// The launch of a kernel of the family over p.tiles_m * p.tiles_n tiles x `slices` batch slices (the caller has set tiles_m / tiles_n / group_m): the
+// dynamic-LDS attribute (once per kernel), the grid check, the profiler slot and the pending weight hint with its share per touching thread (hint_threads
+// per workgroup, see TMIX_PF_TOUCH), the launch.  `arg` is what the kernel takes: p itself, or the struct that holds p (gemm_qattn.hip).
+// `what` names the launcher in the error strings.
+// A launch the grid check refuses consumes neither a profiler slot nor the hint; a failed hipFuncSetAttribute is reported and tried again by the next call.
+template <auto KERNEL, typename Arg>
+int launch_tiles(Params& p, const Arg& arg, int slices, int block, int smem, int hint_threads, hipStream_t st, const char* what) {
+    static std::atomic<bool> attr_set{false};          // (idempotent: racing threads set the same value)
+    if (!attr_set.load(std::memory_order_acquire)) {
+        hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) TMIX_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+        attr_set.store(true, std::memory_order_release);
+    }
+    // the kernels remap the LINEAR workgroup id over the whole (tiles, slices) grid in 32-bit arithmetic (common.h xcd_remap_grid)
+    if ((int64_t)p.tiles_m * p.tiles_n * slices > 0x7fffffffLL) TMIX_FAIL(TMIX_ESHAPE, "%s: %lld x %d workgroups exceed the 32-bit linear grid id", what, (long long)p.tiles_m * p.tiles_n, slices);
+    dim3 grid(p.tiles_m * p.tiles_n, slices, 1);
+    p.prof = tmix_prof_take(&p.prof_detail);
+    tmix_prefetch_take(&p.pf, &p.pf_bytes);
+    { const long long nthr = (long long)grid.x * grid.y * hint_threads, lines = (p.pf_bytes + 127) >> 7;
+      p.pf_per = p.pf ? (int)((lines + nthr - 1) / nthr) : 0; }      // 128-byte lines per touching thread
+    KERNEL<<<grid, block, smem, st>>>(arg);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) TMIX_FAIL((int)e, "%s: launch failed: %s", what, hipGetErrorString(e));
+    return TMIX_OK;
+}
 
 // LW = 1 adds a LOADER wave to the WM x WN math waves (wave specialisation): measured on this chip (tools/ubench/dma_issue),
 // an LDS-DMA instruction blocks the issuing wave for ~100 cycles and a wave's own MFMAs queue up behind its DMA issue
@@ -193,9 +288,7 @@ gemm_conv_kernel(const Params p) {
     static_assert(PHL || (NS - 2) * L <= 63, "vmcnt immediate");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifndef TMIX_NO_KERNARG_TOUCH
     kernarg_touch<(int)sizeof(Params)>();
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -205,49 +298,16 @@ gemm_conv_kernel(const Params p) {
     const bool prof_on = p.prof != nullptr && tid == 0;
     unsigned long long pt0 = 0, pt1 = 0, pt2 = 0;
     if (prof_on) pt0 = prof_enter(p.prof, (blockIdx.x | blockIdx.y) == 0, p.prof_detail);
-    // ---- the NEXT launch's weights (tmix_gemm_prefetch_next): this workgroup's share, one dword per 128-byte line, requested
-    // before the first operands of its own tile -- the prologue waits one memory round trip for those anyway, and these loads are
-    // older in the queue, so the counted vmcnt waits below cover them.  The destinations stay reserved (pf_keep) until then.
-    constexpr int PFU = 8;
-    unsigned pf_keep[PFU];
-#pragma unroll
-    for (int u = 0; u < PFU; ++u) pf_keep[u] = 0;
-    // (with loader waves only they touch: the math waves never wait on vmcnt, so nothing would cover their loads)
-    if (p.pf && (!LW || w >= WM * WN)) {
-        const long long nwg = (long long)gridDim.x * gridDim.y, nth = (LW ? LW : WM * WN * KS) * 64;
-        const long long lines = (p.pf_bytes + 127) >> 7; const int per = p.pf_per;     // lines per thread
-        const long long first = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * nth + (LW ? tid - WM * WN * 64 : tid);
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) {
-            const long long ln = first + (long long)u * nwg * nth;
-            if (u < per && ln < lines) asm volatile("global_load_dword %0, %1, off" : "=v"(pf_keep[u]) : "v"(p.pf + (ln << 7)) : "memory");
-        }
-    }
+    // ---- the NEXT launch's weights, requested before the first operands of this tile (with loader waves only they touch)
+    TMIX_PF_TOUCH(p, pf_keep, !LW || w >= WM * WN, (LW ? LW : WM * WN * KS) * 64, LW ? tid - WM * WN * 64 : tid);
     const bool loader = LW && (w >= NW);               // wave-uniform role
     const bool stager = LW ? loader : true;
     const int sw_id = LW ? max(w - NW, 0) : w;         // this wave's slot among the staging waves
 
-    // Tile order: each XCD (private 4 MiB L2) owns a contiguous range of logical ids, and ids sweep GM tile-rows
-    // per tile-column, so the ~64 tiles resident on an XCD at any time form a compact GM x (64/GM) patch that
-    // shares GM A-panels and 64/GM W-panels instead of streaming one W-panel per tile through the L2.
-#ifdef TMIX_XCD_X_ONLY     // dev A/B builds: the remap of blockIdx.x alone (every XCD works on every slice)
-    const int bid = xcd_remap(blockIdx.x, gridDim.x), by = blockIdx.y;
-#else
-    int bid, by;
-    xcd_remap_grid(bid, by);
-#endif
-    const int per_group = p.group_m * p.tiles_n;
-    const int grp = bid / per_group;
-    const int first_m = grp * p.group_m;
-    const int gsize = min(p.tiles_m - first_m, p.group_m);
-    const int rem = bid - grp * per_group;
-    const int tile_n = rem / gsize, tile_m = first_m + (rem - tile_n * gsize);
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int m0l = (ABL & 1) ? 0 : m0, n0l = (ABL & 1) ? 0 : n0;      // rows the STAGING reads (ablation bit 0: tile (0, 0))
-    // periodic weight sets (co-batched seeds: rows [seed][concept] share the concept's weights): slices that read the same W are issued back to back
-    // (by / w_groups as a multiply-high by the host's reciprocal: scalar instructions only, exact for by, w_groups < 65536)
-    const int bzw = p.w_period > 0 ? (int)__umulhi((unsigned)by, p.w_magic) : by;       // == bz % w_period
-    const int bz = p.w_period > 0 ? (by - bzw * p.w_groups) * p.w_period + bzw : by;
+    const TileId tile = tile_of_workgroup(p);
+    const int tile_n = tile.tile_n, m0 = tile.tile_m * BM, n0 = tile_n * BN;
+    const BatchSlice slice = slice_of_workgroup(p, tile.by);
+    const int bz = slice.bz, bzw = slice.bzw;
 
     const bf16_t* Ab = (const bf16_t*)((const char*)p.A + (int64_t)bz * p.strideA * EB);      // strides count elements (fp8: bytes)
     const bf16_t* Wb = (const bf16_t*)((const char*)p.W + (int64_t)bzw * p.strideW * EB);
@@ -319,15 +379,15 @@ gemm_conv_kernel(const Params p) {
                 const int par = (LW >= 2) ? (sw_id & 1) : pp;   // two / four loaders: instruction parity = loader id & 1 (both slots hold it)
                 const unsigned sw = ((lane & 7) ^ ((4 * par + (lane >> 4)) & 7)) * 8;        // swizzled source chunk, in bf16 elements (x 2 = bytes)
                 swp[pp] = sw;
-                woffp[pp] = (unsigned)(n0l + par * 8 + lrow) * (unsigned)p.ldw * (unsigned)EB + sw * 2u;
+                woffp[pp] = (unsigned)(n0 + par * 8 + lrow) * (unsigned)p.ldw * (unsigned)EB + sw * 2u;
                 wmaxp[pp] = (unsigned)(p.N - 1) * (unsigned)p.ldw * (unsigned)EB + sw * 2u;
-                aoffp[pp] = (unsigned)(m0l + par * 8 + lrow) * (unsigned)p.lda * (unsigned)EB + sw * 2u;
+                aoffp[pp] = (unsigned)(m0 + par * 8 + lrow) * (unsigned)p.lda * (unsigned)EB + sw * 2u;
                 amaxp[pp] = (unsigned)(p.M - 1) * (unsigned)p.lda * (unsigned)EB + sw * 2u;
             }
             if constexpr (CONV) {
 #pragma unroll
                 for (int r = 0; r < RA; ++r) {
-                    int m = m0l + slot_a(r) * 8 + lrow; if (m > p.M - 1) m = p.M - 1;      // (the rows of THIS loader's r-th instruction)
+                    int m = m0 + slot_a(r) * 8 + lrow; if (m > p.M - 1) m = p.M - 1;      // (the rows of THIS loader's r-th instruction)
                     conv_row(r, m, swp[r & 1] * 2u);
                 }
             }
@@ -338,14 +398,14 @@ gemm_conv_kernel(const Params p) {
     for (int r = 0; r < RB; ++r) {
         const int idx = slot_w(r);
         const int sw = ((lane & 7) ^ ((4 * idx + (lane >> 4)) & 7)) * 8;    // swizzled source chunk (elements)
-        int n = n0l + idx * 8 + lrow; if (n > p.N - 1) n = p.N - 1;
+        int n = n0 + idx * 8 + lrow; if (n > p.N - 1) n = p.N - 1;
         woff[r] = (unsigned)n * (unsigned)p.ldw * (unsigned)EB + (unsigned)sw * 2u;
     }
 #pragma unroll
     for (int r = 0; r < RA; ++r) {
         const int idx = slot_a(r);
         const int sw = ((lane & 7) ^ ((4 * idx + (lane >> 4)) & 7)) * 8;
-        int m = m0l + idx * 8 + lrow; if (m > p.M - 1) m = p.M - 1;
+        int m = m0 + idx * 8 + lrow; if (m > p.M - 1) m = p.M - 1;
         asw[r] = sw;
         if constexpr (CONV) {
             conv_row(r, m, (unsigned)sw * 2u);
@@ -366,12 +426,12 @@ gemm_conv_kernel(const Params p) {
         const unsigned ch = (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) * (16 / EB));  // swizzled source chunk (elements)
 #pragma unroll
         for (int r = 0; r < PA; ++r) {
-            int m = m0l + (r * NW + w) * 16 + (lane >> 2); if (m > p.M - 1) m = p.M - 1;
+            int m = m0 + (r * NW + w) * 16 + (lane >> 2); if (m > p.M - 1) m = p.M - 1;
             phA[r] = ((unsigned)m * (unsigned)p.lda + ch) * (unsigned)EB;
         }
 #pragma unroll
         for (int r = 0; r < PB; ++r) {
-            int n = n0l + ph_w(r) * 16 + (lane >> 2); if (n > p.N - 1) n = p.N - 1;
+            int n = n0 + ph_w(r) * 16 + (lane >> 2); if (n > p.N - 1) n = p.N - 1;
             phW[r] = ((unsigned)n * (unsigned)p.ldw + ch) * (unsigned)EB;
         }
     }
@@ -397,7 +457,7 @@ gemm_conv_kernel(const Params p) {
     if constexpr (CONV && SCP) {
         if (stager) {
             const int hw = p.Ho * p.Wo;
-            int m = m0l + sw_id * SRW + min(lane, SRW - 1); if (m > p.M - 1) m = p.M - 1;
+            int m = m0 + sw_id * SRW + min(lane, SRW - 1); if (m > p.M - 1) m = p.M - 1;
             sb_ = m / hw; const int rem = m - sb_ * hw;
             sy_ = rem / p.Wo; sx_ = rem - sy_ * p.Wo;
         }
@@ -453,7 +513,7 @@ gemm_conv_kernel(const Params p) {
         if constexpr (CONV) rsSc = __builtin_amdgcn_make_buffer_rsrc((void*)p.scaleA, 0, (int)(p.bytesA / 32), 0x00020000);      // [pixels][Cin / 32]
         else {
             rsSc = __builtin_amdgcn_make_buffer_rsrc((void*)p.scaleA, 0, (int)((int64_t)(p.K / 32) * p.ldScaleA), 0x00020000);
-            sc_voff = (unsigned)((16 * lane) / BM) * (unsigned)p.ldScaleA + (unsigned)((16 * lane) % BM) + (unsigned)(bz * p.strideScaleA + m0l);
+            sc_voff = (unsigned)((16 * lane) / BM) * (unsigned)p.ldScaleA + (unsigned)((16 * lane) % BM) + (unsigned)(bz * p.strideScaleA + m0);
         }
     }
     auto scale_piece = [&](char* sA, int kt) __attribute__((always_inline)) {
@@ -477,13 +537,11 @@ gemm_conv_kernel(const Params p) {
         // byte offset of this K-tile inside a weight row: the plain GEMM walks K in order; the convolution's cursor (tap, cc) walks CHANNEL-CHUNK major
         // (see the cursor advance below), weight rows are [tap][Cin] (+ the shortcut tensors' channels behind the taps)
         unsigned wk = (unsigned)kt * (BK * 2);
-#ifndef TMIX_ABL_WSEQ     // (dev A/B builds: keep the sequential walk of the weight rows under the chunk-major A gather -- wrong results, timing valid)
         if constexpr (CONV && !LW) {
             const int tap_u = __builtin_amdgcn_readfirstlane(tap), cc_u = __builtin_amdgcn_readfirstlane(cc);
             if (SC && tap_u >= p.ntaps) wk = (unsigned)(p.ntaps * p.Cin + (tap_u > p.ntaps ? p.c1s : 0)) * 2u + (unsigned)cc_u * (BK * 2);
             else wk = (unsigned)(tap_u * p.Cin) * (unsigned)EB + (unsigned)cc_u * (BK * 2);
         }
-#endif
         if constexpr (CONV && SC) {
             // the A source of this K-tile: the conv input for the nine taps, then the shortcut tensors.  The cursor is wave-uniform (said explicitly),
             // and the choice is made on plain pointers -- a select between buffer RESOURCES goes through scratch memory and waterfall loops
@@ -516,7 +574,7 @@ gemm_conv_kernel(const Params p) {
             // re-read went through the fabric: FETCH_SIZE 4.5 x algorithmic.  Now the kx neighbours are consecutive K-tiles and the ky neighbours three apart.  The
             // per-lane tap offsets are recomputed every K-tile (a dozen VALU instructions per staged row, under the MFMAs); the shortcut tensors keep their order.
             // (The loader-wave instantiations -- tiling 20 -- keep the tap-major walk: their two loaders are the launch's critical path, and with the offsets
-            // derived every K-tile and the weight rows walked tap-strided they lost 42 % hot, 152 vs 107 us at 32 x 32 1280 -> 1280; tools/jobs6_wseq.sh.)
+            // derived every K-tile and the weight rows walked tap-strided they lost 42 % hot, 152 vs 107 us at 32 x 32 1280 -> 1280, round 6.)
             if (LW || (SC && tap >= p.ntaps)) { if (++cc == cpt) { cc = 0; ++tap; if (tap < ntaps_all) conv_tap_offsets(); } }
             else {
                 if (++tap == p.ntaps) { tap = 0; if (++cc == cpt) { cc = 0; tap = p.ntaps; } }
@@ -536,8 +594,7 @@ gemm_conv_kernel(const Params p) {
             for (int s = 0; s < PRE; ++s)
                 if (s < nk) stage(s, s);
             if (nk >= PRE) wait_vmcnt<(PRE - 1) * L>(); else wait_vmcnt<0>();
-#pragma unroll
-            for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));
+            pf_keep_alive(pf_keep);
             __builtin_amdgcn_s_barrier();
 #pragma unroll
             for (int s = PRE; s < NS - 1; ++s)
@@ -598,8 +655,6 @@ gemm_conv_kernel(const Params p) {
         }
         if (tid < BN) ln_cs = (p.ln_colsum + (int64_t)bzw * p.strideLnColsum)[min(n0 + tid, p.N - 1)];
     }
-    // x = x1 + x2 + x3 (bf16 pieces by truncation, exact residuals): operand halves {x1,x1,x2,0 | x1,x3,x2,0} for -mean
-    // and {x1,x2,x1,0 | x3,x1,x2,0} for colsum pair up to the six products x_a * y_b with a + b <= 4 (~24 bits)
     auto ln_reduce = [&]() {
         if (tid < BN) { bias_lds[tid] = bias_r; if constexpr (CONV) rgb_lds[tid] = rgb_r; }
         if (!ln_on) return;
@@ -610,20 +665,9 @@ gemm_conv_kernel(const Params p) {
                 if (q < p.ln_parts) { s1 += __uint_as_float(lnv[q].x); s2 += __uint_as_float(lnv[q].y); }
             const float mean = s1 * p.ln_inv_c;
             ln_rs[tid] = rsqrtf(fmaxf(s2 * p.ln_inv_c - mean * mean, 0.f) + p.ln_eps);
-            const float x = -mean;
-            const unsigned x1 = __float_as_uint(x) & 0xffff0000u;
-            const float r1 = x - __uint_as_float(x1);
-            const unsigned x2 = __float_as_uint(r1) & 0xffff0000u;
-            const unsigned x3 = __float_as_uint(r1 - __uint_as_float(x2)) & 0xffff0000u;
-            ln_mfrag[tid] = make_uint4((x1 >> 16) | x1, x2 >> 16, (x1 >> 16) | x3, x2 >> 16);
+            ln_mfrag[tid] = ln_mean_operand(-mean);
         }
-        if (tid < BN) {
-            const unsigned x1 = __float_as_uint(ln_cs) & 0xffff0000u;
-            const float r1 = ln_cs - __uint_as_float(x1);
-            const unsigned x2 = __float_as_uint(r1) & 0xffff0000u;
-            const unsigned x3 = __float_as_uint(r1 - __uint_as_float(x2)) & 0xffff0000u;
-            ln_cfrag[tid] = make_uint4((x1 >> 16) | x2, x1 >> 16, (x3 >> 16) | x1, x2 >> 16);
-        }
+        if (tid < BN) ln_cfrag[tid] = ln_colsum_operand(ln_cs);
     };
 
     f32x16 acc[FM][FN];
@@ -674,7 +718,7 @@ gemm_conv_kernel(const Params p) {
     constexpr int WP_I = (FN / 2) * 4 + (FN & 1) * 2;          // 16-byte residual pieces per lane per 32-row block
     constexpr bool WPREF = FM * WP_I <= 12 && !(CONV && F8L && LW);      // (the loader-wave fp8 convolution has no registers for it: 16 dwords of scratch otherwise)
     uint4 rw[WPREF ? FM * WP_I : 1];
-    const bool wide_res = EK != 1 && WPREF && Rb && (EK >= 2 || (p.wide & 1)) && kg == 0 && !(ABL & 64);
+    const bool wide_res = EK != 1 && WPREF && Rb && (EK >= 2 || (p.wide & 1)) && kg == 0;
     auto prefetch_residual_wide = [&]() {
         if constexpr (WPREF) {
             auto grab = [&](int j0, int base, auto cf_tag) {
@@ -746,8 +790,7 @@ gemm_conv_kernel(const Params p) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (prof_on) pt1 = prof_now();
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));        // the prefetch touches have returned (older than the tiles waited for)
+        pf_keep_alive(pf_keep);                        // the prefetch touches have returned (older than the tiles waited for)
         if (grp) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
         // One slice: LOAD segment (fragment reads of slice s; the wait that makes slice s + 1 visible), barrier, MFMA
         // segment, barrier.  The LDS-DMA instructions of slice s + 3 are issued INSIDE the MFMA cluster, one after every
@@ -811,7 +854,6 @@ gemm_conv_kernel(const Params p) {
 #pragma unroll
                     for (int j = 0; j < FN; ++j) {
                         if constexpr (F8) acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b8[j], a8[i], acc[i][j], 0, 0, 0, f8sW[j], 0, F8B ? f8use[i] : f8sA[i]);
-                        else if constexpr (ABL & 2) asm volatile("" :: "v"(b[kk][j]), "v"(a[kk][i]));
                         else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[kk][j], a[kk][i], acc[i][j], 0, 0, 0);
                         const int idx = (kk * FM + i) * FN + j;
                         if constexpr (ST) {
@@ -831,7 +873,7 @@ gemm_conv_kernel(const Params p) {
             asm volatile("" ::: "memory");
         };
         int s = 0;
-        if constexpr (!(ABL & 4)) for (; s + 3 < ns; ++s) slice(s, std::true_type{});
+        for (; s + 3 < ns; ++s) slice(s, std::true_type{});
         for (; s < ns; ++s) slice(s, std::false_type{});
         if (!grp) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
     } else
@@ -856,8 +898,7 @@ gemm_conv_kernel(const Params p) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (prof_on) pt1 = prof_now();
-#pragma unroll
-    for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));            // the prefetch touches have returned (older than the tiles waited for)
+    pf_keep_alive(pf_keep);                            // the prefetch touches have returned (older than the tiles waited for)
     int cur = 0, nxt = NS - 1;                        // ring positions of tile kt and tile kt+NS-1
     constexpr int KPW = F8L ? 2 : 4 / KS;              // k-steps of this wave's split-K group (fp8: two 64-wide k-steps per 128-byte row)
     const int k0 = kg * KPW;
@@ -890,8 +931,7 @@ gemm_conv_kernel(const Params p) {
         else return (int)((unsigned)(unsigned char)smem[rbuf * STAGE + A_TILE + B_TILE + (2 * kk + lhi) * BM + wr * TM + i * 32 + l31] * 0x01010101u);
     };
     auto mma = [&](f32x16& c, const frag_t& b_, const frag_t& a_, int j, int i, int S) __attribute__((always_inline)) {
-        if constexpr (ABL & 2) asm volatile("" :: "v"(b_), "v"(a_));
-        else if constexpr (F8L) c = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b_, a_, c, 0, 0, 0, f8sW[j], 0, F8B ? f8a[S][F8B ? i : 0] : f8sA[F8B ? 0 : i]);
+        if constexpr (F8L) c = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b_, a_, c, 0, 0, 0, f8sW[j], 0, F8B ? f8a[S][F8B ? i : 0] : f8sA[F8B ? 0 : i]);
         else c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b_, a_, c, 0, 0, 0);
     };
     constexpr int NMF = FM * FN, NRD = FM + FN;
@@ -940,7 +980,7 @@ gemm_conv_kernel(const Params p) {
     // one K-tile; MORE (compile time): tile kt + NS - 1 exists and this wave stages its share of it here.  (The convolution's
     // gather recomputes per-lane offsets at tap boundaries behind a branch: its LDS-DMA instructions stay in front of the k-steps.)
     auto ktile = [&](int kt, auto more_tag) {
-        constexpr bool MORE = decltype(more_tag)::value && !(ABL & 4) && !LW;
+        constexpr bool MORE = decltype(more_tag)::value && !LW;
         if constexpr (CONV && MORE) { stage(nxt, kt + NS - 1); __builtin_amdgcn_sched_barrier(0); }
         if constexpr (!decltype(more_tag)::value) {   // residual rows of the epilogue: requested in front of the LAST K-tile
             if (PREF && kt == nk - 1 && Rb && plain_epi) prefetch_residual();
@@ -1005,14 +1045,6 @@ gemm_conv_kernel(const Params p) {
         __syncthreads();                               // the patches of the staged epilogue reuse this memory
     }
     if (prof_on) pt2 = prof_now();
-    if constexpr (ABL & 8) {
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) asm volatile("" :: "v"(acc[i][j]));
-        if (prof_on) prof_leave(p.prof, p.prof_detail, pt0, pt1, pt2);
-        return;
-    }
     // ---------------------------------------------------------------- fused LayerNorm (consumer side), part 2
     // A was the raw row x; with W' = W*gamma:  Linear(LN(x))[m][n] = rstd_m * (acc[m][n] - mean_m * colsum_n) + t_n
     // (t_n arrives as the bias).  The rank-1 term -mean_m * colsum_n is one more MFMA k-step per fragment, fed from
@@ -1424,7 +1456,7 @@ gemm_conv_kernel(const Params p) {
             float bv[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) bv[k] = 0.f;
-            if (bias && ncok && !(ABL & 16)) {
+            if (bias && ncok) {
                 const float4 b0 = *(const float4*)(bias + nc), b1 = *(const float4*)(bias + nc + 4);
                 bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w; bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
             }
@@ -1437,7 +1469,7 @@ gemm_conv_kernel(const Params p) {
                     for (int k = 0; k < 16; ++k) cv[k] = 0.f;
                 }
                 uint4 rv[NP];
-                if (Rb && !(ABL & 64)) {
+                if (Rb) {
 #pragma unroll
                     for (int ps = 0; ps < NP; ++ps) {
                         const int m = mb + ps * RPI + rr;
@@ -1475,7 +1507,7 @@ gemm_conv_kernel(const Params p) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k) o[k] = o[k] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554669595930157f * o[k]));
                     }
-                    if (Rb && !(ABL & 64)) {
+                    if (Rb) {
                         const unsigned u[4] = {rv[ps].x, rv[ps].y, rv[ps].z, rv[ps].w};
 #pragma unroll
                         for (int k = 0; k < 4; ++k) { o[2 * k] += bf2f((bf16_t)(u[k] & 0xffff)); o[2 * k + 1] += bf2f((bf16_t)(u[k] >> 16)); }
@@ -1487,8 +1519,7 @@ gemm_conv_kernel(const Params p) {
                     } else {
                         uint4 v;
                         v.x = pack_bf2(o[0], o[1]); v.y = pack_bf2(o[2], o[3]); v.z = pack_bf2(o[4], o[5]); v.w = pack_bf2(o[6], o[7]);
-                        if constexpr (ABL & 32) asm volatile("" :: "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-                        else *(uint4*)(Cb + (int64_t)conv_store_row(m) * p.ldc + nc) = v;
+                        *(uint4*)(Cb + (int64_t)conv_store_row(m) * p.ldc + nc) = v;
                         if constexpr (F8C) if (p.f8copy) {
                             // the next GEMM's A operand: the row AS STORED, as e4m3 with one E8M0 scale per 32 columns (MX block = the 4
                             // adjacent lanes of this row; M % 32 == 0 and N % 32 == 0, so a block's lanes are all here)
@@ -1528,7 +1559,7 @@ gemm_conv_kernel(const Params p) {
             for (int c = 0; c < C2; ++c) chunk(c * 2, std::integral_constant<int, 2>{}, fl_tag);
             if constexpr (FN & 1) chunk(FN - 1, std::integral_constant<int, 1>{}, fl_tag);
         };
-        const bool fastp = (WPREF || !Rb) && !f32out && p.epilogue == TMIX_EPI_NONE && (!p.rgb || (CONV && rgb_one)) && !(ABL & 0xf0);      // (ablation bit 7: the generic form only)
+        const bool fastp = (WPREF || !Rb) && !f32out && p.epilogue == TMIX_EPI_NONE && (!p.rgb || (CONV && rgb_one));
         bool f8q = false;
         if constexpr (F8C) f8q = p.f8copy != nullptr;
         // flavour bits: 1 straight-line, 2 row statistics, 4 e4m3 copy, 8 column statistics
@@ -1651,28 +1682,11 @@ int launch_cfg(Params& p, int batch, hipStream_t st) {
     constexpr int SMEM = ((PH >= 1 && PH <= 3) ? 4 * (BM + BN) * 64 : NS * ((BM + BN) * 128 + (PH == 5 ? 1024 : 0))) + (BM + BN) * 16 + BM * 4 + BN * 4 + (CONV ? BN * 4 : 0)      // staging ring + fused-LayerNorm block + the tile's bias (+ time-embedding row)
                        + (PH == 3 ? BM * f8_block_cap(BN) : 0);                                          // + the tile's MX block scales of A
     static_assert(SMEM <= 160 * 1024, "LDS");
-    static bool attr_set = false;   // idempotent; racing threads set the same value
-    auto kern = gemm_conv_kernel<BM, BN, WM, WN, NS, CONV, LW, PH, KS, CS, EK, SC>;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) TMIX_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
     p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
     p.group_m = BM >= 256 ? 4 : 8;
     if (BM >= 256 && BN >= 256) p.group_m = 8;
-    // the kernels remap the LINEAR workgroup id over the whole (tiles, slices) grid in 32-bit arithmetic (common.h xcd_remap_grid)
-    if ((int64_t)p.tiles_m * p.tiles_n * batch > 0x7fffffffLL) TMIX_FAIL(TMIX_ESHAPE, "gemm: %lld x %d workgroups exceed the 32-bit linear grid id", (long long)p.tiles_m * p.tiles_n, batch);
-    dim3 grid(p.tiles_m * p.tiles_n, batch, 1);
-    p.prof = tmix_prof_take(&p.prof_detail);
-    tmix_prefetch_take(&p.pf, &p.pf_bytes);
-    { const long long nthr = (long long)grid.x * grid.y * (LW ? LW : WM * WN * KS) * 64, lines = (p.pf_bytes + 127) >> 7;
-      p.pf_per = p.pf ? (int)((lines + nthr - 1) / nthr) : 0; }
-    kern<<<grid, (WM * WN * KS + LW) * 64, SMEM, st>>>(p);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
+    return launch_tiles<gemm_conv_kernel<BM, BN, WM, WN, NS, CONV, LW, PH, KS, CS, EK, SC>>(p, p, batch, (WM * WN * KS + LW) * 64, SMEM, (LW ? LW : WM * WN * KS) * 64, st, "gemm");
 }
-
 
 // the instantiation of a tiling that holds what this launch needs and nothing else: the epilogue family EK (gemm_conv_kernel), with or without
 // the column statistics of Params::cs_out
@@ -1699,9 +1713,7 @@ int launch_group3(int cfg, int conv, int f8, Params& p, int batch, hipStream_t s
 int launch_group4(int cfg, int conv, int f8, Params& p, int batch, hipStream_t st);
 int launch_group5(int cfg, int conv, int f8, Params& p, int batch, hipStream_t st);      // fp8 in the lock-step loops (f8 = 3: per-row A scales, 4: MX blocks)
 bool w22_eligible(const Params& p, int conv, int f8);                                   // gemm_w22.hip (tiling 23)
-int launch_w22(Params& p, int batch, hipStream_t st, int l2_prefetcher = 0);            // (1: tiling 25, three DMA loaders + an L2 prefetcher wave)
-bool ff1p_eligible(const Params& p, int conv, int f8, int batch);                        // gemm_ff1p.hip (tiling 24)
-int launch_ff1p(Params& p, hipStream_t st);
+int launch_w22(Params& p, int batch, hipStream_t st);
 bool convh_eligible(const Params& p, int conv, int f8);                                 // gemm_convh.hip (tiling 26)
 int launch_convh(Params& p, hipStream_t st);
 // gemm_qattn.hip: attn2.to_q + the cross-attention behind it in one launch (tmix_gemm_q_cross_attn)

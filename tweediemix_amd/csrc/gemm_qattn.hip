@@ -31,11 +31,7 @@ struct QAParams {
 
 namespace {
 
-#ifdef TMIX_QATTN_H4      // dev A/B builds (VERDICT r5 item 6 ii): FOUR heads per tile -- 64 x 256, four math + four loader waves, 40 KB K-tiles, 320 tiles at M = 4096 (1.25 rounds)
-constexpr int Q_BM = 64, Q_BN = 256, Q_NS = 3, Q_NW = 4, Q_LW = 4;
-#else
 constexpr int Q_BM = 64, Q_BN = 320, Q_NS = 3, Q_NW = 5, Q_LW = 3;
-#endif
 constexpr int Q_ATILE = Q_BM * 128, Q_BTILE = Q_BN * 128, Q_STAGE = Q_ATILE + Q_BTILE, Q_RING = Q_NS * Q_STAGE;
 constexpr int Q_IA = Q_BM / 8, Q_IB = Q_BN / 8, Q_L = (Q_IA + Q_IB) / Q_LW;         // 8 + 40 LDS-DMA instructions per K-tile, 16 per loader
 static_assert((Q_IA + Q_IB) % Q_LW == 0 && (Q_NS - 2) * Q_L <= 63, "loader geometry");
@@ -56,32 +52,12 @@ __global__ void __launch_bounds__((Q_NW + Q_LW) * 64, 2) gemm_qattn_kernel(const
     const bool prof_on = p.prof != nullptr && tid == 0;
     unsigned long long pt0 = 0, pt1 = 0, pt2 = 0;
     if (prof_on) pt0 = prof_enter(p.prof, (blockIdx.x | blockIdx.y) == 0, p.prof_detail);
-    // the NEXT launch's weights (tmix_gemm_prefetch_next): touched by the loader waves in front of K-tile 0 (gemm_kernel.h)
-    constexpr int PFU = 8;
-    unsigned pf_keep[PFU];
-#pragma unroll
-    for (int u = 0; u < PFU; ++u) pf_keep[u] = 0;
-    if (p.pf && loader) {
-        const long long nwg = (long long)gridDim.x * gridDim.y, nth = Q_LW * 64;
-        const long long lines = (p.pf_bytes + 127) >> 7; const int per = p.pf_per;
-        const long long first = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * nth + (tid - Q_NW * 64);
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) {
-            const long long ln = first + (long long)u * nwg * nth;
-            if (u < per && ln < lines) asm volatile("global_load_dword %0, %1, off" : "=v"(pf_keep[u]) : "v"(p.pf + (ln << 7)) : "memory");
-        }
-    }
-    int bid, by;
-    xcd_remap_grid(bid, by);
-    const int per_group = p.group_m * p.tiles_n;
-    const int grp = bid / per_group;
-    const int first_m = grp * p.group_m;
-    const int gsize = min(p.tiles_m - first_m, p.group_m);
-    const int rem = bid - grp * per_group;
-    const int tile_n = rem / gsize, tile_m = first_m + (rem - tile_n * gsize);
-    const int m0 = tile_m * Q_BM, n0 = tile_n * Q_BN;
-    const int bzw = p.w_period > 0 ? (int)__umulhi((unsigned)by, p.w_magic) : by;
-    const int bz = p.w_period > 0 ? (by - bzw * p.w_groups) * p.w_period + bzw : by;
+    // the NEXT launch's weights: touched by the loader waves in front of K-tile 0 (gemm_kernel.h TMIX_PF_TOUCH)
+    TMIX_PF_TOUCH(p, pf_keep, loader, Q_LW * 64, tid - Q_NW * 64);
+    const TileId tile = tile_of_workgroup(p);
+    const int m0 = tile.tile_m * Q_BM, n0 = tile.tile_n * Q_BN;
+    const BatchSlice slice = slice_of_workgroup(p, tile.by);
+    const int bz = slice.bz, bzw = slice.bzw;
     const bf16_t* Ab = p.A + (int64_t)bz * p.strideA;
     const bf16_t* Wb = p.W + (int64_t)bzw * p.strideW;
     const int nk = p.K / BK;
@@ -120,8 +96,7 @@ __global__ void __launch_bounds__((Q_NW + Q_LW) * 64, 2) gemm_qattn_kernel(const
         for (int t = 0; t < PRE; ++t)
             if (t < nk) stage(t, t);
         if (nk >= PRE) wait_vmcnt<(PRE - 1) * Q_L>(); else wait_vmcnt<0>();
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));
+        pf_keep_alive(pf_keep);
         __builtin_amdgcn_s_barrier();
         int nxt = Q_NS - 1;
         for (int kt = 0; kt < nk; ++kt) {
@@ -173,20 +148,9 @@ __global__ void __launch_bounds__((Q_NW + Q_LW) * 64, 2) gemm_qattn_kernel(const
                 if (q < p.ln_parts) { s1 += __uint_as_float(lnv[q].x); s2 += __uint_as_float(lnv[q].y); }
             const float mean = s1 * p.ln_inv_c;
             ln_rs[tid] = rsqrtf(fmaxf(s2 * p.ln_inv_c - mean * mean, 0.f) + p.ln_eps);
-            const float x = -mean;
-            const unsigned x1 = __float_as_uint(x) & 0xffff0000u;
-            const float r1 = x - __uint_as_float(x1);
-            const unsigned x2 = __float_as_uint(r1) & 0xffff0000u;
-            const unsigned x3 = __float_as_uint(r1 - __uint_as_float(x2)) & 0xffff0000u;
-            ln_mfrag[tid] = make_uint4((x1 >> 16) | x1, x2 >> 16, (x1 >> 16) | x3, x2 >> 16);
+            ln_mfrag[tid] = ln_mean_operand(-mean);
         }
-        if (tid < Q_BN) {
-            const unsigned x1 = __float_as_uint(ln_cs) & 0xffff0000u;
-            const float r1 = ln_cs - __uint_as_float(x1);
-            const unsigned x2 = __float_as_uint(r1) & 0xffff0000u;
-            const unsigned x3 = __float_as_uint(r1 - __uint_as_float(x2)) & 0xffff0000u;
-            ln_cfrag[tid] = make_uint4((x1 >> 16) | x2, x1 >> 16, (x3 >> 16) | x1, x2 >> 16);
-        }
+        if (tid < Q_BN) ln_cfrag[tid] = ln_colsum_operand(ln_cs);
     }
 
     f32x4 acc[4][4];                                   // [query fragment i][d fragment j]: lane holds query 16 i + l15, d = 16 j + 4 lg + r
@@ -227,9 +191,6 @@ __global__ void __launch_bounds__((Q_NW + Q_LW) * 64, 2) gemm_qattn_kernel(const
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int i = q >> 2, j = q & 3;
-#ifdef TMIX_QATTN_ABL4      // dev ablation (tools/build_variant.sh): the fifth math wave (the second one on its SIMD) issues no MFMAs in the K loop -- wrong results, the loop's
-            if (h < 4)               // time without the doubly-loaded SIMD
-#endif
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[S][j], fa[S][i], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (q < 4) fa[1 - S][q] = *(const frag_ab*)(pa + q * 16 * 128);
@@ -403,30 +364,15 @@ int launch_qattn(Params& p, const QAExtra& x, int batch, hipStream_t st) {
         TMIX_FAIL(TMIX_EALIGN, "gemm_q_cross_attn: K (8-byte), V^T / O (16-byte) alignment");
     constexpr int SMEM = Q_RING + (Q_BM + Q_BN) * 16 + Q_BM * 4 + Q_BN * 4;
     static_assert(SMEM <= 160 * 1024, "LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_qattn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) TMIX_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
     QAParams q;
     p.tiles_m = (p.M + Q_BM - 1) / Q_BM; p.tiles_n = p.N / Q_BN;
     p.group_m = 16;
-    // the kernels remap the LINEAR workgroup id over the whole (tiles, slices) grid in 32-bit arithmetic (common.h xcd_remap_grid)
-    if ((int64_t)p.tiles_m * p.tiles_n * batch > 0x7fffffffLL) TMIX_FAIL(TMIX_ESHAPE, "gemm: %lld x %d workgroups exceed the 32-bit linear grid id", (long long)p.tiles_m * p.tiles_n, batch);
-    dim3 grid(p.tiles_m * p.tiles_n, batch, 1);
-    p.prof = tmix_prof_take(&p.prof_detail);
-    tmix_prefetch_take(&p.pf, &p.pf_bytes);
-    { const long long nthr = (long long)grid.x * grid.y * Q_LW * 64, lines = (p.pf_bytes + 127) >> 7;
-      p.pf_per = p.pf ? (int)((lines + nthr - 1) / nthr) : 0; }
-    q.g = p;
+    q.g = p;                                           // (the launch fills prof / pf / pf_per of THIS copy, the one the kernel reads; the caller's p is not read again)
     q.Kc = (const bf16_t*)x.K; q.ldk = x.ldk; q.strideK = x.strideK;
     q.Vt = (const bf16_t*)x.Vt; q.ldvt = x.ldvt; q.strideVt = x.strideVt;
     q.O = (bf16_t*)x.O; q.ldo = x.ldo;
     q.rows_per_image = x.rows_per_image; q.Skv = x.Skv; q.scale_log2e = x.scale * 1.4426950408889634f;
-    gemm_qattn_kernel<<<grid, (Q_NW + Q_LW) * 64, SMEM, st>>>(q);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
+    return launch_tiles<gemm_qattn_kernel>(q.g, q, batch, (Q_NW + Q_LW) * 64, SMEM, Q_LW * 64, st, "gemm_q_cross_attn");
 }
 
 }  // namespace tmix_gemm

@@ -33,11 +33,6 @@ struct Tiling {
     unsigned char fb, fb_conv;    // fallback of a GEMM / a convolution that needs a capability this tiling lacks (own kernels: that they cannot run); 0 = none needed
 };
 
-#ifdef TMIX_EXPERIMENTAL_TILINGS      // dev variants (make EXPERIMENTAL=1): the library contains and dispatches tilings 24 and 25
-#define TMIX_RESERVED(id, as) id
-#else                                 // the shipped library: ids 24 / 25 are reserved and run as the tilings they were variants of (same bits)
-#define TMIX_RESERVED(id, as) as
-#endif
 constexpr unsigned CAPS_PLAIN = CAP_CONV | CAP_SC | CAP_F8C | CAP_CS;      // the lock-step tilings without loader waves: every epilogue family, GEMM and convolution
 
 constexpr Tiling TILINGS[NUM_CFG + 1] = {
@@ -91,16 +86,14 @@ constexpr Tiling TILINGS[NUM_CFG + 1] = {
     {  256, 320, PHASE_OFFSET, 4,        0, 22, 0,                                       14, 14},
     // 23 = 128x160 over 2 x 2 math waves of 64x80 on v_mfma_f32_16x16x32_bf16 + four loader waves (its own kernel: gemm_w22.hip): the staged plain bf16 epilogue only
     {  128, 160, OWN_KERNEL,   NO_GROUP, 4, 23, 0,                                       21, 12},
-    // 24 = 256x320 (tiling 14's tile and arithmetic) on PERSISTENT workgroups: one per CU walks its tiles, the next tile's first K-tile requested under the last one
-    // (gemm_ff1p.hip); 25 = tiling 23 with the fourth loader wave as an L2 PREFETCHER (touches the tile's operand lines eight K-tiles ahead of the ring).
-    // Both measured slower in the step: dev builds only
-    {  256, 320, OWN_KERNEL,   NO_GROUP, 0, TMIX_RESERVED(24, 14), 0,                    14, 14},
-    {  128, 160, OWN_KERNEL,   NO_GROUP, 3, TMIX_RESERVED(25, 23), 0,                    21, 12},
+    // 24 / 25 = reserved: they were 256x320 on persistent workgroups and tiling 23 with an L2 prefetcher wave, both measured slower in the step (DESIGN.md 5b
+    // items 5, 6) and removed; the ids stay valid and run as the tilings they were variants of (same bits)
+    {  256, 320, OWN_KERNEL,   NO_GROUP, 0, 14, 0,                                       14, 14},
+    {  128, 160, OWN_KERNEL,   NO_GROUP, 3, 23, 0,                                       21, 12},
     // 26 = 3x3 stride-1 convolution with the input halo patch resident in LDS (4 x 32 pixel tiles, channel-chunk-major K loop; its own kernel: gemm_convh.hip);
     // anything it does not carry runs as the loader-wave tilings 20 (conv) / 21 (GEMM)
     {  128, 160, OWN_KERNEL,   NO_GROUP, 0, 26, CAP_CONV | CAP_SC | CAP_CS,              21, 20},
 };
-#undef TMIX_RESERVED
 
 constexpr bool tile_has(int cfg, unsigned cap) { return (TILINGS[cfg].caps & cap) != 0; }
 
@@ -134,7 +127,7 @@ struct TileTraits {
     int n_trans_begin, wide, epilogue;       // as in Params
     bool f8copy, f8out, stats_out, cs_out, rowgroup_bias;
     int M, N, K, batch;
-    bool w22_ok, convh_ok, ff1p_ok;          // w22_eligible / convh_eligible / ff1p_eligible of this launch (the predicates live next to their kernels)
+    bool w22_ok, convh_ok;                   // w22_eligible / convh_eligible of this launch (the predicates live next to their kernels)
 };
 // f8: mode of the kernel's loop on e4m3 operands -- 0 = bf16, 1 / 2 = phase-offset loop with per-row / MX block scales on A, 3 / 4 = the same in the lock-step loop
 struct TileChoice { int cfg, f8, err; };

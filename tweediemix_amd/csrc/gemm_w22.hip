@@ -21,7 +21,7 @@ constexpr int W_BM = 128, W_BN = 160, W_NS = 4, W_LW = 4, W_NW = 4;
 constexpr int W_TM = 64, W_TN = 80, W_FM = 4, W_FN = 5;               // wave tile and its 16 x 16 fragments
 constexpr int W_ATILE = W_BM * 128, W_BTILE = W_BN * 128, W_STAGE = W_ATILE + W_BTILE;
 constexpr int W_RING = W_NS * W_STAGE;
-// (LDS-DMA instructions per K-tile: 16 for A + 20 for W, dealt to the 4 -- or 3, tiling 25 -- DMA loader waves)
+// (LDS-DMA instructions per K-tile: 16 for A + 20 for W, dealt to the 4 loader waves)
 constexpr int W_SR = W_TN * 4 + 16;                                    // bytes per row of a wave's staging patch (80 fp32 columns + pad)
 constexpr int W_PATCH = 32 * W_SR;                                     // 32-row half of a wave tile
 constexpr int W_CG = W_TN / 8;                                         // 8-column groups per row of a wave tile (one 16-byte store each)
@@ -29,57 +29,21 @@ constexpr int W_PASSES = (32 * W_CG) / 64;                             // read-b
 static_assert((W_BM / 8) % W_LW == 0 && (W_BN / 8) % W_LW == 0 && (32 * W_CG) % 64 == 0, "geometry");
 static_assert(W_NW * W_PATCH + 2 * W_BM * W_CG * 8 <= W_RING, "epilogue patches + statistics exchange fit in the staging ring");
 
-// PFW = 1 (tiling 25): the fourth loader wave issues no LDS-DMA -- it walks W_PD K-tiles AHEAD of the ring and touches this tile's A and W lines (one dword per 128-byte
-// line), so that they are in this XCD's L2 when the three DMA loaders ask for them: the ring holds 2 - 3 K-tiles (~1.5 us of lookahead), a line that comes cold through the
-// fabric takes longer than that, and nothing in the LDS budget can deepen the ring.  Its own wave, because vmcnt retires in order: a slow touch in a DMA loader's queue would hold
-// back the hand-over of every K-tile behind it.
-constexpr int W_PD = 8;
-template <int PFW>
 __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifndef TMIX_NO_KERNARG_TOUCH
     kernarg_touch<(int)sizeof(Params)>();
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = w >= W_NW;
     const bool prof_on = p.prof != nullptr && tid == 0;
     unsigned long long pt0 = 0, pt1 = 0, pt2 = 0;
     if (prof_on) pt0 = prof_enter(p.prof, (blockIdx.x | blockIdx.y) == 0, p.prof_detail);
-    // the NEXT launch's weights (tmix_gemm_prefetch_next): touched by the loader waves IN FRONT of K-tile 0, whose counted vmcnt waits cover the loads.
-    // (Round 5 moved the touches behind the first barrier and then spread them over the K loop -- tools/jobs5/r5g_pf.sh, r5h_pf2.sh: the prologue shrinks by what
-    // the loop grows, 2.5 us per launch in front of a 9.8 MB q/k/v weight wherever they sit; the step came out 0.1 - 0.3 ms slower both times.)
-    constexpr int PFU = 8;
-    unsigned pf_keep[PFU];
-#pragma unroll
-    for (int u = 0; u < PFU; ++u) pf_keep[u] = 0;
-#ifdef TMIX_W22_PF_MATH
-    const bool pf_here = false;
-#else
-    const bool pf_here = loader;
-#endif
-    if (p.pf && pf_here) {
-        const long long nwg = (long long)gridDim.x * gridDim.y, nth = W_LW * 64;
-        const long long lines = (p.pf_bytes + 127) >> 7; const int per = p.pf_per;
-        const long long first = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * nth + (tid - W_NW * 64);
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) {
-            const long long ln = first + (long long)u * nwg * nth;
-            if (u < per && ln < lines) asm volatile("global_load_dword %0, %1, off" : "=v"(pf_keep[u]) : "v"(p.pf + (ln << 7)) : "memory");
-        }
-    }
-    // tile order: gemm_kernel.h's (each XCD owns a compact patch of group_m x (64 / group_m) tiles)
-    int bid, by;
-    xcd_remap_grid(bid, by);
-    const int per_group = p.group_m * p.tiles_n;
-    const int grp = bid / per_group;
-    const int first_m = grp * p.group_m;
-    const int gsize = min(p.tiles_m - first_m, p.group_m);
-    const int rem = bid - grp * per_group;
-    const int tile_n = rem / gsize, tile_m = first_m + (rem - tile_n * gsize);
-    const int m0 = tile_m * W_BM, n0 = tile_n * W_BN;
-    const int bzw = p.w_period > 0 ? (int)__umulhi((unsigned)by, p.w_magic) : by;
-    const int bz = p.w_period > 0 ? (by - bzw * p.w_groups) * p.w_period + bzw : by;
+    // the NEXT launch's weights: touched by the loader waves IN FRONT of K-tile 0, whose counted vmcnt waits cover the loads (gemm_kernel.h TMIX_PF_TOUCH)
+    TMIX_PF_TOUCH(p, pf_keep, loader, W_LW * 64, tid - W_NW * 64);
+    const TileId tile = tile_of_workgroup(p);
+    const int tile_n = tile.tile_n, m0 = tile.tile_m * W_BM, n0 = tile_n * W_BN;
+    const BatchSlice slice = slice_of_workgroup(p, tile.by);
+    const int bz = slice.bz, bzw = slice.bzw;
     const bf16_t* Ab = p.A + (int64_t)bz * p.strideA;
     const bf16_t* Wb = p.W + (int64_t)bzw * p.strideW;
     const int nk = p.K / BK;
@@ -90,38 +54,9 @@ __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const P
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, p.bytesA, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)Wb, 0, p.bytesW, 0x00020000);
         const int s = w - W_NW, lrow = lane >> 3;
-        constexpr int DL = W_LW - PFW, IA = W_BM / 8, L = (W_BM / 8 + W_BN / 8) / DL;        // DMA loaders; A instructions of a K-tile; instructions per loader
-        static_assert((W_BM / 8 + W_BN / 8) % DL == 0 && (W_NS - 2) * L <= 63, "loader geometry");
-        if (PFW && s == DL) {
-            // ---- L2 prefetcher wave: line slot i * 64 + lane = A row (< 128) or W row of the tile
-            constexpr int NLI = (W_BM + W_BN + 63) / 64;
-            const char* lp[NLI];
-#pragma unroll
-            for (int i = 0; i < NLI; ++i) {
-                const int line = i * 64 + lane;
-                lp[i] = line < W_BM ? (const char*)Ab + (int64_t)min(m0 + line, p.M - 1) * p.lda * 2
-                      : line < W_BM + W_BN ? (const char*)Wb + (int64_t)min(n0 + line - W_BM, p.N - 1) * p.ldw * 2 : nullptr;
-            }
-            unsigned sink = 0;
-            auto touch = [&](int kp) __attribute__((always_inline)) {
-#pragma unroll
-                for (int i = 0; i < NLI; ++i)
-                    if (lp[i]) asm volatile("global_load_dword %0, %1, off" : "+v"(sink) : "v"(lp[i] + (int64_t)kp * (BK * 2)) : "memory");
-            };
-            for (int kp = W_NS - 1; kp <= W_PD && kp < nk; ++kp) touch(kp);
-            __builtin_amdgcn_s_barrier();
-            for (int kt = 0; kt < nk; ++kt) {
-                if (kt + W_PD + 1 < nk) touch(kt + W_PD + 1);
-                __builtin_amdgcn_s_barrier();
-            }
-            wait_vmcnt<0>();
-            asm volatile("" :: "v"(sink));
-#pragma unroll
-            for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));
-            if (p.stats_out) __syncthreads();
-            return;
-        }
-        // DMA loaders: instruction g = DL r + s of a K-tile: g < 16 -> A rows 8 g .., else W rows 8 (g - 16) ..; the swizzle depends on the instruction's parity only
+        constexpr int IA = W_BM / 8, L = (W_BM / 8 + W_BN / 8) / W_LW;        // A instructions of a K-tile; instructions per loader
+        static_assert((W_BM / 8 + W_BN / 8) % W_LW == 0 && (W_NS - 2) * L <= 63, "loader geometry");
+        // loaders: instruction g = 4 r + s of a K-tile: g < 16 -> A rows 8 g .., else W rows 8 (g - 16) ..; the swizzle depends on the instruction's parity only
         const unsigned sw0 = (unsigned)(((lane & 7) ^ ((lane >> 4) & 7)) * 16), sw1 = (unsigned)(((lane & 7) ^ ((4 + (lane >> 4)) & 7)) * 16);
         const unsigned aoff0 = (unsigned)(m0 + lrow) * (unsigned)p.lda * 2u + sw0, dA = 16u * (unsigned)p.lda + sw1 - sw0;
         const unsigned woff0 = (unsigned)(n0 + lrow) * (unsigned)p.ldw * 2u + sw0, dW = 16u * (unsigned)p.ldw + sw1 - sw0;
@@ -131,7 +66,7 @@ __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const P
             char* sW = sA + W_ATILE;
 #pragma unroll
             for (int r = 0; r < L; ++r) {
-                const int g = r * DL + s;              // wave-uniform
+                const int g = r * W_LW + s;             // wave-uniform
                 if (g < IA) {
                     const unsigned odd = 0u - (unsigned)(g & 1);
                     blds16(rsA, min(aoff0 + (dA & odd) + (unsigned)(g >> 1) * (unsigned)(32 * p.lda), amax0 + (dS & odd)), (unsigned)kt * (BK * 2), sA + g * 1024);
@@ -146,8 +81,7 @@ __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const P
         for (int t = 0; t < PRE; ++t)
             if (t < nk) stage(t, t);
         if (nk >= PRE) wait_vmcnt<(PRE - 1) * L>(); else wait_vmcnt<0>();
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) asm volatile("" :: "v"(pf_keep[u]));
+        pf_keep_alive(pf_keep);
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int t = PRE; t < W_NS - 1; ++t)
@@ -190,7 +124,7 @@ __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const P
         }
         if (tid < W_BN) ln_cs = (p.ln_colsum + (int64_t)bzw * p.strideLnColsum)[min(n0 + tid, p.N - 1)];
     }
-    // (the operand pieces of the rank-1 term -mean_m * colsum_n: x = x1 + x2 + x3 in bf16 pieces, see gemm_kernel.h ln_reduce)
+    // (the operand pieces of the rank-1 term -mean_m * colsum_n: gemm_kernel.h ln_mean_operand / ln_colsum_operand)
     if (tid < W_BN) bias_lds[tid] = bias_r;
     if (ln_on) {
         if (tid < W_BM) {
@@ -200,20 +134,9 @@ __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const P
                 if (q < p.ln_parts) { s1 += __uint_as_float(lnv[q].x); s2 += __uint_as_float(lnv[q].y); }
             const float mean = s1 * p.ln_inv_c;
             ln_rs[tid] = rsqrtf(fmaxf(s2 * p.ln_inv_c - mean * mean, 0.f) + p.ln_eps);
-            const float x = -mean;
-            const unsigned x1 = __float_as_uint(x) & 0xffff0000u;
-            const float r1 = x - __uint_as_float(x1);
-            const unsigned x2 = __float_as_uint(r1) & 0xffff0000u;
-            const unsigned x3 = __float_as_uint(r1 - __uint_as_float(x2)) & 0xffff0000u;
-            ln_mfrag[tid] = make_uint4((x1 >> 16) | x1, x2 >> 16, (x1 >> 16) | x3, x2 >> 16);
+            ln_mfrag[tid] = ln_mean_operand(-mean);
         }
-        if (tid < W_BN) {
-            const unsigned x1 = __float_as_uint(ln_cs) & 0xffff0000u;
-            const float r1 = ln_cs - __uint_as_float(x1);
-            const unsigned x2 = __float_as_uint(r1) & 0xffff0000u;
-            const unsigned x3 = __float_as_uint(r1 - __uint_as_float(x2)) & 0xffff0000u;
-            ln_cfrag[tid] = make_uint4((x1 >> 16) | x2, x1 >> 16, (x3 >> 16) | x1, x2 >> 16);
-        }
+        if (tid < W_BN) ln_cfrag[tid] = ln_colsum_operand(ln_cs);
     }
 
     f32x4 acc[W_FM][W_FN];
@@ -242,21 +165,6 @@ __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const P
             }
     };
 
-#ifdef TMIX_W22_PF_MATH
-    // (dev variant) the touches ride in the MATH waves' queue, which nothing waits on until the residual rows are asked for: the loaders' first K-tile is not behind them
-    unsigned pf_sink = 0;
-    if (p.pf) {
-        static_assert(W_NW == W_LW, "the host deals the lines out over W_LW * 64 threads per workgroup");
-        const long long nwg = (long long)gridDim.x * gridDim.y, nth = W_NW * 64;
-        const long long lines = (p.pf_bytes + 127) >> 7; const int per = p.pf_per;
-        const long long first = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * nth + tid;
-#pragma unroll
-        for (int u = 0; u < PFU; ++u) {
-            const long long ln = first + (long long)u * nwg * nth;
-            if (u < per && ln < lines) asm volatile("global_load_dword %0, %1, off" : "+v"(pf_sink) : "v"(p.pf + (ln << 7)) : "memory");
-        }
-    }
-#endif
     __builtin_amdgcn_s_barrier();                      // K-tile 0 has landed
     asm volatile("" ::: "memory");
     if (prof_on) pt1 = prof_now();
@@ -282,9 +190,6 @@ __global__ void __launch_bounds__((W_NW + W_LW) * 64, 2) gemm_w22_kernel(const P
     };
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
-#ifdef TMIX_W22_PF_MATH
-        if (kt == nk - 1) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(pf_sink) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#endif
         if (kt == nk - 1) { epi_prefetch(); __builtin_amdgcn_sched_barrier(0); }
         kstep(0, cur, c1);
         // every fragment of tile kt is in registers (its ring slot may be restaged after the barrier); tile kt + 1 has landed
@@ -392,33 +297,12 @@ bool w22_eligible(const Params& p, int conv, int f8) {
            && (p.N % W_BN) == 0 && (!p.R || (p.ldr % 8) == 0);
 }
 
-template <int PFW> static int launch_w22_t(Params& p, int batch, hipStream_t st) {
+int launch_w22(Params& p, int batch, hipStream_t st) {
     constexpr int SMEM = W_RING + (W_BM + W_BN) * 16 + W_BM * 4 + W_BN * 4;
     static_assert(SMEM <= 160 * 1024, "LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_w22_kernel<PFW>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) TMIX_FAIL((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
     p.tiles_m = (p.M + W_BM - 1) / W_BM; p.tiles_n = (p.N + W_BN - 1) / W_BN;
     p.group_m = 8;
-    // the kernels remap the LINEAR workgroup id over the whole (tiles, slices) grid in 32-bit arithmetic (common.h xcd_remap_grid)
-    if ((int64_t)p.tiles_m * p.tiles_n * batch > 0x7fffffffLL) TMIX_FAIL(TMIX_ESHAPE, "gemm: %lld x %d workgroups exceed the 32-bit linear grid id", (long long)p.tiles_m * p.tiles_n, batch);
-    dim3 grid(p.tiles_m * p.tiles_n, batch, 1);
-    p.prof = tmix_prof_take(&p.prof_detail);
-    tmix_prefetch_take(&p.pf, &p.pf_bytes);
-    { const long long nthr = (long long)grid.x * grid.y * W_LW * 64, lines = (p.pf_bytes + 127) >> 7;
-      p.pf_per = p.pf ? (int)((lines + nthr - 1) / nthr) : 0; }
-    gemm_w22_kernel<PFW><<<grid, (W_NW + W_LW) * 64, SMEM, st>>>(p);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
+    return launch_tiles<gemm_w22_kernel>(p, p, batch, (W_NW + W_LW) * 64, SMEM, W_LW * 64, st, "gemm (tiling 23)");
 }
-
-#ifdef TMIX_EXPERIMENTAL_TILINGS
-int launch_w22(Params& p, int batch, hipStream_t st, int l2_prefetcher) { return l2_prefetcher ? launch_w22_t<1>(p, batch, st) : launch_w22_t<0>(p, batch, st); }
-#else       // the prefetcher-wave form (tiling 25: 50 % slower) is compiled into dev variants only
-int launch_w22(Params& p, int batch, hipStream_t st, int) { return launch_w22_t<0>(p, batch, st); }
-#endif
 
 }  // namespace tmix_gemm
