@@ -23,6 +23,11 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          there is no tokenizer; --attn_mask_threshold, --save_attention_maps (raw maps as .npy).  Each rank
                          writes the masks it used as '<seg_concept>.jpg' into its side-car directory.  --mask_paths and
                          --random_masks still win over it
+  --long_prompts         prompts past CLIP's 77 tokens: every prompt row (negative, scene, per-concept) is cut into chunks of 75 tokens at
+                         word boundaries, each chunk encoded on its own, the hidden states concatenated: 154 or 231 cross-attention
+                         keys (at most 3 chunks = 225 tokens; more is an error, nothing is dropped).  A run whose prompts all fit one
+                         chunk is bit for bit the run without the flag.  --mask_token_ids then takes positions 77 * chunk + offset,
+                         --text_embeds_path embeddings of [*, 77 c, 2048], and --synthetic draws --synthetic_chunks c x 77 keys
   --keep_latents FILE    hold an earlier result while the loop samples only the --reroll regions anew: FILE is the '.latent.pt' a run
                          wrote ([1,4,h,w] of this resolution).  Needs --mask_paths (the regions must be known before the first step) and
                          --reroll; everything outside the regions comes back bit for bit in the final latent.  With --num_seeds N every
@@ -36,7 +41,8 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          (or runs under torch.distributed.run), every rank samples its seeds, the final latents are gathered
                          over RCCL and rank 0 writes the files (BASELINE config 4; the reference is single-GPU, sample_catdog.sh:3)
 
-Output: {output_path_all}/{prompt_orig}_{seed}.latent.pt, plus the .png when VAE weights are given.
+Output: {output_path_all}/{prompt_orig}_{seed}.latent.pt, plus the .png when VAE weights are given (a prompt of more than 200 bytes:
+its first 160 characters and 8 hex digits of its SHA-1, see output_stem).
 """
 import argparse
 import os
@@ -93,6 +99,9 @@ def build_parser():
     p.add_argument('--mask_token_ids', type=str, default='',
                    help="token positions per foreground concept, '+' between concepts, ',' within one (e.g. '4+7')")
     p.add_argument('--save_attention_maps', action='store_true')
+    p.add_argument('--long_prompts', action='store_true',
+                   help='chunked prompts: 75-token chunks encoded one by one and concatenated (77 c cross-attention keys, c <= 3)')
+    p.add_argument('--synthetic_chunks', type=int, default=1, help='--synthetic with --long_prompts: embeddings of 77 * c keys (c in 1..3)')
     p.add_argument('--keep_latents', type=str, default='', help="'.latent.pt' of an earlier run: kept outside the --reroll regions")
     p.add_argument('--keep_image', type=str, default='', help='RGB image of resolution_w x resolution_h: its VAE encoding is kept outside the --reroll regions')
     p.add_argument('--reroll', type=str, default='', help="regions sampled anew: '+'-separated --seg_concepts phrases or 0-based indices into them")
@@ -154,6 +163,20 @@ def save_attention_outputs(opt, tw, side_dir, seeds):
         for sd_, per in zip(seeds, tw.attention_maps):
             for lvl, m in per.items():
                 np.save(os.path.join(side_dir, f'attention_maps_{sd_}_level{lvl}.npy'), m)
+
+
+def output_stem(prompt_orig):
+    """the '{prompt_orig}' of the output file names (fusion_sampling.py:526).  A file name holds 255 bytes, which a --long_prompts scene
+    prompt exceeds: a stem over 200 bytes is cut to its first 160 characters (shortened further until they fit) plus 8 hex digits of the
+    whole prompt's SHA-1.  Every name that could be written before is unchanged."""
+    stem = prompt_orig.split('+')[0] or 'sample'
+    if len(stem.encode('utf-8')) <= 200:
+        return stem
+    import hashlib
+    head = stem[:160]
+    while len(head.encode('utf-8')) > 190:
+        head = head[:-1]
+    return head + '_' + hashlib.sha1(stem.encode('utf-8')).hexdigest()[:8]
 
 
 def noise_for_seed(seed, h, w):
@@ -268,13 +291,31 @@ def attention_token_ids(opt, tokenizer):
     from tweediemix_amd import text as T
     prompt = opt.prompt_orig.split('+')[0]
     try:
+        if opt.long_prompts:          # positions in the concatenated chunks; `tokenizer` is then the list the prompts were cut with
+            return [T.token_positions_long(tokenizer, prompt, ph) for ph in opt.seg_concepts.split('+')]
         return [T.phrase_token_positions(tokenizer, prompt, ph) for ph in opt.seg_concepts.split('+')]
     except ValueError as e:
         raise SystemExit(f'--mask_source attention: {e}')
 
 
+def check_long_prompt_args(opt):
+    if opt.synthetic_chunks != 1 and not (opt.long_prompts and opt.synthetic):
+        raise SystemExit('--synthetic_chunks belongs to --synthetic --long_prompts')
+    if not 1 <= opt.synthetic_chunks <= 3:
+        raise SystemExit(f'--synthetic_chunks {opt.synthetic_chunks}: 1..3 chunks of 77 keys')
+
+
+def check_long_embeds(opt, te, ts):
+    """--long_prompts: both embedding sets hold 77 c keys, the same c in 1..3; returns the key count"""
+    Lk = te[0].shape[1]
+    if Lk not in (77, 154, 231) or ts[0].shape[1] != Lk:
+        raise SystemExit(f'--long_prompts: text embeddings of {Lk} and {ts[0].shape[1]} keys; both sets need 77 c keys, the same c in 1..3')
+    return Lk
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
+    check_long_prompt_args(opt)
     if opt.dtype == 'fp8' and opt.lora_mode == 'lowrank':
         raise SystemExit('--dtype fp8 quantises the merged per-concept projection weights: use --lora_mode merged')
     keep = check_keep_args(opt)
@@ -305,8 +346,9 @@ def main(argv=None):
         sd = Wt.synthetic_state_dict(cfg, seed=1234, device=opt.device, dtype=torch.bfloat16)
         con = Wt.synthetic_concepts(cfg, kind, K, device=opt.device)
         g = torch.Generator().manual_seed(42)
-        te = (torch.randn(K + 2, 77, cfg.cross_dim, generator=g), torch.randn(K + 2, cfg.pooled_dim, generator=g))
-        ts = (torch.randn(K, 77, cfg.cross_dim, generator=g), torch.randn(K, cfg.pooled_dim, generator=g))
+        Lk = 77 * opt.synthetic_chunks                   # (1 without --long_prompts: the draws below are then today's)
+        te = (torch.randn(K + 2, Lk, cfg.cross_dim, generator=g), torch.randn(K + 2, cfg.pooled_dim, generator=g))
+        ts = (torch.randn(K, Lk, cfg.cross_dim, generator=g), torch.randn(K, cfg.pooled_dim, generator=g))
     else:
         unet_file = opt.unet_path or (opt.sd_path and find_weights(os.path.join(opt.sd_path, 'unet'), 'diffusion_pytorch_model'))
         if not (unet_file and (opt.text_embeds_path or opt.sd_path) and opt.personal_checkpoint):
@@ -322,8 +364,10 @@ def main(argv=None):
             from tweediemix_amd import text as T
             tpath = T.TextPath(opt.sd_path, opt.device)
             te, ts, K_text = tpath.embed(opt, sts)
-            tokenizer = tpath.tokenizers[0]
+            tokenizer = tpath.tokenizers if opt.long_prompts else tpath.tokenizers[0]
             assert K_text == K, (K_text, K)
+    if opt.long_prompts:
+        n_keys = check_long_embeds(opt, te, ts)
     W = U.UNetWeights(cfg, sd, opt.device, (kind, con), lora_mode=opt.lora_mode)
     h, w = opt.resolution_h // 8, opt.resolution_w // 8
     sidecar = False
@@ -335,6 +379,8 @@ def main(argv=None):
     elif opt.mask_source == 'attention':              # in-process masks: the provider below is never called
         fg = None
         attn = dict(tokens=attention_token_ids(opt, tokenizer), threshold=opt.attn_mask_threshold)
+        if opt.long_prompts and max(p for c in attn['tokens'] for p in c) >= n_keys:
+            raise SystemExit(f"--mask_token_ids: positions up to {n_keys - 1} ({n_keys // 77} chunks of 77 keys)")
         side_dir = M.sidecar_layout(opt.output_path, rank, world, local, opt.seg_gpu)[0]
     elif opt.synthetic:
         fg = None                                        # seeded rectangles, one set per trajectory seed (drawn when the sampler asks)
@@ -414,7 +460,7 @@ def main(argv=None):
                                    opt.num_seeds, rank, world)
     if rank == 0:
         os.makedirs(opt.output_path_all, exist_ok=True)
-        prompt_orig = opt.prompt_orig.split('+')[0] or 'sample'
+        prompt_orig = output_stem(opt.prompt_orig)
         for i in range(opt.num_seeds):
             out = f'{opt.output_path_all}/{prompt_orig}_{opt.seed + i}.latent.pt'
             torch.save(lat[i:i + 1].cpu(), out)

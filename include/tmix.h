@@ -456,6 +456,12 @@ int tmix_i2v_temporal_encoder(const float* x, float* y, int clips, int frames, i
 int tmix_xattn_token_maps(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK, float* maps,
                           int B, int H, int Sq, int Lk, int row0, int row_step, int n_rows, const int32_t* tokens, int n_tok,
                           int accumulate, float scale, void* stream);
+/* The same for chunked prompts (text.encode_prompts(long=True): 154 or 231 keys) and longer position lists: same arguments, same
+ * meaning and every property above, with Lk <= 240 and n_tok in 1..32 (errors: n_tok outside 1..32 or a position >= Lk TMIX_EINVAL,
+ * Lk > 240 TMIX_ESHAPE).  A call with Lk <= 80 and n_tok <= 8 is forwarded to tmix_xattn_token_maps: the same launch, the same bits. */
+int tmix_xattn_token_maps_long(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK, float* maps,
+                               int B, int H, int Sq, int Lk, int row0, int row_step, int n_rows, const int32_t* tokens, int n_tok,
+                               int accumulate, float scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,8 @@ SIGNATURES = {
     "tmix_i2v_temporal_encoder": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int64] + [vp] * 11 + [vp]),
     "tmix_xattn_token_maps": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_int32), C.c_int, C.c_int, f32, vp]),
+    "tmix_xattn_token_maps_long": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_int32), C.c_int, C.c_int, f32, vp]),
 }
 
 _lib = None

@@ -481,10 +481,19 @@ def token_array(tokens):
     return (C.c_int32 * max(1, len(tokens)))(*tokens)
 
 
-def xattn_token_maps(q, k, tokens, H, Lk=None, rows=(0, 1, None), scale=None, out=None, accumulate=False):
+XATTN_MAPS_SHORT = (80, 8)        # (keys, positions) of tmix_xattn_token_maps; beyond either: tmix_xattn_token_maps_long (240, 32)
+
+
+def xattn_maps_long(Lk, n_tok):
+    """does a token-map launch over Lk keys and n_tok positions need tmix_xattn_token_maps_long?"""
+    return Lk > XATTN_MAPS_SHORT[0] or n_tok > XATTN_MAPS_SHORT[1]
+
+
+def xattn_token_maps(q, k, tokens, H, Lk=None, rows=(0, 1, None), scale=None, out=None, accumulate=False, long=None):
     """maps [n_rows, n_tok, Sq] fp32: softmax(q k^T * scale) of every head at the key positions `tokens` (<= 8), summed over the
     H heads, for batch rows row0 + i * row_step (rows = (row0, row_step, n_rows); n_rows None: every row from row0 on).
-    q [B,Sq,>=H*64] bf16 (row stride free), k [B,>=Lk,>=H*64] bf16.  accumulate adds to `out` instead of overwriting it."""
+    q [B,Sq,>=H*64] bf16 (row stride free), k [B,>=Lk,>=H*64] bf16.  accumulate adds to `out` instead of overwriting it.
+    long: call tmix_xattn_token_maps_long (Lk <= 240, <= 32 positions); None = only where the short entry point cannot serve."""
     _need_cuda(q, k)
     assert q.dtype == BF16 and k.dtype == BF16 and q.stride(2) == 1 and k.stride(2) == 1
     B, Sq = q.shape[0], q.shape[1]
@@ -495,9 +504,11 @@ def xattn_token_maps(q, k, tokens, H, Lk=None, rows=(0, 1, None), scale=None, ou
         out = torch.zeros(n, len(tokens), Sq, device=q.device, dtype=torch.float32)
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, len(tokens), Sq)
     scale = 64 ** -0.5 if scale is None else scale
-    L.check(L.load().tmix_xattn_token_maps(_p(q), q.stride(1), q.stride(0), _p(k), k.stride(1), k.stride(0), _p(out), B, H, Sq, Lk,
-                                           row0, step, n, token_array(tokens), len(tokens), int(bool(accumulate)), float(scale),
-                                           _stream()), "tmix_xattn_token_maps")
+    long = xattn_maps_long(Lk, len(tokens)) if long is None else long
+    fn = L.load().tmix_xattn_token_maps_long if long else L.load().tmix_xattn_token_maps
+    L.check(fn(_p(q), q.stride(1), q.stride(0), _p(k), k.stride(1), k.stride(0), _p(out), B, H, Sq, Lk,
+               row0, step, n, token_array(tokens), len(tokens), int(bool(accumulate)), float(scale),
+               _stream()), fn.__name__)
     return out
 
 

@@ -69,7 +69,7 @@ class Tweediemix:
                       run_expand.py + preprocess_mask at fusion_sampling.py:453-469)
     lora              True selects the fusion_sampling_lora.py window semantics (needs config.t_stop)
     strict_reference  keep the hooks' hard-coded `batch == 4` routing test (utils_custom.py:62)
-    attention_masks   None (masks come from mask_provider) or dict(tokens=[[positions of concept 1], ...], threshold=0.5,
+    attention_masks   None (masks come from mask_provider) or dict(tokens=[[positions of concept 1], ...] (<= 32 in all), threshold=0.5,
                       levels=None, level_weights=None): the masks come from the cross-attention maps of the look-ahead's calls
                       on the scene prompt (a "probe" plan: the "plain" rows plus tmix_xattn_token_maps launches) through
                       masks.attention_masks; mask_provider is not called.  Needs jumping_steps >= 1.
@@ -102,7 +102,7 @@ class Tweediemix:
         self.text_embeds_single = text_embeds_single
         self.mask_provider = mask_provider
         # in-process masks from the look-ahead's cross-attention (masks.attention_masks): the token positions of every foreground
-        # concept, flattened into the <= 8 positions one probe plan records
+        # concept, flattened into the <= 32 positions one probe plan records
         self.attention_masks = None
         self.attention_maps = None         # after the look-ahead: per seed {level: [n_tok, h_l, w_l]} (raw sums), when attention_masks is set
         self.mask_images = None            # ... and per seed the K-1 uint8 [H, W] masks they gave
@@ -112,8 +112,8 @@ class Tweediemix:
             if len(toks) != self.concept_num - 1 or any(not c for c in toks):
                 raise ValueError(f"attention_masks: {len(toks)} token lists for {self.concept_num - 1} foreground concepts")
             flat = [p for c in toks for p in c]
-            if len(flat) > 8:
-                raise ValueError(f"attention_masks: {len(flat)} token positions, at most 8 in all")
+            if len(flat) > 32:     # tmix_xattn_token_maps_long's limit (more than 8 positions make the probe plan record it)
+                raise ValueError(f"attention_masks: {len(flat)} token positions, at most 32 in all")
             if int(config.jumping_steps) < 1:
                 raise ValueError("attention_masks needs the look-ahead (jumping_steps >= 1): its calls are where the maps come from")
             self.attention_masks = dict(tokens=toks, flat=flat, threshold=float(am.get("threshold", 0.5)),

@@ -232,17 +232,35 @@ class ClipBPETokenizer:
         self.cache[token] = word
         return word
 
-    def _tokenize_plain(self, text: str):
+    def _words_plain(self, text: str):
+        """[(word, its BPE tokens)] of a piece of text without added tokens: the words are the pre-tokenisation pattern's matches"""
         import unicodedata
         import regex
         text = regex.sub(r"\s+", " ", unicodedata.normalize("NFC", text)).strip().lower()
         out = []
         for tok in self.pat.findall(text):
             if tok in (self.bos_token, self.eos_token):
-                out.append(tok)
+                out.append((tok, [tok]))
                 continue
             mapped = "".join(self.byte_map[b] for b in tok.encode("utf-8"))
-            out.extend(self._bpe(mapped))
+            out.append((tok, list(self._bpe(mapped))))
+        return out
+
+    def _tokenize_plain(self, text: str):
+        return [t for _w, ts in self._words_plain(text) for t in ts]
+
+    def words(self, text: str):
+        """[(word, its tokens)] in the order and with the tokens `tokenize` gives (an added or special token is a word of its own):
+        the units the chunked prompts are cut at (chunk_prompt).  Joined by blanks, the words tokenise to the same tokens."""
+        import regex
+        cut = set(self.added) | {self.bos_token, self.eos_token, self.pad_token}
+        alts = "|".join(regex.escape(t) for t in sorted(cut, key=len, reverse=True))
+        out = []
+        for piece in regex.split(f"({alts})", text):
+            if piece in cut:
+                out.append((piece, [piece]))
+            elif piece:
+                out.extend(self._words_plain(piece))
         return out
 
     def tokenize(self, text: str):
@@ -311,6 +329,99 @@ def phrase_token_positions(tokenizer, prompt: str, phrase: str):
     raise ValueError(f"phrase {phrase!r} does not occur in the prompt {prompt!r} (as tokens)")
 
 
+# -------------------------------------------------------------------------------------------- long prompts (additive: --long_prompts)
+CHUNK_TOKENS = 75        # tokens of a chunk between its <bos> and <eos>
+CHUNK_LEN = 77           # keys a chunk adds to the cross-attention
+MAX_CHUNKS = 3           # 231 keys: tmix_xattn_token_maps_long and the V^T rows (padded to 232) stay below 240
+
+
+def _tokenizer_list(tokenizers):
+    return list(tokenizers) if isinstance(tokenizers, (list, tuple)) else [tokenizers]
+
+
+def chunk_prompt(tokenizers, prompt: str, max_chunks: int = MAX_CHUNKS):
+    """The chunk texts of `prompt` (at least one): the words of the tokenizer's pre-tokenisation (ClipBPETokenizer.words) fill a chunk
+    while it holds at most 75 tokens, and a word's tokens are never split.  With several tokenizers (the two SDXL ones count a literal
+    '!' differently) a chunk holds at most 75 tokens of EACH, so both towers cut at the same words.  A prompt that fits comes back as
+    one chunk that tokenises to the prompt's own ids.  ValueError: one word of more than 75 tokens, more than `max_chunks` chunks."""
+    toks = _tokenizer_list(tokenizers)
+    words = toks[0].words(prompt)
+    chunks, fill, total = [[]], [0] * len(toks), 0
+    for w, ts in words:
+        n = [len(ts)] + [len(t.tokenize(w)) for t in toks[1:]]
+        total += n[0]
+        if max(n) > CHUNK_TOKENS:
+            raise ValueError(f"long prompt: the single word {w[:40]!r} is {max(n)} tokens, a chunk holds {CHUNK_TOKENS}")
+        if any(f + k > CHUNK_TOKENS for f, k in zip(fill, n)):
+            chunks.append([])
+            fill = [0] * len(toks)
+        chunks[-1].append(w)
+        fill = [f + k for f, k in zip(fill, n)]
+    if len(chunks) > max_chunks:
+        raise ValueError(f"long prompt {prompt[:60]!r}...: {total} tokens need {len(chunks)} chunks of {CHUNK_TOKENS}; the limit is "
+                         f"{max_chunks} chunks ({max_chunks * CHUNK_TOKENS} tokens)")
+    return [" ".join(c) for c in chunks]
+
+
+def run_chunks(tokenizers, prompts, max_chunks: int = MAX_CHUNKS) -> int:
+    """the chunk count of a run: the maximum over every prompt row it encodes (negative prompt, scene prompt, per-concept prompts)"""
+    return max([1] + [len(chunk_prompt(tokenizers, p, max_chunks)) for p in prompts])
+
+
+def long_ids(tokenizers, prompts, chunks: int | None = None):
+    """(ids per tokenizer [P, c, 77], c): every chunk text through the tokenizer's own __call__ (<bos> tokens <eos> pad), shorter
+    prompts filled up with empty chunks (<bos> <eos> pad...) to c = max(chunks, the longest row's count)"""
+    toks = _tokenizer_list(tokenizers)
+    if isinstance(prompts, str):
+        prompts = [prompts]
+    rows = [chunk_prompt(toks, p) for p in prompts]
+    c = max([chunks or 1] + [len(r) for r in rows])
+    if c > MAX_CHUNKS:
+        raise ValueError(f"long prompts: {c} chunks asked for, the limit is {MAX_CHUNKS} ({MAX_CHUNKS * CHUNK_TOKENS} tokens)")
+    flat = [t for r in rows for t in r + [""] * (c - len(r))]
+    ids = [t(flat, max_length=CHUNK_LEN).view(len(prompts), c, CHUNK_LEN) for t in toks]
+    n0 = [len(toks[0].tokenize(t)) for t in flat]
+    assert max(n0) <= CHUNK_TOKENS, "a chunk text tokenised to more than its words did"      # (words() and tokenize() agree by construction)
+    return ids, c
+
+
+def encode_prompts(encoders, tokenizers, prompts, long: bool = False, chunks: int | None = None):
+    """(prompt_embeds [P, 77 c, sum d] bf16, pooled [P, 1280] fp32).  long=False: encode_prompt of the tokenizers' 77 ids (c = 1, the
+    tail of a longer prompt dropped, as the reference does).  long=True: the prompt in chunks of 75 tokens (chunk_prompt), every chunk
+    one more batch row of the towers (positions 0..76 each), the hidden states concatenated chunk-major along the sequence, the
+    pooled row that of chunk 0.  `chunks`: the run's chunk count when other rows of the run need more than these."""
+    if isinstance(prompts, str):
+        prompts = [prompts]
+    if not long:
+        return encode_prompt(encoders, [t(prompts) for t in tokenizers])
+    ids, c = long_ids(tokenizers, prompts, chunks)
+    P = len(prompts)
+    emb, pooled = encode_prompt(encoders, [i.view(P * c, CHUNK_LEN) for i in ids])
+    return emb.reshape(P, c * CHUNK_LEN, emb.shape[-1]), pooled.view(P, c, -1)[:, 0].contiguous()
+
+
+def token_positions_long(tokenizers, prompt: str, phrase: str):
+    """phrase_token_positions for a chunked prompt: positions in the concatenated sequence, 77 * chunk + offset (every chunk has its
+    own <bos> at offset 0).  The phrase is looked for in the prompt's tokens across the chunk cuts, so it may straddle two chunks and
+    its positions then do too.  `tokenizers`: one tokenizer, or the list the run encodes with (the cuts depend on all of them)."""
+    toks = _tokenizer_list(tokenizers)
+    t0 = toks[0]
+    ptoks, ppos = [], []
+    for ci, text in enumerate(chunk_prompt(toks, prompt)):
+        ids = [t0.convert_tokens_to_ids(t) for t in t0.tokenize(text)]
+        ptoks += ids
+        ppos += [CHUNK_LEN * ci + 1 + o for o in range(len(ids))]
+    words = t0.tokenize(phrase)
+    ftoks = [t0.convert_tokens_to_ids(t) for t in words]
+    n = len(ftoks)
+    for i in range(len(ptoks) - n + 1 if n else 0):
+        if ptoks[i:i + n] == ftoks:
+            pos = ppos[i:i + n]
+            keep = [p for p, w in zip(pos, words) if w.replace("</w>", "") not in STOP_WORDS]
+            return keep or pos
+    raise ValueError(f"phrase {phrase!r} does not occur in the prompt {prompt!r} (as tokens)")
+
+
 def inject_modifier_tokens(tokenizers, encoders, sts, modifier_token_user):
     """fusion_sampling.py:158-189: every user modifier token is appended to both vocabularies, both embedding tables
     grow, and row id_i receives checkpoint i's learned embedding (keys 'modifier_token' / 'modifier_token_2').
@@ -337,10 +448,13 @@ def inject_modifier_tokens(tokenizers, encoders, sts, modifier_token_user):
     return ids, ids_2
 
 
-def get_text_embeds(encoders, tokenizers, prompt, negative_prompt):
-    """fusion_sampling.py:268-285: rows = [negative prompt(s), prompts...] -> (embeds [1+P,77,2048], pooled [1+P,1280])."""
-    pe, pp = encode_prompt(encoders, [t(prompt) for t in tokenizers])
-    ue, up = encode_prompt(encoders, [t(negative_prompt) for t in tokenizers])
+def get_text_embeds(encoders, tokenizers, prompt, negative_prompt, long: bool = False, chunks: int | None = None):
+    """fusion_sampling.py:268-285: rows = [negative prompt(s), prompts...] -> (embeds [1+P,77,2048], pooled [1+P,1280]);
+    long: chunked prompts (encode_prompts), 77 * chunks keys in every row."""
+    if long:
+        chunks = max(chunks or 1, run_chunks(tokenizers, list(prompt) + list(negative_prompt)))
+    pe, pp = encode_prompts(encoders, tokenizers, prompt, long, chunks)
+    ue, up = encode_prompts(encoders, tokenizers, negative_prompt, long, chunks)
     return torch.cat([ue, pe]), torch.cat([up, pp])
 
 
@@ -377,8 +491,12 @@ class TextPath:
         prompts, prompts_single, K = assemble_prompts(opt.prompt, opt.prompt_orig, opt.concepts, opt.modifier_token)
         inject_modifier_tokens(self.tokenizers, self.encoders, sts, opt.modifier_token.split('+'))
         null = [opt.negative_prompt]
-        return (get_text_embeds(self.encoders, self.tokenizers, prompts, null),
-                get_text_embeds(self.encoders, self.tokenizers, prompts_single, null), K)
+        long = bool(getattr(opt, "long_prompts", False))
+        c = None
+        if long:                                     # one chunk count for the run: both embedding sets share the UNet's key count
+            c = run_chunks(self.tokenizers, prompts + prompts_single + null)
+        return (get_text_embeds(self.encoders, self.tokenizers, prompts, null, long, c),
+                get_text_embeds(self.encoders, self.tokenizers, prompts_single, null, long, c), K)
 
 
 # ============================================================================================ vision tower

@@ -403,7 +403,8 @@ def hint_bytes(nbytes, cap, over):
 @dataclass
 class TokenMapSpec:
     """What a probe plan records (UNetPlan(token_maps=...)): for batch rows row0 + i * row_step, i < n_rows, the attn2 probability of
-    every query pixel on the key positions `tokens` (<= 8 of the 77), summed over heads (tmix_xattn_token_maps), accumulated over every
+    every query pixel on the key positions `tokens` (<= 8 of the 77: tmix_xattn_token_maps; up to 32 of up to 240 keys, the chunked prompts:
+    tmix_xattn_token_maps_long), summed over heads, accumulated over every
     attn2 of a level and over every call until the caller zeroes the maps.  levels: block indices (0 = the latent's resolution, level
     l = latent / 2^l) to probe; None = every level that has attention."""
     tokens: tuple
@@ -429,6 +430,7 @@ class UNetPlan:
     token_spec = None
     token_maps = None
     _tok_arr = None
+    _tok_fn = None
 
     def __init__(self, W: UNetWeights, B: int, h: int, w: int, kv: KVCache, pooled: torch.Tensor,
                  time_ids: torch.Tensor, routed: bool = False, autotune: bool = True, row_sets=None,
@@ -491,7 +493,9 @@ class UNetPlan:
         self.token_maps = {}
         if token_maps is not None:
             tok = tuple(int(t) for t in token_maps.tokens)
-            assert 1 <= len(tok) <= 8 and all(0 <= t < kv.Lk for t in tok), tok
+            assert 1 <= len(tok) <= 32 and all(0 <= t < kv.Lk for t in tok) and kv.Lk <= 240, tok
+            # past 80 keys or 8 positions: the long entry point; every other probe plan records the launch it always did
+            self._tok_fn = self.lib.tmix_xattn_token_maps_long if ops.xattn_maps_long(kv.Lk, len(tok)) else self.lib.tmix_xattn_token_maps
             lv = attention_levels(self.cfg) if token_maps.levels is None else tuple(token_maps.levels)
             assert lv and all(l in attention_levels(self.cfg) for l in lv), lv
             self._tok_arr = ops.token_array(tok)
@@ -872,10 +876,10 @@ class UNetPlan:
         return lvl if lvl in self.token_maps else None
 
     def _token_maps(self, q, a2, H, S, lvl):
-        """one tmix_xattn_token_maps launch on the attn2 q of this site, accumulating into the level's maps"""
+        """one tmix_xattn_token_maps (or _long) launch on the attn2 q of this site, accumulating into the level's maps"""
         sp, k, m = self.token_spec, self.kv.k[a2], self.token_maps[lvl]
         assert m.shape[2] == S
-        self._emit(self.lib.tmix_xattn_token_maps, q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
+        self._emit(self._tok_fn, q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
                    m.data_ptr(), self.B, H, S, self.kv.Lk, sp.row0, sp.row_step, sp.n_rows, self._tok_arr, m.shape[1], 1,
                    self.cfg.head_dim ** -0.5)
 
