@@ -35,6 +35,11 @@ the loop through the HF hub (checkpoint download) takes local paths here:
   --keep_image FILE      the same with an RGB image of exactly resolution_w x resolution_h: kept is the VAE encoder's mean times the scaling
                          factor (nothing is drawn).  Excludes --keep_latents
   --reroll LIST          the regions sampled anew: '+'-separated --seg_concepts phrases or 0-based indices into them ('a dog', '1', '0+a dog')
+  --canvas_h / --canvas_w  a WIDE CANVAS in pixels (0: the window, i.e. none): the picture is sampled as overlapping windows of
+                         resolution_h x resolution_w that share every UNet launch like co-batched seeds and are reconciled after every
+                         step; --window_overlap is their minimum overlap in pixels (default: half the smaller window side).  At most 8
+                         windows; masks (--mask_paths, --random_masks, the synthetic rectangles) are built on the canvas grid, the
+                         '.latent.pt' and '.png' are canvas-sized.  Not with --keep_*, --mask_source attention or --streams 2
   --num_seeds N          N trajectories, seeds seed..seed+N-1 (trajectory i is exactly what `--seed seed+i` alone produces: its
                          x_T comes from its own generator), co-batched --seeds_per_batch at a time
   --gpus G               shard those seeds round-robin over G GPUs of this node: the script starts one process per GPU itself
@@ -105,6 +110,9 @@ def build_parser():
     p.add_argument('--keep_latents', type=str, default='', help="'.latent.pt' of an earlier run: kept outside the --reroll regions")
     p.add_argument('--keep_image', type=str, default='', help='RGB image of resolution_w x resolution_h: its VAE encoding is kept outside the --reroll regions')
     p.add_argument('--reroll', type=str, default='', help="regions sampled anew: '+'-separated --seg_concepts phrases or 0-based indices into them")
+    p.add_argument('--canvas_h', type=int, default=0, help='canvas height in pixels (0: resolution_h, no canvas)')
+    p.add_argument('--canvas_w', type=int, default=0, help='canvas width in pixels (0: resolution_w, no canvas)')
+    p.add_argument('--window_overlap', type=int, default=-1, help='minimum overlap of neighbouring windows in pixels (default: half the smaller window side)')
     p.add_argument('--num_seeds', type=int, default=1, help='trajectories to sample: seeds seed..seed+n-1')
     p.add_argument('--seeds_per_batch', type=int, default=0, help='seeds co-batched into every UNet launch (0: all of this rank\'s seeds, at most 4)')
     p.add_argument('--gpus', type=int, default=1, help='shard the seeds over this many GPUs (one process per GPU, started by this script)')
@@ -258,6 +266,47 @@ def check_keep_args(opt):
     return keep
 
 
+def check_canvas_args(opt):
+    """None for a run without a canvas (no flags, or a canvas of the window's size), else dict(height, width, overlap, n_win) in pixels; refuses
+    what a canvas run cannot do (before anything touches the GPU)."""
+    if not (opt.canvas_h or opt.canvas_w):
+        if opt.window_overlap >= 0:
+            raise SystemExit('--window_overlap is the overlap of the windows of a canvas: it needs --canvas_h or --canvas_w')
+        return None
+    from tweediemix_amd import canvas as CV
+    rh, rw = opt.resolution_h, opt.resolution_w
+    H, Wd = opt.canvas_h or rh, opt.canvas_w or rw
+    if H % 8 or Wd % 8:
+        raise SystemExit(f'--canvas_h {H} / --canvas_w {Wd}: canvas sizes are multiples of 8 pixels (the latent grid)')
+    if H < rh or Wd < rw:
+        raise SystemExit(f'--canvas_h {H} / --canvas_w {Wd}: the canvas is smaller than the window resolution_w x resolution_h = {rw} x {rh}')
+    ov = opt.window_overlap if opt.window_overlap >= 0 else (min(rh, rw) // 2) // 8 * 8
+    if ov % 8 or not 0 <= ov < min(rh, rw):
+        raise SystemExit(f'--window_overlap {ov}: a multiple of 8 pixels below the window size {min(rh, rw)}')
+    n_win = len(CV.window_layout(H // 8, Wd // 8, rh // 8, rw // 8, ov // 8))
+    if n_win > 8:
+        raise SystemExit(f'--canvas_h {H} / --canvas_w {Wd} with --window_overlap {ov}: {n_win} windows of {rw} x {rh}, at most 8 share a UNet launch')
+    if n_win == 1:
+        return None
+    if opt.keep_latents or opt.keep_image or opt.reroll:
+        raise SystemExit('--keep_latents / --keep_image / --reroll do not combine with a canvas: reconciling the windows would change the kept bits')
+    if opt.mask_source == 'attention' and not (opt.mask_paths or opt.random_masks):
+        raise SystemExit('--mask_source attention does not combine with a canvas: the token maps come per window and are not stitched')
+    if opt.streams != 1:
+        raise SystemExit(f'--streams {opt.streams}: a canvas runs on one launch chain (--streams 1)')
+    if opt.seeds_per_batch and opt.seeds_per_batch * n_win > 8:
+        raise SystemExit(f'--seeds_per_batch {opt.seeds_per_batch} x {n_win} windows = {opt.seeds_per_batch * n_win} co-batched row sets, at most 8')
+    return dict(height=H, width=Wd, overlap=ov, n_win=n_win)
+
+
+def default_seeds_per_batch(n_seeds, n_win=1):
+    """seeds co-batched into every UNet launch when --seeds_per_batch is not given: all of this rank's seeds, at most 4; on a canvas of
+    n_win windows as many as keep seeds x windows within the 8 co-batched row sets"""
+    if n_win == 1:
+        return min(max(n_seeds, 1), 4)
+    return max(1, min(n_seeds, 8 // n_win))
+
+
 def encode_keep_image(image, vae, scaling_factor, device, synthetic=False):
     """the kept latent of --keep_image: the VAE encoder's MEAN times the factor decode_final divides by (deterministic: no sample is drawn)"""
     from tweediemix_amd import vae as V, video as VI
@@ -318,6 +367,7 @@ def main(argv=None):
     check_long_prompt_args(opt)
     if opt.dtype == 'fp8' and opt.lora_mode == 'lowrank':
         raise SystemExit('--dtype fp8 quantises the merged per-concept projection weights: use --lora_mode merged')
+    canvas = check_canvas_args(opt)
     keep = check_keep_args(opt)
     from tweediemix_amd import dist as D, launch as LA, masks as M, sampler as S, unet as U, weights as Wt
     if opt.gpus > 1 and not LA.launched():
@@ -369,7 +419,8 @@ def main(argv=None):
     if opt.long_prompts:
         n_keys = check_long_embeds(opt, te, ts)
     W = U.UNetWeights(cfg, sd, opt.device, (kind, con), lora_mode=opt.lora_mode)
-    h, w = opt.resolution_h // 8, opt.resolution_w // 8
+    out_h, out_w = (canvas['height'], canvas['width']) if canvas else (opt.resolution_h, opt.resolution_w)      # what the files hold
+    h, w = out_h // 8, out_w // 8                        # the grid of x_T, the masks and the results: the canvas's, where there is one
     sidecar = False
     attn = None
     if opt.mask_paths:
@@ -406,7 +457,7 @@ def main(argv=None):
         from tweediemix_amd import vae as V
         vae = (V.TINY, V.synthetic_state_dict(V.TINY))
     seeds = D.seed_shard([opt.seed + i for i in range(opt.num_seeds)], rank, world)
-    per = opt.seeds_per_batch or min(max(len(seeds), 1), 4)
+    per = opt.seeds_per_batch or default_seeds_per_batch(len(seeds), canvas['n_win'] if canvas else 1)
     strict = not opt.no_strict_reference
     if strict and K + 1 != 4 and kind in ('custom', 'lora'):
         say(f"note: {K} concepts -> UNet batch {K + 1}: the reference's attention hooks only route concept weights when the batch is 4 "
@@ -419,11 +470,12 @@ def main(argv=None):
             return M.build_masks(fg, h, w, opt.device)
         sd_ = current["ids"][current["turn"] % len(current["ids"])]
         current["turn"] += 1
-        return M.build_masks(M.random_rectangle_masks(K, opt.resolution_h, opt.resolution_w, seed=sd_), h, w, opt.device)
+        return M.build_masks(M.random_rectangle_masks(K, out_h, out_w, seed=sd_), h, w, opt.device)
 
     tw = S.Tweediemix(opt, W, te, ts, provider, concept_num=K, lora=LORA,
                       strict_reference=strict, use_graphs=not opt.no_graphs, n_seeds=per, n_streams=opt.streams, vae=vae,
-                      fp8=(opt.dtype == 'fp8'), attention_masks=attn)
+                      fp8=(opt.dtype == 'fp8'), attention_masks=attn,
+                      **(dict(canvas={k: canvas[k] for k in ('height', 'width', 'overlap')}) if canvas else {}))
     if vae_scaling:                                       # fusion_sampling.py:518 divides by vae.config.scaling_factor
         tw.vae_scaling_factor = float(vae_scaling)
     if sidecar and vae is not None:
@@ -456,7 +508,7 @@ def main(argv=None):
         import torch.distributed as dist
         lat = D.gather_latents(lat.contiguous(), opt.num_seeds, rank, world)
         if vae is not None:
-            img = D.gather_latents(img.contiguous() if img is not None else torch.zeros(0, 3, opt.resolution_h, opt.resolution_w, device=dev),
+            img = D.gather_latents(img.contiguous() if img is not None else torch.zeros(0, 3, out_h, out_w, device=dev),
                                    opt.num_seeds, rank, world)
     if rank == 0:
         os.makedirs(opt.output_path_all, exist_ok=True)

@@ -102,6 +102,23 @@ int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps, int eps_dt
  * argument of the UNet call :340): latent[(s*rows + r)][n] = x[s][n] for every row r, t_dev[s*rows + r] = params[0]. */
 int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,
                        int64_t n, void* stream);
+/* WIDE CANVASES (no reference counterpart: the reference samples one image of the trained size).  A canvas larger than the trained
+ * window is sampled as n_win overlapping windows that share every UNet launch like co-batched seeds; after every step the windows are
+ * reconciled: each canvas pixel that several windows cover becomes, in all of them, the weighted mean of their values.
+ *   x        [groups][n_win][C][h][w] fp32, dense, updated in place (groups = co-batched seeds; window-major inside a group)
+ *   win_yx   HOST array of 2*n_win ints {oy_0, ox_0, oy_1, ...}: the windows' top-left corners on the canvas.  Read at call time and
+ *            passed in the kernel arguments, so a captured launch carries them by value (n_win <= TMIX_MAX_WINDOWS)
+ *   weight   [h*w] fp32 device array, one weight per WINDOW pixel, or NULL = all ones
+ * For every group, channel and canvas pixel, over the windows i that cover it in ascending i, with v_i the window's element and wt_i its weight:
+ *   acc = acc + wt_i * v_i     ws = ws + wt_i     (from 0.0f; separate products and sums, not contracted)     r = acc / ws
+ * and r is written to that element of every covering window.  A pixel that ONE window covers is not written: its bits stay (NaN payloads
+ * included).  One thread owns one canvas pixel and a window element belongs to exactly one canvas pixel: no atomics, results independent
+ * of the grid.  No alignment requirement on h or w.  n_win == 1 succeeds and launches nothing.
+ * TMIX_EINVAL: null x / win_yx, n_win outside 1..TMIX_MAX_WINDOWS, groups < 1.  TMIX_ESHAPE: a non-positive size, a window that reaches
+ * outside the canvas, a canvas pixel that no window covers.  All checked on the host before any launch. */
+#define TMIX_MAX_WINDOWS 8
+int tmix_window_consensus(float* x, int groups, int n_win, const int* win_yx, int C, int h, int w, int canvas_h, int canvas_w,
+                          const float* weight, void* stream);
 
 /* Video sampler (I2VGen-XL loop, BASELINE config #5; replaces video_gen/pipeline_i2vgen_xl.py:699-719):
  *   x [n], v [2n] (uncond rows first), out [n], all of `dtype` (TMIX_F32 / TMIX_F16 / TMIX_BF16); sa = sqrt(alpha(t)) etc. with

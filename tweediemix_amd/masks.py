@@ -259,4 +259,4 @@ class SidecarMaskProvider:
         subprocess.call(cmd, shell=True, env=sidecar_child_env())                # (os.system with a cleaned environment; return code ignored, like the reference)
         paths = [os.path.join(self.output_path, sp + ".jpg") for sp in self.seg_concepts.split("+")]
         s = self.sampler
-        return build_masks(paths, s.h, s.w, s.device)
+        return build_masks(paths, s.canvas_h, s.canvas_w, s.device)      # (the window's grid unless the sampler has a canvas)

@@ -91,6 +91,22 @@ def fused_tweedie_step_keep_dev(x, eps, masks, mode, K, params, keep_x0, keep_ep
     return out_x
 
 
+def window_consensus(x, groups, offsets, canvas_hw, weight=None):
+    """tmix_window_consensus, in place on x [groups * n_win, C, h, w] fp32 (group-major: b = group * n_win + window): every canvas pixel
+    that several windows cover becomes their weighted mean in all of them.  offsets [(oy, ox), ...] the windows' corners on the canvas
+    of canvas_hw = (canvas_h, canvas_w); weight [h, w] fp32 per window pixel, or None = all ones.  Returns x."""
+    _need_cuda(x, weight)
+    n_win = len(offsets)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[0] == groups * n_win, (tuple(x.shape), groups, n_win)
+    Cc, h, w = x.shape[1:]
+    if weight is not None:
+        assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() == h * w, tuple(weight.shape)
+    yx = (C.c_int32 * (2 * n_win))(*[int(v) for o in offsets for v in o])
+    L.check(L.load().tmix_window_consensus(_p(x), int(groups), n_win, yx, Cc, h, w, int(canvas_hw[0]), int(canvas_hw[1]), _p(weight),
+                                           _stream()), "tmix_window_consensus")
+    return x
+
+
 def stats_parts(N, tile_cfg):
     """number of row-statistics partials a GEMM of width N writes with tiling tile_cfg (tmix_gemm_stats_parts)."""
     n = L.load().tmix_gemm_stats_parts(int(N), int(tile_cfg))

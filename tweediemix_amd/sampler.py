@@ -73,11 +73,18 @@ class Tweediemix:
                       levels=None, level_weights=None): the masks come from the cross-attention maps of the look-ahead's calls
                       on the scene prompt (a "probe" plan: the "plain" rows plus tmix_xattn_token_maps launches) through
                       masks.attention_masks; mask_provider is not called.  Needs jumping_steps >= 1.
+    canvas            None, or dict(height, width, overlap) in pixels (multiples of 8): a WIDE CANVAS sampled as overlapping windows of
+                      resolution_h x resolution_w (canvas.window_layout) that share every UNet launch like co-batched seeds and are
+                      reconciled after every step (tmix_window_consensus behind the fused step, inside the captured graph).  run_fusion /
+                      sample_loop / denoise_step then take and return canvas latents [n_seeds, 4, height / 8, width / 8], mask_provider
+                      gets the assembled preview [1, 4, height / 8, width / 8] and returns [K, 1, height / 8, width / 8], decode_final /
+                      decode_latent return [n, 3, height, width].  n_seeds * windows <= 8; not with attention_masks, set_keep or
+                      n_streams > 1.  A canvas of the window's size is one window: today's launches and bits.
     """
 
     def __init__(self, config, weights: UNetWeights, text_embeds, text_embeds_single, mask_provider,
                  concept_num: int, lora: bool = False, strict_reference: bool = True, use_graphs: bool = False,
-                 n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None):
+                 n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None):
         self.config = config
         self.fp8 = bool(fp8)          # optional: FF / QKV projections on e4m3 operands (tmix_gemm_fp8); default bf16 like the reference's fp16
         self.W = weights
@@ -89,6 +96,8 @@ class Tweediemix:
         # n_seeds independent trajectories share every UNet launch (rows [seed][uncond, concepts...]); the
         # reference runs one seed per process -- co-batching only raises the GEMM M dimension.
         self.n_seeds = int(n_seeds)
+        self.n_canvas = self.n_seeds       # trajectories the caller sees (with a canvas, n_seeds below counts their windows)
+        self.windows = None                # canvas: [(oy, ox), ...] of the windows on the latent canvas grid, row-major
         # n_streams > 1 splits the rows of every UNet call into that many independent launch chains (PlanGroup)
         self.n_streams = int(n_streams)
         # optional VAE decoder: (config, state_dict) of tweediemix_amd.vae -- enables decode_latent / decoded outputs
@@ -123,6 +132,9 @@ class Tweediemix:
         self.skip = self.scheduler.skip
         self.final_alpha_cumprod = self.scheduler.final_alpha_cumprod
         self.h, self.w = config.resolution_h // 8, config.resolution_w // 8
+        self.canvas_h, self.canvas_w = self.h, self.w
+        if canvas is not None:
+            self._init_canvas(dict(canvas), attention_masks)
         # compute_time_ids, fusion_sampling.py:70-78
         self.add_time_ids = torch.tensor([[config.resolution_h, config.resolution_w, config.crops_coords_top_left_h,
                                            config.crops_coords_top_left_w, config.resolution_h, config.resolution_w]],
@@ -148,6 +160,51 @@ class Tweediemix:
         self._hp_i = 0
         self._mask_buf = None            # fixed-address copy of self.masks that the captured fusion step reads
 
+    # ------------------------------------------------------------------ wide canvas
+    def _init_canvas(self, cv, attention_masks):
+        """the windows of a canvas become co-batched row sets: n_seeds <- n_seeds * windows, group-major (b = seed * windows + window)"""
+        from . import canvas as CV
+        H, Wd, ov = int(cv["height"]), int(cv["width"]), int(cv.get("overlap", 0))
+        rh, rw = self.config.resolution_h, self.config.resolution_w
+        if H % 8 or Wd % 8 or ov % 8:
+            raise ValueError(f"canvas {Wd} x {H}, overlap {ov}: pixel values must be multiples of 8 (the latent grid)")
+        if H < rh or Wd < rw or not 0 <= ov < min(rh, rw):
+            raise ValueError(f"canvas {Wd} x {H}, overlap {ov}: the canvas must hold the {rw} x {rh} window and 0 <= overlap < {min(rh, rw)}")
+        wins = CV.window_layout(H // 8, Wd // 8, self.h, self.w, ov // 8)
+        if len(wins) == 1:                 # the canvas is the window: nothing to reconcile, the sampler is today's
+            return
+        if self.n_seeds * len(wins) > L.MAX_WINDOWS:
+            raise ValueError(f"canvas {Wd} x {H}: {len(wins)} windows x {self.n_seeds} seeds = {self.n_seeds * len(wins)} co-batched row sets, at most {L.MAX_WINDOWS}")
+        if attention_masks is not None:
+            raise ValueError(f"canvas {Wd} x {H}: attention_masks come per window ({len(wins)} windows) and are not stitched; use a mask_provider")
+        if self.n_streams > 1:
+            raise ValueError(f"canvas {Wd} x {H}: n_streams = {self.n_streams}, a canvas runs on one launch chain (n_streams = 1)")
+        self.windows = wins
+        self.canvas_h, self.canvas_w = H // 8, Wd // 8
+        self.n_seeds = self.n_canvas * len(wins)
+        self._pixel_weight = None          # tent weight of the pixel-space blend (decode), built on first use
+
+    def _consensus(self, x):
+        """reconcile the windows of every canvas in x [n_seeds, 4, h, w], in place (on the current stream; capturable); returns x"""
+        return ops.window_consensus(x, self.n_canvas, self.windows, (self.canvas_h, self.canvas_w))
+
+    def _to_windows(self, x):
+        """canvas latents [n_canvas, C, canvas_h, canvas_w] -> [n_seeds, C, h, w]; without a canvas x itself"""
+        if self.windows is None:
+            return x
+        from . import canvas as CV
+        want = (self.n_canvas, self.canvas_h, self.canvas_w)
+        if x.dim() != 4 or (x.shape[0], x.shape[2], x.shape[3]) != want:
+            raise ValueError(f"canvas latent is {tuple(x.shape)}, expected [{want[0]}, C, {want[1]}, {want[2]}]")
+        return CV.crop_windows(x, self.windows, self.h, self.w)
+
+    def _to_canvas(self, x):
+        """reconciled windows [n_seeds, C, h, w] -> canvas latents [n_canvas, C, canvas_h, canvas_w]; without a canvas a copy of x"""
+        if self.windows is None:
+            return x.clone()
+        from . import canvas as CV
+        return CV.assemble(x, self.windows, self.canvas_h, self.canvas_w)
+
     # ------------------------------------------------------------------ keep region
     def set_keep(self, x0, weight, eps):
         """Hold part of the latent while the loop samples the rest (re-roll one concept of a finished image, or sample into a template image).
@@ -155,6 +212,9 @@ class Tweediemix:
         the fixed noise of every seed's kept part.  From the next run_fusion / sample_loop on every step writes
         weight * (sa' x0 + s1' eps) + (1 - weight) * (its own result), with sa' / s1' of the state it writes (tmix_fused_tweedie_step_keep_dev),
         x_T is composited the same way once, and the final latent holds x0 itself.  The tensors are copied: captured steps read these buffers."""
+        if self.windows is not None:     # the mean of equal values is not always that value bit for bit: the kept region's promise would break
+            raise ValueError(f"set_keep: not on a canvas ({len(self.windows)} windows on {self.canvas_w * 8} x {self.canvas_h * 8}): "
+                             f"reconciling the windows would change the kept bits")
         S = self.n_seeds
         want = (("x0", x0, 4), ("weight", weight, 1), ("eps", eps, 4))
         for name, t, c in want:
@@ -272,6 +332,8 @@ class Tweediemix:
                                        self.step_params.data_ptr(), S, rows, n, st), "tmix_step_prologue")
         p.run()
         self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st)
+        if self.windows is not None:
+            self._consensus(self.x_state)
 
     def _fused_step(self, eps_ptr, eps_dt, rows, mode, st):
         """the fused step for every seed, in place on x_state; with a keep region set (set_keep) through the entry that holds it"""
@@ -312,6 +374,8 @@ class Tweediemix:
             eps = self._unet(kind, self.x_state, t).contiguous()
             self._fused_step(eps.data_ptr(), ops._EPS_DT[eps.dtype], eps.shape[0] // self.n_seeds, mode,
                              torch.cuda.current_stream().cuda_stream)
+            if self.windows is not None:
+                self._consensus(self.x_state)
             return
         if not self.use_graphs:
             self._enqueue_step(kind, mode)
@@ -336,7 +400,22 @@ class Tweediemix:
         if self.vae is None:
             raise L.TmixError("no VAE weights were given to Tweediemix(vae=(config, state_dict))")
         from .vae import decode_in_groups
-        return decode_in_groups(self.vae, latent, inv_scale, self._vae_plans, self.device)
+        if self.windows is None:
+            return decode_in_groups(self.vae, latent, inv_scale, self._vae_plans, self.device)
+        # a canvas is decoded window by window through the same plans (the whole canvas would leave the conv kernel's 32-bit offsets and
+        # materialise the mid-block attention's [S, S] scores) and the decoded windows are blended in pixel space: the same kernel,
+        # offsets x 8, a separable tent weight
+        from . import canvas as CV
+        n, ch, cw = latent.shape[0], latent.shape[2], latent.shape[3]
+        if (ch, cw) != (self.canvas_h, self.canvas_w):
+            raise ValueError(f"canvas latent is {tuple(latent.shape)}, expected [n, 4, {self.canvas_h}, {self.canvas_w}]")
+        wins = CV.crop_windows(latent.to(self.device, F32), self.windows, self.h, self.w)
+        img = decode_in_groups(self.vae, wins, inv_scale, self._vae_plans, self.device).clone()
+        if self._pixel_weight is None:
+            self._pixel_weight = CV.tent_weight(8 * self.h, 8 * self.w, self.device)
+        px = [(8 * oy, 8 * ox) for oy, ox in self.windows]
+        ops.window_consensus(img, n, px, (8 * ch, 8 * cw), self._pixel_weight)
+        return CV.assemble(img, px, 8 * ch, 8 * cw)
 
     @torch.no_grad()
     def decode_latent(self, latent):
@@ -414,9 +493,16 @@ class Tweediemix:
                 self._run_step(look, L.STEP_PLAIN, tt, a_t, self.alpha(tt - 150))
                 tt = tt - 150
             self.preview_x0 = (self.x0_state if cfg.jumping_steps else self._x_backup_x0()).clone()
+            if self.windows is not None:              # the step reconciles x_state only: the estimate is reconciled here, where it is read
+                self.preview_x0 = self._to_canvas(self._consensus(self.preview_x0))
             self.x_state.copy_(self._x_backup)
             if self.attention_masks is not None:
                 m = self._masks_from_attention()
+            elif self.windows is not None:            # one canvas mask set per seed, cropped into one set per window (a crop of a partition is a partition)
+                m = torch.stack([self.mask_provider(self.preview_x0[i:i + 1]).to(self.device, F32) for i in range(self.n_canvas)])
+                if tuple(m.shape[1:]) != (self.concept_num, 1, self.canvas_h, self.canvas_w):
+                    raise ValueError(f"canvas masks are {tuple(m.shape[1:])}, expected [{self.concept_num}, 1, {self.canvas_h}, {self.canvas_w}]")
+                m = self._to_windows(m.squeeze(2)).unsqueeze(2)
             elif self.n_seeds == 1:
                 m = self.mask_provider(self.preview_x0).to(self.device, F32).contiguous()
                 assert m.shape[0] == self.concept_num
@@ -450,9 +536,9 @@ class Tweediemix:
     @torch.no_grad()
     def denoise_step(self, x, t):
         """x [n_seeds,4,h,w] fp32 on the device, t python int (or 0-dim tensor). Returns the next latent(s)."""
-        self.x_state.copy_(x)
+        self.x_state.copy_(self._to_windows(x))
         self._denoise_inplace(t)
-        return self.x_state.clone()
+        return self._to_canvas(self.x_state)
 
     def run_fusion(self, x=None, decode=False):
         cfg = self.config
@@ -462,7 +548,7 @@ class Tweediemix:
         else:
             self.init_fusion(t_cond)
         if x is None:      # drawn on the CPU like the reference (fusion_sampling.py:488): device-independent seeds
-            x = torch.randn(self.n_seeds, 4, self.h, self.w)
+            x = torch.randn(self.n_canvas, 4, self.canvas_h, self.canvas_w)
         x = x * self.scheduler.init_noise_sigma          # :488 (1.0 for this scheduler), however x arrived
         return self.sample_loop(x.to(self.device, F32), decode=decode)
 
@@ -470,10 +556,10 @@ class Tweediemix:
     def sample_loop(self, x, decode=False):
         """runs every scheduler timestep; returns the final latent, or the decoded image [n,3,H,W] in [0,1] when
         decode=True and VAE weights were given (fusion_sampling.py:496-528)."""
-        self.x_state.copy_(x)
+        self.x_state.copy_(self._to_windows(x))
         if self._keep is not None:
             self._composite_keep(self.scheduler.timesteps[0])
         for t in self.scheduler.timesteps:
             self._denoise_inplace(t)
-        x = self.x_state.clone()
+        x = self._to_canvas(self.x_state)
         return self.decode_final(x) if decode else x
