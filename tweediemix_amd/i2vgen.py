@@ -19,7 +19,7 @@ import torch
 
 from . import lib as L
 from . import ops
-from .unet import UNetPlan, BF16, F32, refine_group, run_chains, SHARED as U_SHARED
+from .unet import BlockPlan, BF16, F32, refine_group, run_chains, SHARED as U_SHARED
 from .weights import fold_layernorm, interleave_geglu
 
 
@@ -214,7 +214,7 @@ class _Inject:
         return p.lib.tmix_frame_inject(self.ptr, L.BF16, p.clips, p.frames, self.per_frame, int(self.hard), a, b, st)
 
 
-class I2VPlan(UNetPlan):
+class I2VPlan(BlockPlan):
     """pre-recorded forward of the I2VGen-XL UNet for `clips` videos of `frames` latent frames of h x w (CFG: clips = 2).
     __call__(sample [clips,4,F,h,w], t) -> prediction [clips,4,F,h,w] fp32."""
 
@@ -224,31 +224,24 @@ class I2VPlan(UNetPlan):
                  interp: float = 0.7, shared: bool = False):
         cfg = W.cfg
         B = clips * frames                               # spatial layers see every frame as one image
+        t2d, tt = _sites(cfg)
         # weight hints name whole tensors (a clip's launches last 50 - 800 us), at every size: not hint_policy()'s 8 MB heads for small calls
-        self._init_emit_state(W, B, h, w, (int(float(os.environ.get("TMIX_PF_CAP_MB", "0")) * (1 << 20)),
-                                           int(float(os.environ.get("TMIX_PF_CAP_OVER_MB", "20")) * (1 << 20))))
+        hints = (int(float(os.environ.get("TMIX_PF_CAP_MB", "0")) * (1 << 20)), int(float(os.environ.get("TMIX_PF_CAP_OVER_MB", "20")) * (1 << 20)))
+        # every switch of the image UNet stays off: fp8 projections (wired for the image UNet only), LoRA routing (merged or low-rank),
+        # attn2.to_q + cross-attention as one launch, token maps
+        super().__init__(W, B, h, w, hints, _KV(W, context, frames),
+                         gn_channels=max(max(cfg.block_out_channels) * 2, cfg.transformer_in_heads * cfg.head_dim),
+                         ln_floats=max(((inner + 127) // 128) for _p, _c, inner in tt + [(p_, c_, c_) for p_, c_ in t2d]) * B * h * w * 2,
+                         tune_ctx=U_SHARED if shared else "")
         self.clips, self.frames = clips, frames
         self.inject, self.interp = False, interp         # raised per step by the sampling loop (FeatureInjector schedule)
-        self.tune_ctx = U_SHARED if shared else ""
-        # what the image UNet has and this one does not: fp8 projections (wired for the image UNet only), LoRA routing (merged or
-        # low-rank), attn2.to_q + cross-attention as one launch
-        self.fp8 = self.fp8_chain_ff = self.fp8_attn_out = self.fp8_conv = False
-        self.fp8_tile = self.fp8_conv_tile = 0
-        self.row_sets, self.routed, self.lowrank, self._sets_dev = list(range(B)), False, False, None
-        self._qattn = False
         dev = self.dev
-        self.kv = _KV(W, context, frames)
         self.x_in = torch.zeros(B, 2 * cfg.in_channels, h, w, device=dev, dtype=F32)
         self.x_in.view(clips, frames, 2 * cfg.in_channels, h, w)[:, :, cfg.in_channels:] = il_feat.to(dev, F32).permute(0, 2, 1, 3, 4)
         self.latent = self.x_in                          # (UNetPlan interface name)
         self.t_dev = torch.zeros(clips, device=dev, dtype=F32)
         self.eps = torch.zeros(B, cfg.out_channels, h, w, device=dev, dtype=F32)
         self.fps_emb = fps_emb.to(dev, F32).contiguous()
-        cmax = max(max(cfg.block_out_channels) * 2, cfg.transformer_in_heads * cfg.head_dim)
-        self._gn_ws = ops.groupnorm_ws(B, cmax, cfg.norm_groups, dev)
-        t2d, tt = _sites(cfg)
-        need = max(((inner + 127) // 128) for _p, _c, inner in tt + [(p_, c_, c_) for p_, c_ in t2d]) * B * h * w * 2
-        self._ln_buf = torch.zeros(need, device=dev, dtype=F32)
         self._build()
         self._link_ln()
         if autotune:
@@ -280,23 +273,13 @@ class I2VPlan(UNetPlan):
         owner._cs = ((cs, Cc),)
         return cs
 
-    def _gn_b(self, x, Bn, Cc, HW, name, eps, silu):
-        """GroupNorm over whole clips (Bn = clips images of HW = frames x hw rows)"""
-        out = self.arena.get(*x.shape)
-        W = self.W
-        parts = getattr(x, "_cs", None)
-        if parts and len(parts) == 1 and parts[0][1] == Cc and HW % ops.COLSTATS_ROWS == 0 and HW <= self.CLIP_COLSTATS_MAX:
-            self._emit(self.lib.tmix_groupnorm_nhwc_pre, x.data_ptr(), Cc, None, 0, out.data_ptr(), W[name + ".weight"].data_ptr(), W[name + ".bias"].data_ptr(),
-                       self._gn_ws.data_ptr(), Bn, HW, self.cfg.norm_groups, eps, int(silu), parts[0][0].data_ptr(), Cc, None, 0)
-        else:
-            self._emit(self.lib.tmix_groupnorm_nhwc, x.data_ptr(), Cc, None, 0, out.data_ptr(), W[name + ".weight"].data_ptr(),
-                       W[name + ".bias"].data_ptr(), self._gn_ws.data_ptr(), Bn, HW, self.cfg.norm_groups, eps, int(silu))
-        self.op_meta[len(self.ops) - 1] = ("norm", 0, ("norm", Bn, HW, Cc))      # (every instrumented launch needs its entry: the slots are dealt out in issue order)
-        return out
+    def _gn_b(self, x, Cc, HW, name, eps, silu):
+        """GroupNorm over whole clips (clips images of HW = frames x hw rows)"""
+        return self._gn(x, Cc, HW, name, eps, silu, images=self.clips, max_rows=self.CLIP_COLSTATS_MAX)
 
     def _inject_site(self, buf, site, per_frame):
         if site in self.INJECT_SITES:
-            self.ops.append((_Inject(self, buf, per_frame, self.INJECT_SITES[site]), ()))
+            self._emit(_Inject(self, buf, per_frame, self.INJECT_SITES[site]))
             for cs, _c in getattr(buf, "_cs", None) or ():      # the injection rewrites the tensor behind its producer: the partials no longer describe it
                 self.arena.put(cs)
             buf._cs = None
@@ -307,13 +290,9 @@ class I2VPlan(UNetPlan):
         shp = (self.clips, self.frames, HW, Cc)
         d = ops.make_conv_desc(x.view(*shp), self.W[wname + ".weight"], out.view(*shp), self.W[wname + ".bias"], None,
                                None if residual is None else residual, L.CONV_T3, col_stats_out=self._colstats(out, self.B * HW, HW, Cc))
-        self.keep.append(d)
-        self._emit(self.lib.tmix_conv3x3_nhwc, C.byref(d))
-        fl = 2 * self.B * HW * Cc * 3 * Cc
-        self.flops += fl
-        self.launches["conv"].append((d, fl))
-        self._tunable.append((len(self.ops) - 1, "conv", d))
-        self.op_meta[len(self.ops) - 1] = ("conv", fl, d)
+        # weight=None: this convolution has never been hinted, alone among the convolutions, and the recorded launches stay as they are;
+        # whether a hint pays here is a measurement of its own
+        self._launch("tmix_conv3x3_nhwc", (C.byref(d),), 2 * self.B * HW * Cc * 3 * Cc, desc=d, weight=None, tunable="conv")
         return out
 
     def _temp_conv(self, x, Cc, HW, name):
@@ -321,7 +300,7 @@ class I2VPlan(UNetPlan):
         A = self.arena
         v = x
         for k, idx in ((1, 2), (2, 3), (3, 3), (4, 3)):
-            gq = self._gn_b(v, self.clips, Cc, self.frames * HW, f"{name}.conv{k}.0", 1e-5, True)
+            gq = self._gn_b(v, Cc, self.frames * HW, f"{name}.conv{k}.0", 1e-5, True)
             if v is not x:
                 A.put(v)
             v = self._conv_t3(gq, f"{name}.conv{k}.{idx}", HW, Cc, residual=x if k == 4 else None)
@@ -345,7 +324,7 @@ class I2VPlan(UNetPlan):
         """diffusers TransformerTemporalModel (1 layer, both attentions self over the frames, GEGLU feed-forward)."""
         A, W, M = self.arena, self.W, self.B * HW
         heads = inner // self.cfg.head_dim
-        gq = self._gn_b(x, self.clips, Cc, self.frames * HW, name + ".norm", 1e-6, False)
+        gq = self._gn_b(x, Cc, self.frames * HW, name + ".norm", 1e-6, False)
         h = A.get(self.B, HW, inner)
         pm = (inner + 127) // 128
         st = self._ln_buf[:pm * M * 2].view(pm, M, 2)
@@ -449,7 +428,7 @@ class I2VPlan(UNetPlan):
         A.put(x)
         self._emit(lib.tmix_conv_out, y.data_ptr(), W["conv_out.weight"].data_ptr(), W["conv_out.bias"].data_ptr(),
                    self.eps.data_ptr(), B, C0, Hh, Ww, cfg.out_channels)
-        self.ops = [(fn, tuple(a)) for fn, a in self.ops]
+        self._freeze()
 
     def __call__(self, sample, t):
         cfg = self.cfg

@@ -27,6 +27,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from .plan import LaunchPlan, hint_bytes  # noqa: F401  (hint_bytes: part of this module's interface, beside hint_policy)
 from .weights import fold_layernorm, interleave_geglu
 
 BF16 = torch.bfloat16
@@ -307,39 +308,6 @@ class KVCache:
 
 
 # =====================================================================================
-class _Arena:
-    """Size-keyed free list: the plan is a static, stream-ordered launch sequence, so a buffer released
-    at plan position i can be handed to any op planned after i."""
-
-    def __init__(self, device):
-        self.device, self.free, self.total = device, {}, 0
-        self.bufs = []          # owns every buffer for the plan's lifetime (views handed out are not owners)
-
-    def get(self, *shape, dtype=BF16):
-        n = 1
-        for s in shape:
-            n *= s
-        nbytes = (n * torch.empty((), dtype=dtype).element_size() + 255) // 256 * 256
-        lst = self.free.get(nbytes)
-        if lst:
-            buf = lst.pop()
-        else:
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self.bufs.append(buf)
-            self.total += nbytes
-        tns = buf.view(dtype)[:n].view(*shape)
-        tns._arena_buf = buf
-        return tns
-
-    def put(self, *ts):
-        for tns in ts:
-            buf = tns._arena_buf
-            self.free.setdefault(buf.numel(), []).append(buf)
-            for cs, _c in getattr(tns, "_cs", None) or ():  # GroupNorm column partials of this tensor (UNetPlan._colstats): every reader came before
-                self.put(cs)
-            tns._cs = None
-
-
 _TUNE_CACHE = {}      # repr((kind, shape key)) -> best TMIX_TILE_* id, shared by every plan in the process
 # The same launch wants a different tiling when its chain has the chip to itself than when a sibling chain runs beside it
 # (PlanGroup): alone, the tilings that put exactly one workgroup on each of the 256 CUs win by 15-35 % (L.TILE_EXCLUSIVE:
@@ -371,13 +339,14 @@ def save_tune_table(path):
         json.dump(dict(sorted(_TUNE_CACHE.items())), f, indent=0)
 
 
-def tune_lookup(ctx, key):
+def tune_lookup(ctx, key, table=_TUNE_CACHE):
     """tiling for launch shape `key` in context `ctx` ("" = the chain has the chip to itself, SHARED = a sibling chain runs
     beside it), or None when it must be measured: a shared chain falls back to the plain entry (tables written before the
-    contexts existed) unless that entry is a one-workgroup-per-CU tiling, which must not be inherited."""
-    c = _TUNE_CACHE.get(ctx + key)
+    contexts existed) unless that entry is a one-workgroup-per-CU tiling, which must not be inherited.  table: the process
+    cache, or another {context + key: tiling} dict (tilings_follow_table: the shipped file)."""
+    c = table.get(ctx + key)
     if c is None and ctx:
-        c = _TUNE_CACHE.get(key)
+        c = table.get(key)
         if ctx == SHARED and c in L.TILE_EXCLUSIVE:
             c = None
     return c
@@ -393,11 +362,6 @@ def hint_policy(B, h, w):
     cap = int(float(os.environ.get("TMIX_PF_CAP_MB", "8" if small_call else "0")) * (1 << 20))
     over = int(float(os.environ.get("TMIX_PF_CAP_OVER_MB", "20")) * (1 << 20))
     return cap, over
-
-
-def hint_bytes(nbytes, cap, over):
-    """bytes of an `nbytes` weight tensor that the launch in front of its consumer touches (tmix_gemm_prefetch_next)"""
-    return min(nbytes, cap) if cap and nbytes > over else nbytes
 
 
 @dataclass
@@ -419,78 +383,57 @@ def attention_levels(cfg: UNetConfig):
     return tuple(bi for bi, n in enumerate(cfg.transformer_layers) if n)
 
 
-class UNetPlan:
-    """One UNet call shape: batch B, latent h x w, a KV cache (prompt rows) and a routing flag.
+class BlockPlan(LaunchPlan):
+    """The op emitters of the blocks both UNets are made of -- ResnetBlock2D, Transformer2DModel with cached cross-attention K / V,
+    GroupNorm, implicit-GEMM convolutions -- with the state they keep while a plan is recorded and the tiling tuner.  UNetPlan and
+    i2vgen.I2VPlan derive from it, each with its own _build.  Every feature switch is a constructor parameter whose default means
+    "off", so a network states what it uses; every attribute an emitter reads is assigned here or in LaunchPlan.__init__
+    (tests/test_plan_attrs_cpu.py)."""
 
-    inputs  : self.latent [B,4,h,w] fp32, self.t_dev [B] fp32 (timestep, same value in every row)
-    output  : self.eps [B,4,h,w] fp32
-    """
-
-    # probe plans only (token_maps=...); the defaults serve every other plan and the video plan, which borrows _t2d
-    token_spec = None
-    token_maps = None
-    _tok_arr = None
-    _tok_fn = None
-
-    def __init__(self, W: UNetWeights, B: int, h: int, w: int, kv: KVCache, pooled: torch.Tensor,
-                 time_ids: torch.Tensor, routed: bool = False, autotune: bool = True, row_sets=None,
-                 latent=None, eps=None, shared: bool = False, t_dev=None, fp8: bool = False, token_maps: TokenMapSpec | None = None):
-        # How much of a LARGE weight tensor a hint names (round 6, profiles/r6_experiments/weight_hint_cap_*.txt): a launch of a single-seed call lasts 20 - 90 us, and
-        # touching the 39 MB of a routed q/k/v weight (or FF1's 26 MB) inside it costs the hinting launch more than the hinted one gains -- tensors over 20 MB
-        # are named by their first 8 MB there (1 MB ... 12 MB measure the same; 13 MB tensors want all of themselves: capping those loses 0.5 - 1 ms).  The co-batched
-        # calls (launches of 0.2 - 1 ms) keep whole-tensor hints.  TMIX_PF_CAP_MB / TMIX_PF_CAP_OVER_MB override (cap 0: whole tensors everywhere).
-        self._init_emit_state(W, B, h, w, hint_policy(B, h, w))
-        # fp8: the attn1 q/k/v, FF up- and down-projections run as tmix_gemm_fp8 (e4m3 operands, per-row power-of-two scales);
-        # their A operand is quantised by one tmix_quantize_fp8_rows launch in front of the GEMM
+    def __init__(self, W, B: int, h: int, w: int, hints, kv, gn_channels: int, ln_floats: int, *, fp8: bool = False, row_sets=None,
+                 routed: bool = False, lowrank: bool = False, qattn: bool = False, tune_ctx: str = "", token_maps: TokenMapSpec | None = None):
+        """hints: (cap, over) bytes of the weight hints (hint_policy); kv: the cached cross-attention K / V^T (k, vt, Lk, ld);
+        gn_channels: widest GroupNorm; ln_floats: size of the LayerNorm row-statistics buffer.
+        fp8: the attn1 q/k/v, FF up- and down-projections run as tmix_gemm_fp8 (e4m3 operands, per-row power-of-two scales), the
+        convolutions as tmix_conv3x3_nhwc_fp8;  routed: batch row b reads the merged LoRA weight set row_sets[b];  lowrank: the routed
+        projections run on SHARED weights over K + 64 input columns instead, and row_sets[b] only decides what tmix_lora_down writes into
+        the pad columns of row b (UNetWeights.lora_mode);  qattn: attn2.to_q and the cross-attention behind it as ONE launch where the
+        shapes allow;  tune_ctx: tile-table context ("" / SHARED / ROUTED);  token_maps: a probe plan, see TokenMapSpec."""
+        super().__init__(W.device, hints)
+        self.W, self.cfg, self.B, self.h, self.w, self.kv = W, W.cfg, B, h, w, kv
+        env = os.environ.get
+        # GroupNorm statistics come from the launch that WRITES the normalised tensor (col_stats_out of the conv / proj_out epilogue), so a
+        # norm is two launches (combine partials, apply) and one pass over x instead of three and two (TMIX_GN_STATS_KERNEL=1: the old form)
+        self._gn_fused = not env("TMIX_GN_STATS_KERNEL")
+        # conv_shortcut rides in conv2's K loop (tmix_conv_desc.S1 / S2): no shortcut GEMM, and the up-blocks' concatenations are never written
+        # (TMIX_SHORTCUT_GEMM=1: the separate GEMM + concat launches)
+        self._sc_fused = not env("TMIX_SHORTCUT_GEMM")
+        # key-split attention tail (tmix_attn_fwd_ws with a workspace), by request only (TMIX_ATTN_SPLIT=1): hot it takes 5 % off the S = 4096 launches and 2 % off
+        # S = 1024, in the captured step nothing (DESIGN.md 5b item 8) -- and a co-batched seed would no longer equal its single run bit for bit
+        self._attn_split = bool(env("TMIX_ATTN_SPLIT"))
         self.fp8 = bool(fp8)
-        self.fp8_chain_ff = not os.environ.get("TMIX_FP8_FF_ROWS")    # =1: quantise the FF intermediate per row with a separate launch
-        self.fp8_attn_out = not os.environ.get("TMIX_FP8_NO_ATTN_OUT")  # =1: attention output in bf16, out-projections on bf16 operands (round 3)
-        self.fp8_conv = not os.environ.get("TMIX_FP8_NO_CONV")         # =1: every convolution on bf16 operands (before round 4's tmix_conv3x3_nhwc_fp8)
-        self.fp8_conv_tile = int(os.environ.get("TMIX_FP8_CONV_TILE", "20"))   # 128 x 160 with two loader waves (12: without)
-        self.fp8_tile = int(os.environ.get("TMIX_FP8_TILE", "21"))      # 128 x 160 e4m3 tiling of the N = 1280 / 640 launches (21: loader waves, 12: none, 0: phase-offset only)
-        self.kv = kv
-        # LoRA routing: batch row b uses merged weight set row_sets[b] (default: row b of a single seed)
+        self.fp8_chain_ff = not env("TMIX_FP8_FF_ROWS")        # =1: quantise the FF intermediate per row with a separate launch
+        self.fp8_attn_out = not env("TMIX_FP8_NO_ATTN_OUT")    # =1: attention output in bf16, out-projections on bf16 operands (round 3)
+        self.fp8_conv = not env("TMIX_FP8_NO_CONV")            # =1: every convolution on bf16 operands (before round 4's tmix_conv3x3_nhwc_fp8)
+        self.fp8_conv_tile = int(env("TMIX_FP8_CONV_TILE", "20"))     # 128 x 160 with two loader waves (12: without)
+        self.fp8_tile = int(env("TMIX_FP8_TILE", "21"))        # 128 x 160 e4m3 tiling of the N = 1280 / 640 launches (21: loader waves, 12: none, 0: phase-offset only)
         self.row_sets = list(row_sets) if row_sets is not None else list(range(B))
-        self.routed = bool(routed) and W.kind == "lora" and len(self.row_sets) == B and max(self.row_sets) <= W.K
-        # tile-table context: this chain runs beside a sibling chain (PlanGroup member) / its projections are concept-routed / neither
-        self.tune_ctx = SHARED if shared else (ROUTED if (self.routed and getattr(W, "lora_mode", "merged") != "lowrank") else "")
-        # low-rank LoRA (UNetWeights.lora_mode): the routed projections run on SHARED weights over K + 64 input columns; the concept of a
-        # batch row only decides what tmix_lora_down writes into the pad columns of its rows
-        self.lowrank = self.routed and getattr(W, "lora_mode", "merged") == "lowrank"
-        if self.lowrank:
-            assert not self.fp8, "low-rank LoRA runs the bf16 projections only"
-            self.routed = False
-            self._sets_dev = torch.tensor(self.row_sets, device=W.device, dtype=torch.int32)
-        cfg = self.cfg
-        assert kv.B == B
-        dev = self.dev
-        # I/O buffers may be views into a larger batch owned by a PlanGroup (row-split execution on several streams)
-        self.latent = latent if latent is not None else torch.zeros(B, cfg.in_channels, h, w, device=dev, dtype=F32)
-        self.t_dev = t_dev if t_dev is not None else torch.zeros(B, device=dev, dtype=F32)
-        self.eps = eps if eps is not None else torch.zeros(B, cfg.out_channels, h, w, device=dev, dtype=F32)
-        assert self.latent.is_contiguous() and self.eps.is_contiguous() and self.latent.shape[0] == B
-        # static conditioning: aug_emb = add_embedding(cat[pooled, sinusoid(time_ids)])  (depends on rows only)
-        tid = ops.timestep_embedding(time_ids.to(dev, F32).reshape(-1).contiguous(), cfg.addition_time_embed_dim)
-        add_in = torch.cat([pooled.to(dev, F32), tid.reshape(B, -1)], dim=-1).contiguous()
-        hid = ops.linear_small(add_in, W["add_embedding.linear_1.weight"], W["add_embedding.linear_1.bias"], act_out=True)
-        self.aug = ops.linear_small(hid, W["add_embedding.linear_2.weight"], W["add_embedding.linear_2.bias"])
-        torch.cuda.synchronize()
-        self._gn_ws = ops.groupnorm_ws(B, 4096, cfg.norm_groups, dev)
+        self.routed, self.lowrank, self.tune_ctx = bool(routed), bool(lowrank), tune_ctx
+        assert not (self.routed and self.lowrank) and not (self.lowrank and self.fp8), "low-rank LoRA runs shared bf16 projections"
+        self._sets_dev = torch.tensor(self.row_sets, device=self.dev, dtype=torch.int32) if self.lowrank else None
+        # (tmix_gemm_q_cross_attn: no q round trip, 70 launches fewer per call); bf16 plans with the merged / shared weights, five-head tiles
+        # (C % 320 == 0, checked per site), <= 80 cached keys (TMIX_NO_QATTN=1: the two-launch form)
+        self._qattn = bool(qattn) and not env("TMIX_NO_QATTN") and not self.fp8 and not self.lowrank and kv.Lk <= 80 and kv.ld == 80
+        self._gn_ws = ops.groupnorm_ws(B, gn_channels, self.cfg.norm_groups, self.dev)
         # LayerNorm row statistics travel from the GEMM that writes the hidden state to the GEMM behind the norm as
         # per-column-tile partial sums [parts][B*S][2]; launches on one stream are ordered, so all sites share one buffer
-        nb = len(cfg.block_out_channels)
-        need = 1
-        for pfx, cc, _n in transformer_sites(cfg):
-            lvl = nb - 1 if pfx.startswith("mid") else int(pfx.split(".")[1]) if pfx.startswith("down") else nb - 1 - int(pfx.split(".")[1])
-            need = max(need, ((cc + 127) // 128) * B * (h >> lvl) * (w >> lvl) * 2)
-        self._ln_buf = torch.zeros(need, device=dev, dtype=F32)
-        # attn2.to_q and the 77-key cross-attention behind it as ONE launch (tmix_gemm_q_cross_attn: no q round trip, 70 launches fewer per call); bf16 plans
-        # with the merged / shared weights, five-head tiles (C % 320 == 0), <= 80 cached keys (TMIX_NO_QATTN=1: the two-launch form)
-        self._qattn = not os.environ.get("TMIX_NO_QATTN") and not self.fp8 and not self.lowrank and kv.Lk <= 80 and kv.ld == 80
+        self._ln_buf = torch.zeros(ln_floats, device=self.dev, dtype=F32)
+        self._ln_links = []                 # (producer desc, [consumer descs]): ln_parts follows the producer's tiling
+        self._vt, self._rows_cache, self._attn_ws = {}, {}, {}      # V^T buffers, per-row weight sets, key-split workspaces (_attn)
+        self._temb = {}                     # resnet name -> its rows of the one stacked time_emb_proj launch (filled by _build)
         # probe plan (token_maps): every attn2 of a probed level runs the two-launch form, whose q tensor one tmix_xattn_token_maps launch reads;
         # self.token_maps[level] is that level's fp32 [n_rows, n_tok, (h >> level) * (w >> level)] accumulator.  Without it: nothing changes.
-        self.token_spec = token_maps
-        self.token_maps = {}
+        self.token_spec, self.token_maps, self._tok_arr, self._tok_fn = token_maps, {}, None, None
         if token_maps is not None:
             tok = tuple(int(t) for t in token_maps.tokens)
             assert 1 <= len(tok) <= 32 and all(0 <= t < kv.Lk for t in tok) and kv.Lk <= 240, tok
@@ -501,42 +444,9 @@ class UNetPlan:
             self._tok_arr = ops.token_array(tok)
             for l in lv:
                 self.token_maps[l] = torch.zeros(token_maps.n_rows, len(tok), (h >> l) * (w >> l), device=self.dev, dtype=F32)
-        self._build()
-        self._link_ln()
-        if autotune:
-            self.autotune()
-        for m in self.token_maps.values():      # the tuner ran the forward (map launches included) on its own inputs
-            m.zero_()
 
-    def _init_emit_state(self, W, B: int, h: int, w: int, hints):
-        """the state the op emitters below keep while a plan is recorded, for this plan and i2vgen.I2VPlan alike: op list, buffer arena,
-        launch bookkeeping, the tuner's lists, caches, weight-prefetch hints (hints = (cap, over) bytes, see hint_policy) and the feature
-        switches both networks share.  What differs between the two (fp8, LoRA routing, attn2 in one launch, tile-table context) each
-        constructor sets itself."""
-        self.W, self.cfg, self.B, self.h, self.w = W, W.cfg, B, h, w
-        self.lib = L.load()
-        self.dev = W.device
-        self.ops = []
-        self.keep = []                      # descriptors / tensors that must outlive the plan
-        self.arena = _Arena(self.dev)
-        self.flops = 0
-        self.gemm_flops = 0
-        self.launches = {"gemm": [], "conv": [], "attn": []}
-        self.op_meta = {}                   # index into self.ops -> (class, flops, shape key) of the instrumented launches
-        self._tunable = []                  # (index into self.ops, kind, descriptor) of every GEMM / conv launch
-        self._ln_links = []                 # (producer desc, [consumer descs]): ln_parts follows the producer's tiling
-        self._vt, self._rows_cache, self._attn_ws = {}, {}, {}      # V^T buffers, per-row weight sets, key-split workspaces (_attn)
-        # every GEMM / conv launch is preceded by a tmix_gemm_prefetch_next hint naming the weights of the launch AFTER it (patched in
-        # when that launch is planned): the chain otherwise meets every weight cold from HBM (TMIX_NO_PREFETCH=1 switches it off)
-        self._pf_prev = None
-        self._pf_on = not os.environ.get("TMIX_NO_PREFETCH")
-        self._pf_cap, self._pf_cap_over = hints
-        # GroupNorm statistics come from the launch that WRITES the normalised tensor (col_stats_out of the conv / proj_out epilogue), so a
-        # norm is two launches (combine partials, apply) and one pass over x instead of three and two (TMIX_GN_STATS_KERNEL=1: the old form)
-        self._gn_fused = not os.environ.get("TMIX_GN_STATS_KERNEL")
-        # conv_shortcut rides in conv2's K loop (tmix_conv_desc.S1 / S2): no shortcut GEMM, and the up-blocks' concatenations are never written
-        # (TMIX_SHORTCUT_GEMM=1: the separate GEMM + concat launches)
-        self._sc_fused = not os.environ.get("TMIX_SHORTCUT_GEMM")
+    def refine(self, **kw):
+        return refine_group(self, **kw)
 
     @staticmethod
     def _tune_key(kind, d):
@@ -605,20 +515,6 @@ class UNetPlan:
         torch.cuda.synchronize()
 
     # ------------------------------------------------------------------ op emitters
-    def _emit(self, fn, *args):
-        self.ops.append((fn, args))
-
-    def _hint_weights(self, w):
-        """called when a GEMM / conv launch over weight tensor `w` is planned, BEFORE its op is emitted: names `w` in the previous
-        launch's prefetch hint and opens this launch's own hint slot."""
-        if not self._pf_on:
-            return
-        if self._pf_prev is not None:
-            self._pf_prev[0], self._pf_prev[1] = w.data_ptr(), hint_bytes(w.numel() * w.element_size(), self._pf_cap, self._pf_cap_over)
-        self._pf_prev = [None, 0]
-        self.keep.append(w)
-        self.ops.append((self.lib.tmix_gemm_prefetch_next, self._pf_prev))
-
     def _colstats(self, owner, rows, HW, Cc):
         """column-partials buffer [rows/32, 2, Cc] for the launch that writes `owner` ([B, HW, Cc]); it travels with the tensor (owner._cs, released
         with it) and _gn picks it up.  None when the geometry does not allow it (32-row blocks must not straddle images)."""
@@ -628,46 +524,54 @@ class UNetPlan:
         owner._cs = ((cs, Cc),)
         return cs
 
+    @staticmethod
+    def _cs_parts(x, x2=None):
+        """the producers' column partials ((buffer, channels), ...) of x, or of the channel-concatenation [x | x2]; None without them"""
+        parts = getattr(x, "_cs", None)
+        if x2 is not None:
+            p2 = getattr(x2, "_cs", None)
+            parts = (parts[0], p2[0]) if parts and p2 and len(parts) == 1 and len(p2) == 1 else None
+        return parts
+
     def _gn_f8_ok(self, x, Cc, HW, x2=None):
         """can the GroupNorm over x (| x2) leave its result as e4m3 + row-major MX scales for tmix_conv3x3_nhwc_fp8?  fp8 plans, Cc % 128 == 0, and the
         statistics must come from the producers (the e4m3 output exists for tmix_groupnorm_nhwc_pre only)"""
         if not (self.fp8 and self.fp8_conv) or Cc % 128 or HW % 32:
             return False
-        parts = getattr(x, "_cs", None)
-        if x2 is not None:
-            p2 = getattr(x2, "_cs", None)
-            parts = (parts[0], p2[0]) if parts and p2 and len(parts) == 1 and len(p2) == 1 else None
+        parts = self._cs_parts(x, x2)
         return bool(parts) and sum(c for _t, c in parts) == Cc
 
-    def _gn(self, x, Cc, HW, name, eps, silu, out=None, x2=None, f8=False):
+    def _gn(self, x, Cc, HW, name, eps, silu, out=None, x2=None, f8=False, images=None, max_rows=None):
         """x2: a second tensor normalised as the channel-concatenation [x | x2] (Cc counts both).
-        f8 (only when _gn_f8_ok): returns (e4m3 bytes [B, HW, Cc], scales [B * HW, Cc / 32]) instead of the bf16 tensor."""
+        f8 (only when _gn_f8_ok): returns (e4m3 bytes [B, HW, Cc], scales [B * HW, Cc / 32]) instead of the bf16 tensor.
+        images: images of HW rows each (default: the batch); max_rows: the producers' partials serve up to this many rows per image."""
+        Bn = self.B if images is None else images
         if f8:
-            out = (self.arena.get(self.B, HW, Cc, dtype=torch.uint8), self.arena.get(self.B * HW, Cc // 32, dtype=torch.uint8))
+            out = (self.arena.get(Bn, HW, Cc, dtype=torch.uint8), self.arena.get(Bn * HW, Cc // 32, dtype=torch.uint8))
         else:
-            out = out if out is not None else self.arena.get(self.B, HW, Cc)
+            out = out if out is not None else self.arena.get(Bn, HW, Cc)
         W = self.W
         C2 = 0 if x2 is None else x2.shape[-1]
-        parts = getattr(x, "_cs", None)
-        if x2 is not None:
-            p2 = getattr(x2, "_cs", None)
-            parts = (parts[0], p2[0]) if parts and p2 and len(parts) == 1 and len(p2) == 1 else None
-        if parts and sum(c for _t, c in parts) == Cc and HW % ops.COLSTATS_ROWS == 0:     # (video plans keep partials whose 32-row blocks fit the CLIP but not the frame)
+        args = [x.data_ptr(), Cc - C2, x2.data_ptr() if C2 else None, C2, *(o.data_ptr() for o in (out if f8 else (out,))),
+                W[name + ".weight"].data_ptr(), W[name + ".bias"].data_ptr(), self._gn_ws.data_ptr(), Bn, HW, self.cfg.norm_groups, eps, int(silu)]
+        parts = self._cs_parts(x, x2)
+        # (video plans keep partials whose 32-row blocks fit the CLIP but not the frame)
+        if parts and sum(c for _t, c in parts) == Cc and HW % ops.COLSTATS_ROWS == 0 and (max_rows is None or HW <= max_rows):
             (cs1, c1), (cs2, c2) = (parts[0], parts[1]) if len(parts) == 2 else (parts[0], (None, 0))
-            if f8:
-                self._emit(self.lib.tmix_groupnorm_nhwc_pre_f8, x.data_ptr(), Cc - C2, x2.data_ptr() if C2 else None, C2, out[0].data_ptr(), out[1].data_ptr(),
-                           W[name + ".weight"].data_ptr(), W[name + ".bias"].data_ptr(), self._gn_ws.data_ptr(), self.B, HW, self.cfg.norm_groups, eps, int(silu),
-                           cs1.data_ptr(), c1, cs2.data_ptr() if cs2 is not None else None, c2)
-            else:
-              self._emit(self.lib.tmix_groupnorm_nhwc_pre, x.data_ptr(), Cc - C2, x2.data_ptr() if C2 else None, C2, out.data_ptr(), W[name + ".weight"].data_ptr(),
-                       W[name + ".bias"].data_ptr(), self._gn_ws.data_ptr(), self.B, HW, self.cfg.norm_groups, eps, int(silu),
-                       cs1.data_ptr(), c1, cs2.data_ptr() if cs2 is not None else None, c2)
+            fn = "tmix_groupnorm_nhwc_pre_f8" if f8 else "tmix_groupnorm_nhwc_pre"
+            args += [cs1.data_ptr(), c1, cs2.data_ptr() if cs2 is not None else None, c2]
         else:
             assert not f8
-            self._emit(self.lib.tmix_groupnorm_nhwc, x.data_ptr(), Cc - C2, x2.data_ptr() if C2 else None, C2, out.data_ptr(), W[name + ".weight"].data_ptr(),
-                       W[name + ".bias"].data_ptr(), self._gn_ws.data_ptr(), self.B, HW, self.cfg.norm_groups, eps, int(silu))
-        self.op_meta[len(self.ops) - 1] = ("norm", 0, ("norm", self.B, HW, Cc))
+            fn = "tmix_groupnorm_nhwc"
+        self._launch(fn, tuple(args), 0, key=("norm", Bn, HW, Cc))
         return out
+
+    def _ln_link(self, d, kw):
+        """a GEMM that writes LayerNorm row statistics opens a site; one that reads them joins the site opened last"""
+        if kw.get("row_stats_out") is not None:
+            self._ln_links.append((d, []))
+        elif kw.get("ln_stats") is not None:
+            self._ln_links[-1][1].append(d)
 
     def _gemm(self, a, w, out, fp8_key=None, f8_copy=None, a8=None, **kw):
         """f8_copy: an ops.F8Copy that also receives the e4m3 + MX-block copy of the stored rows (fp8 plans: the next projection's A
@@ -685,19 +589,9 @@ class UNetPlan:
         if f8_copy is not None:
             f8_copy.attach(d)
             self.keep.append(f8_copy)
-        if kw.get("row_stats_out") is not None:
-            self._ln_links.append((d, []))
-        elif kw.get("ln_stats") is not None:
-            self._ln_links[-1][1].append(d)
-        self.keep.append(d)
-        self._hint_weights(w)
-        self._emit(self.lib.tmix_gemm_bf16, C.byref(d))
+        self._ln_link(d, kw)
         fl = 2 * d.M * d.N * d.K * d.batch
-        self.flops += fl
-        self.gemm_flops += fl
-        self.launches["gemm"].append((d, fl))
-        self._tunable.append((len(self.ops) - 1, "gemm", d))
-        self.op_meta[len(self.ops) - 1] = ("gemm", fl, d)
+        self._launch("tmix_gemm_bf16", (C.byref(d),), fl, gemm_flops=fl, desc=d, weight=w, tunable="gemm")
         return out
 
     def _gemm_fp8(self, a, key, out, f8_out=None, f8_copy=None, **kw):
@@ -743,18 +637,9 @@ class UNetPlan:
         if f8_copy is not None:
             f8_copy.attach(d)
             self.keep.append(f8_copy)
-        if kw.get("row_stats_out") is not None:
-            self._ln_links.append((d, []))
-        elif kw.get("ln_stats") is not None:
-            self._ln_links[-1][1].append(d)
-        self.keep += [d, a8, sa]
-        self._hint_weights(w8)
-        self._emit(self.lib.tmix_gemm_fp8, C.byref(d), sa.data_ptr(), sw.data_ptr())
+        self._ln_link(d, kw)
         fl = 2 * d.M * d.N * d.K * d.batch
-        self.flops += fl
-        self.gemm_flops += fl
-        self.launches["gemm"].append((d, fl))
-        self.op_meta[len(self.ops) - 1] = ("gemm_fp8", fl, d)       # its own class: priced against the fp8 MFMA peak (bench.py)
+        self._launch("tmix_gemm_fp8", (C.byref(d), sa.data_ptr(), sw.data_ptr()), fl, gemm_flops=fl, desc=d, weight=w8, keep=(a8, sa))      # (not tunable: tile_cfg is set above)
         if owned:
             self.arena.put(*owned)                  # stream-ordered: free for ops planned after this GEMM
         return out
@@ -770,13 +655,8 @@ class UNetPlan:
             d = ops.make_conv_desc(x8.view(self.B, Hh, Ww, Cin), w8.view(Cout, 3, 3, Cin), out.view(self.B, Ho, Wo, Cout), self.W[wname + ".bias"], batch_bias,
                                    residual, mode, tile_cfg=self.fp8_conv_tile, bias_images=bias_images,
                                    col_stats_out=self._colstats(out, self.B * Ho * Wo, Ho * Wo, Cout), _fp8=True)
-            self.keep += [d, x8, sx, w8, sw]
-            self._hint_weights(w8)
-            self._emit(self.lib.tmix_conv3x3_nhwc_fp8, C.byref(d), sx.data_ptr(), sw.data_ptr())
-            fl = 2 * self.B * Ho * Wo * Cout * 9 * Cin
-            self.flops += fl
-            self.launches["conv"].append((d, fl))
-            self.op_meta[len(self.ops) - 1] = ("conv_fp8", fl, d)
+            self._launch("tmix_conv3x3_nhwc_fp8", (C.byref(d), sx.data_ptr(), sw.data_ptr()), 2 * self.B * Ho * Wo * Cout * 9 * Cin,
+                         desc=d, weight=w8, keep=(x8, sx, w8, sw))
             return out
         w, bias, sc, csc = self.W[wname + ".weight"], self.W[wname + ".bias"], None, 0
         taps = 9
@@ -790,14 +670,8 @@ class UNetPlan:
                                bias, batch_bias, residual, mode, bias_images=bias_images,
                                col_stats_out=self._colstats(out, self.B * Ho * Wo, Ho * Wo, Cout),      # every conv output of this network feeds a GroupNorm
                                shortcut=sc)
-        self.keep.append(d)
-        self._hint_weights(w)
-        self._emit(self.lib.tmix_conv3x3_nhwc, C.byref(d))
-        fl = 2 * self.B * Ho * Wo * Cout * (taps * Cin + csc)      # (the flops performed: the folded upsampler counts its 4 taps)
-        self.flops += fl
-        self.launches["conv"].append((d, fl))
-        self._tunable.append((len(self.ops) - 1, "conv", d))
-        self.op_meta[len(self.ops) - 1] = ("conv", fl, d)
+        self._launch("tmix_conv3x3_nhwc", (C.byref(d),), 2 * self.B * Ho * Wo * Cout * (taps * Cin + csc),      # (the flops performed: the folded upsampler counts its 4 taps)
+                     desc=d, weight=w, tunable="conv")
         return out
 
     def _ln_stats(self, S, Cc):
@@ -825,47 +699,30 @@ class UNetPlan:
               "bias": self._rows(key, ".bias") if self.routed else W[key + ".bias"]}
         w = self._rows(key) if self.routed else W[key]
         d = ops.make_gemm_desc(h.view(*shp, Cc), w, None, **kw)
-        self._ln_links[-1][1].append(d)
+        self._ln_link(d, kw)
         args = ops.q_cross_attn_args(k, vt, ao, S, self.cfg.head_dim ** -0.5)
-        self.keep += [d, k, vt, ao]
-        self._hint_weights(w)
-        self._emit(self.lib.tmix_gemm_q_cross_attn, C.byref(d), *args)
         fl = 2 * d.M * d.N * d.K * d.batch
         fla = 4 * self.B * (Cc // 64) * S * k.shape[1] * 64
-        self.flops += fl + fla
-        self.gemm_flops += fl
-        self.launches["gemm"].append((d, fl))
-        self.op_meta[len(self.ops) - 1] = ("gemm", fl + fla, d)
+        self._launch("tmix_gemm_q_cross_attn", (C.byref(d), *args), fl + fla, gemm_flops=fl, desc=d, weight=w, keep=(k, vt, ao))
         return ao
 
     def _attn(self, q, k, vt, out, H, Sq, Skv, f8_out=None):
         """f8_out: an ops.F8Copy that receives the output as e4m3 + MX block scales instead of the bf16 tensor `out` (fp8 plans: the out-projection's
         A operand without a quantiser launch and with half the bytes)"""
-        # key-split tail (tmix_attn_fwd_ws), by request only (TMIX_ATTN_SPLIT=1): hot it takes 5 % off the S = 4096 launches and 2 % off S = 1024, in the
-        # captured step nothing (DESIGN.md 5b item 8) -- and a co-batched seed would no longer equal its single run bit for bit.  One zeroed workspace per
-        # launch shape of this chain (launches of a chain are serial on its stream)
+        # TMIX_ATTN_SPLIT: one zeroed workspace per launch shape of this chain (launches of a chain are serial on its stream)
         ws = None
-        if os.environ.get("TMIX_ATTN_SPLIT"):
+        if self._attn_split:
             wkey = (self.B, H, Sq, Skv)
             if wkey not in self._attn_ws:
                 self._attn_ws[wkey] = ops.attention_split_ws(*wkey, q.device)
             ws = self._attn_ws[wkey]
-        wsa = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
         if f8_out is not None:
-            args = (q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
-                    vt.data_ptr(), vt.stride(1), vt.stride(0), f8_out.q.data_ptr(), f8_out.N, f8_out.scales.data_ptr(), f8_out.rows,
-                    self.B, H, Sq, Skv, self.cfg.head_dim ** -0.5, *wsa)
-            self._emit(self.lib.tmix_attn_fwd_f8_ws, *args)
-            self.keep.append(f8_out)
+            fn, dst = "tmix_attn_fwd_f8_ws", (f8_out.q.data_ptr(), f8_out.N, f8_out.scales.data_ptr(), f8_out.rows)
         else:
-            args = (q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
-                    vt.data_ptr(), vt.stride(1), vt.stride(0), out.data_ptr(), out.stride(1), out.stride(0),
-                    self.B, H, Sq, Skv, self.cfg.head_dim ** -0.5, *wsa)
-            self._emit(self.lib.tmix_attn_fwd_ws, *args)
-        fl = 4 * self.B * H * Sq * Skv * 64
-        self.flops += fl
-        self.launches["attn"].append((args, fl))
-        self.op_meta[len(self.ops) - 1] = ("attn", fl, ("attn", self.B, H, Sq, Skv))
+            fn, dst = "tmix_attn_fwd_ws", (out.data_ptr(), out.stride(1), out.stride(0))
+        args = (q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), vt.data_ptr(), vt.stride(1), vt.stride(0), *dst,
+                self.B, H, Sq, Skv, self.cfg.head_dim ** -0.5, *((ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)))
+        self._launch(fn, args, 4 * self.B * H * Sq * Skv * 64, key=("attn", self.B, H, Sq, Skv), keep=(f8_out,))
         return out
 
     def _probe_level(self, Hh):
@@ -911,23 +768,11 @@ class UNetPlan:
         h1 = self._gn(x, Ci, HW, name + ".norm1", 1e-5, True, x2=x2, f8=f81)
         temb, per = self._time_bias(name, Co, emb)
         h2 = self._conv(h1, name + ".conv1", Hh, Ww, Ci, Co, batch_bias=temb, bias_images=per)
-        A.put(*h1) if f81 else A.put(h1)
+        self._put(h1)
         sc_fused = self._sc_ok(Ci, Co, x.shape[-1], 0 if x2 is None else x2.shape[-1])
         f82 = (not sc_fused) and self._gn_f8_ok(h2, Co, HW)
         h3 = self._gn(h2, Co, HW, name + ".norm2", 1e-5, True, f8=f82)
         A.put(h2)
-        if f82:
-            assert x2 is None
-            if Ci != Co:
-                sc = A.get(B, HW, Co)
-                self._gemm(x.view(B * HW, Ci), W[name + ".conv_shortcut.weight"], sc.view(B * HW, Co), bias=W[name + ".conv_shortcut.bias"])
-            else:
-                sc = x
-            out = self._conv(h3, name + ".conv2", Hh, Ww, Co, Co, residual=sc)
-            A.put(*h3)
-            if Ci != Co:
-                A.put(sc)
-            return out
         if sc_fused:
             out = self._conv(h3, name + ".conv2", Hh, Ww, Co, Co, shortcut=(name, x, x2))
             A.put(h3)
@@ -939,10 +784,14 @@ class UNetPlan:
         else:
             sc = x
         out = self._conv(h3, name + ".conv2", Hh, Ww, Co, Co, residual=sc)
-        A.put(h3)
+        self._put(h3)
         if Ci != Co:
             A.put(sc)
         return out
+
+    def _put(self, t):
+        """release a GroupNorm result: the bf16 tensor, or the (e4m3 bytes, scales) pair of _gn(f8=True)"""
+        self.arena.put(*t) if isinstance(t, tuple) else self.arena.put(t)
 
     def _proj(self, a, key, out, S, Cin, ln=None, stats_out=None, fp8=False, a8=None, a_full=None, **kw):
         """Linear over [B,S,Cin] tokens: per-row merged weights when LoRA-routed, else one shared GEMM.
@@ -951,6 +800,10 @@ class UNetPlan:
         W = self.W
         batched = self.routed or kw.get("out_t") is not None    # transposed V is per batch row -> keep the batch dimension
         shp = (self.B, S) if batched else (self.B * S,)
+        if stats_out is not None:
+            kw["row_stats_out"] = stats_out
+        if kw.get("residual") is not None:
+            kw["residual"] = kw["residual"].view(*shp, kw["residual"].shape[-1])
         if self.lowrank and (key + ".lr") in W.t:
             # up(down(x)) as the projection's last K-tile: the pad columns behind the rows of `a` (a_full = the [B, S, Cin + 64] buffer `a`
             # is a view of) receive the rows' down-projections, then ONE shared GEMM over Cin + 64 columns
@@ -962,20 +815,12 @@ class UNetPlan:
                        1e-5, self._sets_dev.data_ptr(), S)
             if lnk:
                 kw["ln_stats"], kw["ln_colsum"], kw["bias"] = ln, W[key + ".colsum"], W[key + ".bias"]
-            if stats_out is not None:
-                kw["row_stats_out"] = stats_out
-            if kw.get("residual") is not None:
-                kw["residual"] = kw["residual"].view(*shp, kw["residual"].shape[-1])
             kw["ln_k"] = Cin if lnk else None
             return self._gemm(a_full.view(*shp, Cin + 64), W[key + ".lr"], out.view(*shp, out.shape[-1]), **kw)
         if ln is not None:
             kw["ln_stats"] = ln
             kw["ln_colsum"] = self._rows(key, ".colsum") if self.routed else W[key + ".colsum"]
             kw["bias"] = self._rows(key, ".bias") if self.routed else W[key + ".bias"]
-        if stats_out is not None:
-            kw["row_stats_out"] = stats_out
-        if kw.get("residual") is not None:
-            kw["residual"] = kw["residual"].view(*shp, kw["residual"].shape[-1])
         w = self._rows(key) if self.routed else W[key]
         if fp8 and self.fp8:
             kw["fp8_key"] = (key + "_rows", tuple(range(w.shape[0])) if self._periodic(w.shape[0]) else tuple(self.row_sets)) if self.routed else key
@@ -996,10 +841,29 @@ class UNetPlan:
             self._rows_cache[key + suffix] = w[torch.tensor(self.row_sets, device=w.device)].contiguous()
         return self._rows_cache[key + suffix]
 
+    def _attn_out(self, q, k, vt, Skv, a, release, h, S, Cc, st, h8, ao8, pad, lvl=None):
+        """one attention of a transformer block and its out-projection back into the residual stream h: the output goes to the e4m3 copy ao8
+        (fp8 plans: the out-projection reads e4m3 operands, no quantiser launch) or to a bf16 buffer (with `pad` columns behind every row
+        for low-rank LoRA); lvl: the probe level whose token maps read q; `release`: the arena tensor q (and k) live in, free once the
+        attention has read it"""
+        B, A = self.B, self.arena
+        H = Cc // self.cfg.head_dim
+        kw = dict(bias=self.W[a + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8)
+        ao_full = None if ao8 is not None else A.get(B, S, Cc + pad)
+        ao = None if ao8 is not None else ao_full[:, :, :Cc] if pad else ao_full
+        self._attn(q, k, vt, ao, H, S, Skv, f8_out=ao8)
+        if lvl is not None:
+            self._token_maps(q, a, H, S, lvl)
+        A.put(release)
+        if ao8 is not None:
+            self._proj(ao8.q.view(B, S, Cc), a + ".out", h, S, Cc, fp8=True, a8=ao8, **kw)
+        else:
+            self._proj(ao, a + ".out", h, S, Cc, a_full=ao_full, **kw)
+            A.put(ao_full)
+
     def _t2d(self, x, Cc, Hh, Ww, name, n):
         B, W, A = self.B, self.W, self.arena
         S = Hh * Ww
-        H = Cc // self.cfg.head_dim
         g = self._gn(x, Cc, S, name + ".norm", 1e-6, False)
         pad = 64 if self.lowrank else 0              # low-rank LoRA: 64 pad columns behind every row that feeds a routed projection
         h_full = A.get(B, S, Cc + pad)
@@ -1025,17 +889,7 @@ class UNetPlan:
             # --- self attention; norm1 is folded into the q/k/v projection
             qk = A.get(B, S, 2 * Cc)
             self._proj(h, a1 + ".qkv", qk, S, Cc, ln=st, out_t=vt, n_trans_begin=2 * Cc, fp8=True, a8=h8, a_full=h_full)
-            if ao8 is not None:                        # fp8 plans: attention output as e4m3 + MX blocks, out-projection on e4m3 operands
-                self._attn(qk[:, :, :Cc], qk[:, :, Cc:], vt, None, H, S, S, f8_out=ao8)
-                A.put(qk)
-                self._proj(ao8.q.view(B, S, Cc), a1 + ".out", h, S, Cc, bias=W[a1 + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8, fp8=True, a8=ao8)
-            else:
-                ao_full = A.get(B, S, Cc + pad)
-                ao = ao_full[:, :, :Cc] if pad else ao_full
-                self._attn(qk[:, :, :Cc], qk[:, :, Cc:], vt, ao, H, S, S)
-                A.put(qk)
-                self._proj(ao, a1 + ".out", h, S, Cc, bias=W[a1 + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8, a_full=ao_full)
-                A.put(ao_full)
+            self._attn_out(qk[:, :, :Cc], qk[:, :, Cc:], vt, S, a1, qk, h, S, Cc, st, h8, ao8, pad)
             # --- cross attention against the cached K / V^T; norm2 folded into to_q
             # The choice is a function of the IMAGE's shape only, never of the batch (like gn_small_gpw): the one-launch form rounds q and runs its softmax
             # differently from the pair, so a batch-dependent choice would make a co-batched seed differ from its single-seed run.  64 tiles of
@@ -1047,27 +901,10 @@ class UNetPlan:
                 self._q_attn(h, a2 + ".q", self.kv.k[a2], self.kv.vt[a2], ao, S, Cc, st)
                 self._proj(ao, a2 + ".out", h, S, Cc, bias=W[a2 + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8, a_full=ao)
                 A.put(ao)
-                q = None
             else:
                 q = A.get(B, S, Cc)
                 self._proj(h, a2 + ".q", q, S, Cc, ln=st, fp8=h8 is not None, a8=h8, a_full=h_full)
-            if q is None:
-                pass
-            elif ao8 is not None:
-                self._attn(q, self.kv.k[a2], self.kv.vt[a2], None, H, S, self.kv.Lk, f8_out=ao8)
-                if lvl is not None:
-                    self._token_maps(q, a2, H, S, lvl)
-                A.put(q)
-                self._proj(ao8.q.view(B, S, Cc), a2 + ".out", h, S, Cc, bias=W[a2 + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8, fp8=True, a8=ao8)
-            else:
-                ao_full = A.get(B, S, Cc + pad)
-                ao = ao_full[:, :, :Cc] if pad else ao_full
-                self._attn(q, self.kv.k[a2], self.kv.vt[a2], ao, H, S, self.kv.Lk)
-                if lvl is not None:
-                    self._token_maps(q, a2, H, S, lvl)
-                A.put(q)
-                self._proj(ao, a2 + ".out", h, S, Cc, bias=W[a2 + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8, a_full=ao_full)
-                A.put(ao_full)
+                self._attn_out(q, self.kv.k[a2], self.kv.vt[a2], self.kv.Lk, a2, q, h, S, Cc, st, h8, ao8, pad, lvl)
             # --- feed forward: norm3 folded into the first GEMM, GEGLU fused in its epilogue
             if self.fp8 and self.fp8_chain_ff:
                 # the intermediate leaves FF1 as e4m3 with one E8M0 scale per 32 columns and FF2 reads it as block-scaled A
@@ -1105,6 +942,55 @@ class UNetPlan:
             out._cs = (p1[0], p2[0])
             x1._cs = x2._cs = None
         return out
+
+
+class UNetPlan(BlockPlan):
+    """One UNet call shape: batch B, latent h x w, a KV cache (prompt rows) and a routing flag.
+
+    inputs  : self.latent [B,4,h,w] fp32, self.t_dev [B] fp32 (timestep, same value in every row)
+    output  : self.eps [B,4,h,w] fp32
+    """
+
+    def __init__(self, W: UNetWeights, B: int, h: int, w: int, kv: KVCache, pooled: torch.Tensor,
+                 time_ids: torch.Tensor, routed: bool = False, autotune: bool = True, row_sets=None,
+                 latent=None, eps=None, shared: bool = False, t_dev=None, fp8: bool = False, token_maps: TokenMapSpec | None = None):
+        cfg = W.cfg
+        assert kv.B == B
+        # LoRA routing: batch row b uses merged weight set row_sets[b] (default: row b of a single seed)
+        row_sets = list(row_sets) if row_sets is not None else list(range(B))
+        routed = bool(routed) and W.kind == "lora" and len(row_sets) == B and max(row_sets) <= W.K
+        lowrank = routed and W.lora_mode == "lowrank"
+        # tile-table context: this chain runs beside a sibling chain (PlanGroup member) / its projections are concept-routed / neither
+        tune_ctx = SHARED if shared else (ROUTED if routed and not lowrank else "")
+        nb = len(cfg.block_out_channels)
+        need = 1                            # the widest LayerNorm site's row statistics
+        for pfx, cc, _n in transformer_sites(cfg):
+            lvl = nb - 1 if pfx.startswith("mid") else int(pfx.split(".")[1]) if pfx.startswith("down") else nb - 1 - int(pfx.split(".")[1])
+            need = max(need, ((cc + 127) // 128) * B * (h >> lvl) * (w >> lvl) * 2)
+        # How much of a LARGE weight tensor a hint names (round 6, profiles/r6_experiments/weight_hint_cap_*.txt): a launch of a single-seed call lasts 20 - 90 us, and
+        # touching the 39 MB of a routed q/k/v weight (or FF1's 26 MB) inside it costs the hinting launch more than the hinted one gains -- tensors over 20 MB
+        # are named by their first 8 MB there (1 MB ... 12 MB measure the same; 13 MB tensors want all of themselves: capping those loses 0.5 - 1 ms).  The co-batched
+        # calls (launches of 0.2 - 1 ms) keep whole-tensor hints.  TMIX_PF_CAP_MB / TMIX_PF_CAP_OVER_MB override (cap 0: whole tensors everywhere).
+        super().__init__(W, B, h, w, hint_policy(B, h, w), kv, 4096, need, fp8=fp8, row_sets=row_sets, routed=routed and not lowrank,
+                         lowrank=lowrank, qattn=True, tune_ctx=tune_ctx, token_maps=token_maps)
+        dev = self.dev
+        # I/O buffers may be views into a larger batch owned by a PlanGroup (row-split execution on several streams)
+        self.latent = latent if latent is not None else torch.zeros(B, cfg.in_channels, h, w, device=dev, dtype=F32)
+        self.t_dev = t_dev if t_dev is not None else torch.zeros(B, device=dev, dtype=F32)
+        self.eps = eps if eps is not None else torch.zeros(B, cfg.out_channels, h, w, device=dev, dtype=F32)
+        assert self.latent.is_contiguous() and self.eps.is_contiguous() and self.latent.shape[0] == B
+        # static conditioning: aug_emb = add_embedding(cat[pooled, sinusoid(time_ids)])  (depends on rows only)
+        tid = ops.timestep_embedding(time_ids.to(dev, F32).reshape(-1).contiguous(), cfg.addition_time_embed_dim)
+        add_in = torch.cat([pooled.to(dev, F32), tid.reshape(B, -1)], dim=-1).contiguous()
+        hid = ops.linear_small(add_in, W["add_embedding.linear_1.weight"], W["add_embedding.linear_1.bias"], act_out=True)
+        self.aug = ops.linear_small(hid, W["add_embedding.linear_2.weight"], W["add_embedding.linear_2.bias"])
+        torch.cuda.synchronize()
+        self._build()
+        self._link_ln()
+        if autotune:
+            self.autotune()
+        for m in self.token_maps.values():      # the tuner ran the forward (map launches included) on its own inputs
+            m.zero_()
 
     # ------------------------------------------------------------------ whole network
     def _build(self):
@@ -1187,21 +1073,9 @@ class UNetPlan:
         self._emit(lib.tmix_conv_out, y.data_ptr(), W["conv_out.weight"].data_ptr(), W["conv_out.bias"].data_ptr(),
                    self.eps.data_ptr(), B, C0, Hh, Ww, cfg.out_channels)
         self.flops += 2 * B * Hh * Ww * 9 * (cfg.in_channels * C0 + C0 * cfg.out_channels)
-        self.ops = [(fn, tuple(a)) for fn, a in self.ops]
+        self._freeze()
 
     # ------------------------------------------------------------------ execution
-    def issued_meta(self):
-        """(class, flops, key) of the instrumented launches (tmix_prof_begin) in the order run() issues them."""
-        return [self.op_meta[i] for i in range(len(self.ops)) if i in self.op_meta]
-
-    def run(self, stream=None):
-        """enqueue the whole forward on `stream` (default: torch's current stream). No sync, no alloc."""
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        for fn, args in self.ops:
-            rc = fn(*args, st)
-            if rc:
-                L.check(rc, fn.__name__)
-
     def __call__(self, latent, t):
         """eps = unet(latent[B,4,h,w], t) with this plan's prompt rows.  Returns the plan's eps buffer."""
         self.latent.copy_(latent)
@@ -1348,26 +1222,15 @@ def tilings_follow_table(plan):
     with open(_TUNE_FILE) as f:                 # the FILE, not the process cache (which also holds shapes timed on this box)
         table = {k: int(v) for k, v in json.load(f).items()}
 
-    def shipped(ctx, key):
-        c = table.get(ctx + key)
-        if c is None and ctx:
-            c = table.get(key)
-            if ctx == SHARED and c in L.TILE_EXCLUSIVE:
-                c = None
-        return c
-
     for p in _plans_of(plan):
         for _i, kind, d in p._tunable:
             k = p._tune_key(kind, d)
-            want = shipped(p.tune_ctx, k)
+            want = tune_lookup(p.tune_ctx, k, table)
             if kind == "gemm" and (d.reserved0 & L.F8_COPY_OUT) and want is not None:
                 want = ops.f8copy_tile(want)
             if want != d.tile_cfg:
                 bad.append((k, d.tile_cfg, want))
     return not bad, bad
-
-
-UNetPlan.refine = lambda self, **kw: refine_group(self, **kw)
 
 
 class PlanGroup:

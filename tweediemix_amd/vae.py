@@ -16,7 +16,7 @@ import torch
 
 from . import lib as L
 from . import ops
-from .unet import _Arena
+from .plan import LaunchPlan
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -121,35 +121,41 @@ def synthetic_state_dict(cfg, seed=4321, device="cpu", nontrivial=False, encoder
     return sd
 
 
-class VAEDecoderPlan:
-    """decode(latent[B,4,h,w] fp32) -> image [B,3,8h,8w] fp32 in [0,1]."""
+def kernel_layout_weights(sd, side, dev, fold_up2=False):
+    """the `side` ("decoder" / "encoder") half of an AutoencoderKL state dict in kernel layouts: norms and biases fp32, 3x3 convolutions
+    [Co, 3, 3, Ci] bf16 (the upsamplers also folded into four 2x2 phase kernels when fold_up2: TMIX_CONV_UP2F, from the checkpoint's precision),
+    1x1 shortcuts and Linear weights [N, K] bf16, conv_in fp32, the mid-block attention's q / k / v stacked.  The 1x1 (post_)quant_conv is not
+    in it: the plans apply it themselves."""
+    t = {}
+    for k, v in sd.items():
+        if not k.startswith(side + "."):
+            continue
+        v = v.to(dev)
+        if k.endswith(".bias") or "norm" in k:
+            t[k] = v.to(F32).contiguous()
+        elif v.dim() == 4 and v.shape[-1] == 3 and not k.startswith(side + ".conv_in"):
+            t[k] = v.permute(0, 2, 3, 1).to(BF16).contiguous()
+            if fold_up2 and ".upsamplers." in k:
+                t[k + ".up2f"] = ops.fold_up2_weight(v.permute(0, 2, 3, 1))
+        elif v.dim() == 4 and v.shape[-1] == 1:
+            t[k] = v.reshape(v.shape[0], v.shape[1]).to(BF16).contiguous()
+        elif v.dim() == 2:
+            t[k] = v.to(BF16).contiguous()
+    t[side + ".conv_in.weight"] = sd[side + ".conv_in.weight"].to(dev, F32).permute(0, 2, 3, 1).contiguous()
+    a = side + ".mid_block.attentions.0"
+    t[a + ".qkv"] = torch.cat([t[a + ".to_q.weight"], t[a + ".to_k.weight"], t[a + ".to_v.weight"]]).contiguous()
+    t[a + ".qkv.bias"] = torch.cat([t[a + ".to_q.bias"], t[a + ".to_k.bias"], t[a + ".to_v.bias"]]).contiguous()
+    return t
+
+
+class VAEDecoderPlan(LaunchPlan):
+    """decode(latent[B,4,h,w] fp32) -> image [B,3,8h,8w] fp32 in [0,1].  No weight hints: its launches are recorded with weight=None."""
 
     def __init__(self, cfg, sd, B, h, w, inv_scale, device="cuda"):
+        super().__init__(torch.device(device))
         self.cfg, self.B, self.h, self.w = cfg, B, h, w
-        self.dev = torch.device(device)
-        self.lib = L.load()
-        self.ops, self.keep = [], []
-        self.arena = _Arena(self.dev)
-        self.flops = 0
         dev = self.dev
-        t = {}
-        for k, v in sd.items():
-            v = v.to(dev)
-            if k.endswith(".bias") or "norm" in k:
-                t[k] = v.to(F32).contiguous()
-            elif v.dim() == 4 and v.shape[-1] == 3 and not k.startswith("decoder.conv_in"):
-                t[k] = v.permute(0, 2, 3, 1).to(BF16).contiguous()
-                if ".upsamplers." in k and ops.up2_fold_enabled():
-                    t[k + ".up2f"] = ops.fold_up2_weight(v.permute(0, 2, 3, 1))      # TMIX_CONV_UP2F: four 2x2 phase kernels, folded from the checkpoint's precision
-            elif v.dim() == 4 and v.shape[-1] == 1 and not k.startswith("post_quant"):
-                t[k] = v.reshape(v.shape[0], v.shape[1]).to(BF16).contiguous()
-            elif v.dim() == 2:
-                t[k] = v.to(BF16).contiguous()
-        t["decoder.conv_in.weight"] = sd["decoder.conv_in.weight"].to(dev, F32).permute(0, 2, 3, 1).contiguous()
-        a = "decoder.mid_block.attentions.0"
-        t[a + ".qkv"] = torch.cat([t[a + ".to_q.weight"], t[a + ".to_k.weight"], t[a + ".to_v.weight"]]).contiguous()
-        t[a + ".qkv.bias"] = torch.cat([t[a + ".to_q.bias"], t[a + ".to_k.bias"], t[a + ".to_v.bias"]]).contiguous()
-        self.t = t
+        self.t = kernel_layout_weights(sd, "decoder", dev, fold_up2=ops.up2_fold_enabled())
         # z -> post_quant_conv(z * inv_scale): per-pixel 4x4 map (host floats, passed by value to the kernel)
         pq = sd["post_quant_conv.weight"].float().reshape(4, 4) * float(inv_scale)
         self._pre_w = (C.c_float * 16)(*[float(x) for x in pq.reshape(-1)])
@@ -159,13 +165,10 @@ class VAEDecoderPlan:
         self._gn_ws = ops.groupnorm_ws(B, 4096, cfg["groups"], dev)
         self._build()
 
-    def _emit(self, fn, *a):
-        self.ops.append((fn, a))
-
     def _gn(self, x, Cc, HW, name, silu):
         out = self.arena.get(self.B, HW, Cc)
-        self._emit(self.lib.tmix_groupnorm_nhwc, x.data_ptr(), Cc, None, 0, out.data_ptr(), self.t[name + ".weight"].data_ptr(),
-                   self.t[name + ".bias"].data_ptr(), self._gn_ws.data_ptr(), self.B, HW, self.cfg["groups"], 1e-6, int(silu))
+        self._launch("tmix_groupnorm_nhwc", (x.data_ptr(), Cc, None, 0, out.data_ptr(), self.t[name + ".weight"].data_ptr(),
+                     self.t[name + ".bias"].data_ptr(), self._gn_ws.data_ptr(), self.B, HW, self.cfg["groups"], 1e-6, int(silu)), 0, key=("norm", self.B, HW, Cc))
         return out
 
     def _conv(self, x, name, Hh, Ww, Ci, Co, mode=L.CONV_S1, residual=None):
@@ -176,16 +179,15 @@ class VAEDecoderPlan:
             mode, w, taps = L.CONV_UP2F, self.t[name + ".weight.up2f"], 4
         d = ops.make_conv_desc(x.view(self.B, Hh, Ww, Ci), w, out.view(self.B, Ho, Wo, Co),
                                self.t[name + ".bias"], None, residual, mode)
-        self.keep.append(d)
-        self._emit(self.lib.tmix_conv3x3_nhwc, C.byref(d))
-        self.flops += 2 * self.B * Ho * Wo * Co * taps * Ci          # (the flops performed)
+        self._launch("tmix_conv3x3_nhwc", (C.byref(d),), 2 * self.B * Ho * Wo * Co * taps * Ci, desc=d)          # (the flops performed)
         return out
 
     def _gemm(self, a, w, out, **kw):
-        d = ops.make_gemm_desc(a, w, out, **kw)
-        self.keep.append(d)
-        self._emit(self.lib.tmix_gemm_bf16, C.byref(d))
-        self.flops += 2 * d.M * d.N * d.K * d.batch
+        return self._gemm_desc(ops.make_gemm_desc(a, w, out, **kw))
+
+    def _gemm_desc(self, d):
+        fl = 2 * d.M * d.N * d.K * d.batch
+        self._launch("tmix_gemm_bf16", (C.byref(d),), fl, gemm_flops=fl, desc=d)
         return d
 
     def _resnet(self, x, Ci, Co, Hh, Ww, name):
@@ -222,9 +224,7 @@ class VAEDecoderPlan:
         self.keep += [scores, probs]
         d = ops.make_gemm_desc(qk[:, :, :Cc], qk[:, :, Cc:], None)
         d.C, d.ldc, d.strideC, d.epilogue = scores.data_ptr(), S, S * S, L.EPI_F32OUT
-        self.keep.append(d)
-        self._emit(self.lib.tmix_gemm_bf16, C.byref(d))
-        self.flops += 2 * B * S * S * Cc
+        self._gemm_desc(d)
         self._emit(self.lib.tmix_softmax_rows, scores.data_ptr(), S, probs.data_ptr(), S, B * S, S, Cc ** -0.5)
         ao = A.get(B, S, Cc)
         self._gemm(probs, vt, ao)
@@ -263,13 +263,7 @@ class VAEDecoderPlan:
         self._emit(lib.tmix_conv_out, y.data_ptr(), t["decoder.conv_out.weight"].data_ptr(), t["decoder.conv_out.bias"].data_ptr(),
                    raw.data_ptr(), B, ch[-1], Hh, Ww, cfg["out_channels"])
         self._emit(lib.tmix_affine_clamp, raw.data_ptr(), self.image.data_ptr(), raw.numel(), 0.5, 0.5, 0.0, 1.0)
-
-    def run(self, stream=None):
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        for fn, a in self.ops:
-            rc = fn(*a, st)
-            if rc:
-                L.check(rc, fn.__name__)
+        self._freeze()
 
     def __call__(self, latent):
         self.latent.copy_(latent)
@@ -301,31 +295,10 @@ class VAEEncoderPlan(VAEDecoderPlan):
     decoder; the stride-2 convs pad right / bottom only (`TMIX_CONV_S2A`), conv_in takes the 3 RGB planes in fp32."""
 
     def __init__(self, cfg, sd, B, H, W, device="cuda"):
+        LaunchPlan.__init__(self, torch.device(device))        # (not the decoder's constructor: other weights, other buffers)
         self.cfg, self.B, self.H, self.Wd = cfg, B, H, W
-        self.dev = torch.device(device)
-        self.lib = L.load()
-        self.ops, self.keep = [], []
-        self.arena = _Arena(self.dev)
-        self.flops = 0
         dev = self.dev
-        t = {}
-        for k, v in sd.items():
-            if not k.startswith(("encoder.", "quant_conv")):
-                continue
-            v = v.to(dev)
-            if k.endswith(".bias") or "norm" in k:
-                t[k] = v.to(F32).contiguous()
-            elif v.dim() == 4 and v.shape[-1] == 3 and not k.startswith("encoder.conv_in"):
-                t[k] = v.permute(0, 2, 3, 1).to(BF16).contiguous()
-            elif v.dim() == 4 and v.shape[-1] == 1 and not k.startswith("quant_conv"):
-                t[k] = v.reshape(v.shape[0], v.shape[1]).to(BF16).contiguous()
-            elif v.dim() == 2:
-                t[k] = v.to(BF16).contiguous()
-        t["encoder.conv_in.weight"] = sd["encoder.conv_in.weight"].to(dev, F32).permute(0, 2, 3, 1).contiguous()
-        a = "encoder.mid_block.attentions.0"
-        t[a + ".qkv"] = torch.cat([t[a + ".to_q.weight"], t[a + ".to_k.weight"], t[a + ".to_v.weight"]]).contiguous()
-        t[a + ".qkv.bias"] = torch.cat([t[a + ".to_q.bias"], t[a + ".to_k.bias"], t[a + ".to_v.bias"]]).contiguous()
-        self.t = t
+        self.t = kernel_layout_weights(sd, "encoder", dev)
         lc = cfg["latent_channels"]
         self.qw = sd["quant_conv.weight"].to(dev, F32).reshape(2 * lc, 2 * lc)
         self.qb = sd["quant_conv.bias"].to(dev, F32)
@@ -360,6 +333,7 @@ class VAEEncoderPlan(VAEDecoderPlan):
         A.put(x)
         self._emit(lib.tmix_conv_out, y.data_ptr(), t["encoder.conv_out.weight"].data_ptr(), t["encoder.conv_out.bias"].data_ptr(),
                    self.moments.data_ptr(), B, ci, Hh, Ww, 2 * cfg["latent_channels"])
+        self._freeze()
 
     def __call__(self, image):
         """-> (mean, logvar) after quant_conv (an 8x8 per-pixel map on the 1/8-resolution moments, once per video: tmix_linear_f32 over 256-pixel row blocks --
