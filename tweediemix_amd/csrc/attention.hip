@@ -20,7 +20,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 constexpr int QB = 128;          // query rows per 4-wave workgroup (32 per wave); the 8-wave form covers 256
@@ -82,15 +81,11 @@ __device__ __forceinline__ void store_row_f8(const AttnParams& p, int64_t row, i
             f[k] = (float)(__bf16)v[2 * blk + (k >> 2)][k & 3];
             am = fmaxf(am, fabsf(f[k]));
         }
-        am = xor16_max(am); am = xor32_max(am);
-        const int e = e8m0_for_amax(am);
-        const float inv = exp2_neg_int(e);
-        int q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false); q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, q0, true);
-        int q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, 0, false); q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, q1, true);
+        const MxPacked mx = mx_pack8(f, xor32_max(xor16_max(am)));
         if (ok) {
             unsigned char* dst = p.O8 + row * p.ldo8 + h * 64 + blk * 32 + fg * 4;
-            *(int*)dst = q0; *(int*)(dst + 16) = q1;
-            if (fg == 0) p.Sc[(int64_t)(h * 2 + blk) * p.ldSc + row] = (unsigned char)(e + 127);
+            *(unsigned*)dst = mx.lo; *(unsigned*)(dst + 16) = mx.hi;
+            if (fg == 0) p.Sc[(int64_t)(h * 2 + blk) * p.ldSc + row] = (unsigned char)(mx.e + 127);
         }
     }
 }
@@ -649,7 +644,7 @@ static int attn_entry(const void* Q, int64_t ldq, int64_t strideQ, const void* K
     p.O = (bf16_t*)O; p.ldo = ldo; p.strideO = strideO;
     p.O8 = (unsigned char*)O8; p.ldo8 = ldo8; p.Sc = (unsigned char*)Sc; p.ldSc = ldSc;
     p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.nq = (Sq + QB - 1) / QB;
-    p.scale_log2e = scale * 1.4426950408889634f;
+    p.scale_log2e = scale * LOG2E;
     p.prof = tmix_prof_take(&p.prof_detail);
     if (Skv <= SK_MAX && !tmix_env(TMIX_ENV_ATTN_GENERAL)) {          // short key set: K / V^T resident in registers, no LDS
         p.nq = (Sq + SQW - 1) / SQW;

@@ -11,6 +11,8 @@ typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) short  bf16x8;   // one MFMA A/B fragment (4 VGPR)
 typedef __attribute__((ext_vector_type(4))) float  f32x4;    // 16x16 accumulator fragment
 typedef __attribute__((ext_vector_type(16))) float f32x16;   // 32x32 accumulator fragment
+typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab;  // 8 x bf16: the A / B operand of the bf16 MFMAs, 16 bytes per lane
+constexpr float LOG2E = 1.4426950408889634f;                 // exp(x) = exp2(LOG2E * x): softmax scales are folded into it on the host
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // fp32 -> bf16, round-to-nearest-even, on gfx950's v_cvt_pk_bf16_f32 (one instruction per PAIR; the integer form -- NaN test, rounding
@@ -52,6 +54,41 @@ __device__ __forceinline__ int e8m0_for_amax(float amax) {
 }
 // 2^-e, e in [-127, 127] (e = 127 -- only reachable from non-finite input -- is the denormal 2^-127, not 0: 0 * inf would be NaN bytes)
 __device__ __forceinline__ float exp2_neg_int(int e) { return e >= 127 ? __uint_as_float(0x00400000u) : __uint_as_float((unsigned)(127 - e) << 23); }
+// The MX block step, the ONE copy behind every e4m3 output of the library: a lane's 8 values f (fp32, already rounded to bf16 precision) and amax, the largest
+// magnitude of the block they belong to, give the block's exponent e (stored as e + 127) and two packed e4m3 words, lo = f[0..3], hi = f[4..7]: the bytes a torch
+// MX quantiser makes of the bf16 tensor.  Reducing amax over the block's lanes is the caller's business (a DPP quad, lanes ^ 16 / ^ 32, a whole wave).
+struct MxPacked { unsigned lo, hi; int e; };
+__device__ __forceinline__ MxPacked mx_pack8(const float (&f)[8], float amax) {
+    const int e = e8m0_for_amax(amax);
+    const float inv = exp2_neg_int(e);
+    int q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false); q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, q0, true);
+    int q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, 0, false); q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, q1, true);
+    return {(unsigned)q0, (unsigned)q1, e};
+}
+// maximum over the four lanes of a quad (an MX block of 32 values is often the 8-value vectors of 4 adjacent lanes) on DPP quad_perm moves:
+// two VALU instructions instead of two ds_bpermute round trips
+__device__ __forceinline__ float quad_max(float x) {
+    float y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false));      // lane ^ 1
+    x = fmaxf(x, y);
+    y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, false));            // lane ^ 2
+    return fmaxf(x, y);
+}
+
+// 8 x bf16 (one 16-byte access) <-> 8 x fp32
+__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
+    f[0] = bf2f((bf16_t)(v.x & 0xffff)); f[1] = bf2f((bf16_t)(v.x >> 16));
+    f[2] = bf2f((bf16_t)(v.y & 0xffff)); f[3] = bf2f((bf16_t)(v.y >> 16));
+    f[4] = bf2f((bf16_t)(v.z & 0xffff)); f[5] = bf2f((bf16_t)(v.z >> 16));
+    f[6] = bf2f((bf16_t)(v.w & 0xffff)); f[7] = bf2f((bf16_t)(v.w >> 16));
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+    uint4 v;
+    v.x = pack_bf2(f[0], f[1]); v.y = pack_bf2(f[2], f[3]); v.z = pack_bf2(f[4], f[5]); v.w = pack_bf2(f[6], f[7]);
+    return v;
+}
+__device__ __forceinline__ float silu_fast(float x) {     // x * sigmoid(x) with v_exp_f32 / v_rcp_f32
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * x));
+}
 
 // thread-local error string (host side)
 void tmix_set_error(const char* fmt, ...);

@@ -28,20 +28,10 @@
 namespace tmix_gemm {
 
 constexpr int BK = 64;
-typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab;
 
 static __device__ __forceinline__ float xor32_sum(float x) {      // x + (value of lane ^ 32)
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// maximum over the four lanes of a quad (the MX block of an e4m3 copy is the 4 adjacent lanes of a row) on DPP quad_perm moves:
-// two VALU instructions instead of two ds_bpermute round trips
-static __device__ __forceinline__ float quad_max(float x) {
-    float y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false));      // lane ^ 1
-    x = fmaxf(x, y);
-    y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, false));            // lane ^ 2
-    return fmaxf(x, y);
 }
 
 // DPP move within rows of 16 lanes (CTRL 0x120 + n: row_ror:n -- lane l reads lane (l - n) mod 16 of its row)
@@ -1260,14 +1250,10 @@ gemm_conv_kernel(const Params p) {
 #pragma unroll
                             for (int k = 0; k < 4; ++k) { f[2 * k] = __uint_as_float(u[k] << 16); f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
                                                           am = fmaxf(am, fmaxf(fabsf(f[2 * k]), fabsf(f[2 * k + 1]))); }
-                            am = quad_max(am);
-                            const int e = e8m0_for_amax(am);
-                            const float inv = exp2_neg_int(e);
-                            int q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false); q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, q0, true);
-                            int q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, 0, false); q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, q1, true);
+                            const MxPacked mx = mx_pack8(f, quad_max(am));
                             if (m >= p.M || nb >= p.N) continue;
-                            *(uint2*)((unsigned char*)p.C + (int64_t)bz * p.strideC + (int64_t)m * p.ldc + col) = make_uint2((unsigned)q0, (unsigned)q1);
-                            if ((lane & 3) == 0) p.scale_out[(int64_t)(col >> 5) * p.ldScaleOut + (int64_t)bz * p.M + m] = (unsigned char)(e + 127);
+                            *(uint2*)((unsigned char*)p.C + (int64_t)bz * p.strideC + (int64_t)m * p.ldc + col) = make_uint2(mx.lo, mx.hi);
+                            if ((lane & 3) == 0) p.scale_out[(int64_t)(col >> 5) * p.ldScaleOut + (int64_t)bz * p.M + m] = (unsigned char)(mx.e + 127);
                             continue;
                         }
                     }
@@ -1426,14 +1412,10 @@ gemm_conv_kernel(const Params p) {
 #pragma unroll
                             for (int k = 0; k < 4; ++k) { f[2 * k] = __uint_as_float(u8[k] << 16); f[2 * k + 1] = __uint_as_float(u8[k] & 0xffff0000u);
                                                           am = fmaxf(am, fmaxf(fabsf(f[2 * k]), fabsf(f[2 * k + 1]))); }
-                            am = quad_max(am);
-                            const int e = e8m0_for_amax(am);
-                            const float inv = exp2_neg_int(e);
-                            int q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false); q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, q0, true);
-                            int q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, 0, false); q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, q1, true);
+                            const MxPacked mx = mx_pack8(f, quad_max(am));
                             if (ok) {
-                                *(uint2*)(p.f8copy + ((int64_t)bz * p.M + m) * p.ldF8copy + nc) = make_uint2((unsigned)q0, (unsigned)q1);
-                                if ((lane & 3) == 0) p.scale_out[(int64_t)(nc >> 5) * p.ldScaleOut + (int64_t)bz * p.M + m] = (unsigned char)(e + 127);
+                                *(uint2*)(p.f8copy + ((int64_t)bz * p.M + m) * p.ldF8copy + nc) = make_uint2(mx.lo, mx.hi);
+                                if ((lane & 3) == 0) p.scale_out[(int64_t)(nc >> 5) * p.ldScaleOut + (int64_t)bz * p.M + m] = (unsigned char)(mx.e + 127);
                             }
                         }
                         if constexpr ((FL & 2) != 0) {                  // statistics of the values AS STORED (same order as the generic form)
@@ -1528,13 +1510,9 @@ gemm_conv_kernel(const Params p) {
 #pragma unroll
                             for (int k = 0; k < 4; ++k) { f[2 * k] = __uint_as_float(u8[k] << 16); f[2 * k + 1] = __uint_as_float(u8[k] & 0xffff0000u);
                                                           am = fmaxf(am, fmaxf(fabsf(f[2 * k]), fabsf(f[2 * k + 1]))); }
-                            am = quad_max(am);
-                            const int e = e8m0_for_amax(am);
-                            const float inv = exp2_neg_int(e);
-                            int q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false); q0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, q0, true);
-                            int q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, 0, false); q1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, q1, true);
-                            *(uint2*)(p.f8copy + ((int64_t)bz * p.M + m) * p.ldF8copy + nc) = make_uint2((unsigned)q0, (unsigned)q1);
-                            if ((lane & 3) == 0) p.scale_out[(int64_t)(nc >> 5) * p.ldScaleOut + (int64_t)bz * p.M + m] = (unsigned char)(e + 127);
+                            const MxPacked mx = mx_pack8(f, quad_max(am));
+                            *(uint2*)(p.f8copy + ((int64_t)bz * p.M + m) * p.ldF8copy + nc) = make_uint2(mx.lo, mx.hi);
+                            if ((lane & 3) == 0) p.scale_out[(int64_t)(nc >> 5) * p.ldScaleOut + (int64_t)bz * p.M + m] = (unsigned char)(mx.e + 127);
                         }
                         if (sto) {                                 // statistics of the values AS STORED
                             const unsigned u[4] = {v.x, v.y, v.z, v.w};

@@ -371,7 +371,7 @@ int launch_qattn(Params& p, const QAExtra& x, int batch, hipStream_t st) {
     q.Kc = (const bf16_t*)x.K; q.ldk = x.ldk; q.strideK = x.strideK;
     q.Vt = (const bf16_t*)x.Vt; q.ldvt = x.ldvt; q.strideVt = x.strideVt;
     q.O = (bf16_t*)x.O; q.ldo = x.ldo;
-    q.rows_per_image = x.rows_per_image; q.Skv = x.Skv; q.scale_log2e = x.scale * 1.4426950408889634f;
+    q.rows_per_image = x.rows_per_image; q.Skv = x.Skv; q.scale_log2e = x.scale * LOG2E;
     return launch_tiles<gemm_qattn_kernel>(q.g, q, batch, (Q_NW + Q_LW) * 64, SMEM, Q_LW * 64, st, "gemm_q_cross_attn");
 }
 

@@ -236,7 +236,7 @@ extern "C" int tmix_xattn_token_maps(const void* Q, int64_t ldq, int64_t strideQ
     const dim3 grid((unsigned)((Sq + XM_QT - 1) / XM_QT), (unsigned)n_rows);
     xattn_token_maps_kernel<<<grid, XM_QT * 2 * XM_WAVES, 0, (hipStream_t)stream>>>(
         (const bf16_t*)Q, ldq, strideQ, (const bf16_t*)K, ldk, strideK, maps, H, Sq, Lk, row0, row_step, tp, n_tok, accumulate ? 1 : 0,
-        scale * 1.4426950408889634f);
+        scale * LOG2E);
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
 }
@@ -267,7 +267,7 @@ extern "C" int tmix_xattn_token_maps_long(const void* Q, int64_t ldq, int64_t st
     const auto kern = Lk <= 96 ? xattn_token_maps_long_kernel<3> : (Lk <= 160 ? xattn_token_maps_long_kernel<5> : xattn_token_maps_long_kernel<8>);
     kern<<<grid, XM_QT * 2 * XM_WAVES, 0, (hipStream_t)stream>>>(
         (const bf16_t*)Q, ldq, strideQ, (const bf16_t*)K, ldk, strideK, maps, H, Sq, Lk, row0, row_step, tp, n_tok, accumulate ? 1 : 0,
-        scale * 1.4426950408889634f);
+        scale * LOG2E);
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
 }
