@@ -20,7 +20,9 @@ the loop through the HF hub (checkpoint download) takes local paths here:
   --mask_source attention  masks from the cross-attention maps of the look-ahead instead of the segmentation side-car: no VAE,
                          no second process.  Token positions of every --seg_concepts phrase in --prompt_orig (checkpoint
                          tokenizer), or --mask_token_ids '4+7' ('+' between concepts, ',' between positions of one) where
-                         there is no tokenizer; --attn_mask_threshold, --save_attention_maps (raw maps as .npy).  Each rank
+                         there is no tokenizer; --attn_mask_threshold, --save_attention_maps (raw maps as .npy).
+                         --attn_mask_propagate N (0..3, default 0) pushes the maps N times through the self-attention of the last
+                         look-ahead call before they are thresholded: a response on part of an object spreads over the object.  Each rank
                          writes the masks it used as '<seg_concept>.jpg' into its side-car directory.  --mask_paths and
                          --random_masks still win over it
   --long_prompts         prompts past CLIP's 77 tokens: every prompt row (negative, scene, per-concept) is cut into chunks of 75 tokens at
@@ -104,6 +106,8 @@ def build_parser():
     p.add_argument('--mask_token_ids', type=str, default='',
                    help="token positions per foreground concept, '+' between concepts, ',' within one (e.g. '4+7')")
     p.add_argument('--save_attention_maps', action='store_true')
+    p.add_argument('--attn_mask_propagate', type=int, default=0,
+                   help='--mask_source attention: rounds (0..3) of pushing the token maps through the self-attention before thresholding')
     p.add_argument('--long_prompts', action='store_true',
                    help='chunked prompts: 75-token chunks encoded one by one and concatenated (77 c cross-attention keys, c <= 3)')
     p.add_argument('--synthetic_chunks', type=int, default=1, help='--synthetic with --long_prompts: embeddings of 77 * c keys (c in 1..3)')
@@ -157,7 +161,8 @@ def save_png(img, path):
 def save_attention_outputs(opt, tw, side_dir, seeds):
     """--mask_source attention: the masks this rank used, under the side-car's file names '{side_dir}/{seg_concept}.jpg' (those of
     the last seed of the batch: like the side-car, every mask acquisition overwrites them), and with --save_attention_maps the raw
-    per-level maps of every seed as attention_maps_{seed}_level{l}.npy ([n_tok, h_l, w_l], token order of --mask_token_ids)"""
+    per-level maps of every seed as attention_maps_{seed}_level{l}.npy ([n_tok, h_l, w_l], token order of --mask_token_ids) and, with
+    --attn_mask_propagate, the propagated ones beside them as attention_maps_{seed}_level{l}_prop.npy"""
     import numpy as np
     from PIL import Image
     os.makedirs(side_dir, exist_ok=True)
@@ -171,6 +176,9 @@ def save_attention_outputs(opt, tw, side_dir, seeds):
         for sd_, per in zip(seeds, tw.attention_maps):
             for lvl, m in per.items():
                 np.save(os.path.join(side_dir, f'attention_maps_{sd_}_level{lvl}.npy'), m)
+        for sd_, per in zip(seeds, tw.propagated_maps or []):
+            for lvl, m in per.items():
+                np.save(os.path.join(side_dir, f'attention_maps_{sd_}_level{lvl}_prop.npy'), m)
 
 
 def output_stem(prompt_orig):
@@ -222,6 +230,15 @@ def keep_weight(masks, reroll):
     """[1,1,h,w] weight of the KEPT part from the blend masks [K,1,h,w] (masks.build_masks: foreground masks, then the background):
     1 - min(1, sum of the re-rolled regions' foreground masks)"""
     return (1.0 - masks[list(reroll)].sum(dim=0, keepdim=True).clamp(max=1.0)).contiguous()
+
+
+def check_propagate_args(opt):
+    """--attn_mask_propagate: 0..3 rounds, and only where the masks come from the attention maps (before anything touches the GPU)"""
+    n = opt.attn_mask_propagate
+    if not 0 <= n <= 3:
+        raise SystemExit(f'--attn_mask_propagate {n}: 0..3 rounds through the self-attention')
+    if n and opt.mask_source != 'attention':
+        raise SystemExit(f'--attn_mask_propagate {n} refines the masks of --mask_source attention: it needs that mask source')
 
 
 def check_keep_args(opt):
@@ -367,6 +384,7 @@ def main(argv=None):
     check_long_prompt_args(opt)
     if opt.dtype == 'fp8' and opt.lora_mode == 'lowrank':
         raise SystemExit('--dtype fp8 quantises the merged per-concept projection weights: use --lora_mode merged')
+    check_propagate_args(opt)
     canvas = check_canvas_args(opt)
     keep = check_keep_args(opt)
     from tweediemix_amd import dist as D, launch as LA, masks as M, sampler as S, unet as U, weights as Wt
@@ -429,7 +447,7 @@ def main(argv=None):
         fg = None
     elif opt.mask_source == 'attention':              # in-process masks: the provider below is never called
         fg = None
-        attn = dict(tokens=attention_token_ids(opt, tokenizer), threshold=opt.attn_mask_threshold)
+        attn = dict(tokens=attention_token_ids(opt, tokenizer), threshold=opt.attn_mask_threshold, propagate=opt.attn_mask_propagate)
         if opt.long_prompts and max(p for c in attn['tokens'] for p in c) >= n_keys:
             raise SystemExit(f"--mask_token_ids: positions up to {n_keys - 1} ({n_keys // 77} chunks of 77 keys)")
         side_dir = M.sidecar_layout(opt.output_path, rank, world, local, opt.seg_gpu)[0]

@@ -480,6 +480,25 @@ int tmix_xattn_token_maps_long(const void* Q, int64_t ldq, int64_t strideQ, cons
                                int B, int H, int Sq, int Lk, int row0, int row_step, int n_rows, const int32_t* tokens, int n_tok,
                                int accumulate, float scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Token maps through self-attention (masks.attention_masks with propagate >= 1; no reference counterpart): the row-stochastic attn1
+ * matrix of every head applied to a few fp32 maps and summed over heads.  For the selected batch rows b_i = row0 + i * row_step,
+ * i < n_rows, every map j < n_tok and query pixel s < S:
+ *   dst[i][j][s] (+)= out_scale * sum_h sum_{s' < S} softmax_{s'}( scale * Q[b_i][s][h*64..+64) . K[b_i][s'][h*64..+64) ) * src[i][j][s']
+ *   Q, K bf16 [B][S][ld] (row stride stride*): the attn1 to_q / to_k outputs (two column ranges of one buffer in a plan);
+ *   src, dst fp32 [n_rows][n_tok][S], the layout of UNetPlan.token_maps; they must not overlap.  accumulate != 0 adds to dst, 0
+ *   overwrites.  Head size 64, H heads (ldq, ldk >= H * 64), n_tok in 1..32.
+ * Flash-attention forward whose V is the maps: scores, running max and sum in fp32; the probabilities and src enter the second
+ * product rounded to bf16 (nearest even), the sum that normalises is the fp32 one: |error| <= 2^-7 * |out_scale| * H * max|src|.
+ * Deterministic: one thread owns every output element, heads and waves are added in a fixed order, no atomics, and a row's result
+ * does not depend on the other rows of the batch.  Rows behind S of Q, K, src and dst are neither read nor written.
+ * Q, K, src, dst 8-byte aligned; ldq, strideQ, ldk, strideK multiples of 4.  Errors (before any launch): n_tok outside 1..32,
+ * scale <= 0, a null pointer, overlapping src / dst TMIX_EINVAL; B, H, S < 1, rows outside the batch, ld < H * 64 TMIX_ESHAPE;
+ * alignment TMIX_EALIGN. */
+int tmix_sattn_propagate(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK,
+                         const float* src, float* dst, int B, int H, int S, int row0, int row_step, int n_rows,
+                         int n_tok, int accumulate, float scale, float out_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

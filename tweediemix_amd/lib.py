@@ -124,6 +124,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_int32), C.c_int, C.c_int, f32, vp]),
     "tmix_xattn_token_maps_long": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.POINTER(C.c_int32), C.c_int, C.c_int, f32, vp]),
+    "tmix_sattn_propagate": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, f32, f32, vp]),
 }
 
 _lib = None

@@ -528,6 +528,27 @@ def xattn_token_maps(q, k, tokens, H, Lk=None, rows=(0, 1, None), scale=None, ou
     return out
 
 
+def sattn_propagate(q, k, src, H, rows=(0, 1, None), scale=None, out=None, accumulate=False, out_scale=1.0):
+    """out [n_rows, n_tok, S] fp32 (+)= out_scale * sum over the H heads of softmax(q k^T * scale) @ src: the maps `src`
+    [n_rows, n_tok <= 32, S] fp32 pushed through the self-attention of batch rows row0 + i * row_step (rows = (row0, row_step, n_rows);
+    n_rows None: every row from row0 on).  q, k [B,S,>=H*64] bf16 (row stride free: the two halves of one q/k buffer serve).
+    accumulate adds to `out` instead of overwriting it; `out` must not alias `src`."""
+    _need_cuda(q, k, src)
+    assert q.dtype == BF16 and k.dtype == BF16 and q.stride(2) == 1 and k.stride(2) == 1 and q.shape[:2] == k.shape[:2]
+    B, S = q.shape[0], q.shape[1]
+    row0, step, n = rows
+    n = len(range(row0, B, step)) if n is None else n
+    assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 3 and src.shape[0] == n and src.shape[2] == S
+    if out is None:
+        out = torch.zeros_like(src)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == src.shape
+    scale = 64 ** -0.5 if scale is None else scale
+    L.check(L.load().tmix_sattn_propagate(_p(q), q.stride(1), q.stride(0), _p(k), k.stride(1), k.stride(0), _p(src), _p(out), B, H, S,
+                                          row0, step, n, src.shape[1], int(bool(accumulate)), float(scale), float(out_scale),
+                                          _stream()), "tmix_sattn_propagate")
+    return out
+
+
 def groupnorm_ws(B, C, groups, device):
     return torch.empty(L.load().tmix_groupnorm_ws_floats(B, C, groups), device=device, dtype=torch.float32)
 

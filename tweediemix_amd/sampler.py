@@ -30,7 +30,7 @@ import torch
 from . import lib as L
 from . import ops
 from .schedule import Schedule
-from .unet import KVCache, PlanGroup, TokenMapSpec, UNetPlan, UNetWeights
+from .unet import KVCache, PlanGroup, TokenMapSpec, TokenPropSpec, UNetPlan, UNetWeights
 
 F32 = torch.float32
 
@@ -72,7 +72,9 @@ class Tweediemix:
     attention_masks   None (masks come from mask_provider) or dict(tokens=[[positions of concept 1], ...] (<= 32 in all), threshold=0.5,
                       levels=None, level_weights=None): the masks come from the cross-attention maps of the look-ahead's calls
                       on the scene prompt (a "probe" plan: the "plain" rows plus tmix_xattn_token_maps launches) through
-                      masks.attention_masks; mask_provider is not called.  Needs jumping_steps >= 1.
+                      masks.attention_masks; mask_provider is not called.  Needs jumping_steps >= 1.  propagate=N (0..3, default 0):
+                      the maps are pushed N times through the self-attention of the last look-ahead call (a "propagate" plan: the
+                      "plain" rows plus tmix_sattn_propagate launches, replayed on that call's input) before they are thresholded.
     canvas            None, or dict(height, width, overlap) in pixels (multiples of 8): a WIDE CANVAS sampled as overlapping windows of
                       resolution_h x resolution_w (canvas.window_layout) that share every UNet launch like co-batched seeds and are
                       reconciled after every step (tmix_window_consensus behind the fused step, inside the captured graph).  run_fusion /
@@ -115,6 +117,7 @@ class Tweediemix:
         self.attention_masks = None
         self.attention_maps = None         # after the look-ahead: per seed {level: [n_tok, h_l, w_l]} (raw sums), when attention_masks is set
         self.mask_images = None            # ... and per seed the K-1 uint8 [H, W] masks they gave
+        self.propagated_maps = None        # ... and, with propagate >= 1, per seed {level: [n_tok, h_l, w_l]} after the last round
         if attention_masks is not None:
             am = dict(attention_masks)
             toks = [[int(p) for p in c] for c in am["tokens"]]
@@ -125,8 +128,11 @@ class Tweediemix:
                 raise ValueError(f"attention_masks: {len(flat)} token positions, at most 32 in all")
             if int(config.jumping_steps) < 1:
                 raise ValueError("attention_masks needs the look-ahead (jumping_steps >= 1): its calls are where the maps come from")
+            prop = am.get("propagate", 0)
+            if isinstance(prop, bool) or not isinstance(prop, int) or not 0 <= prop <= 3:
+                raise ValueError(f"attention_masks: propagate={prop!r}, an integer 0..3 (rounds through the self-attention)")
             self.attention_masks = dict(tokens=toks, flat=flat, threshold=float(am.get("threshold", 0.5)),
-                                        levels=am.get("levels"), level_weights=am.get("level_weights"))
+                                        levels=am.get("levels"), level_weights=am.get("level_weights"), propagate=prop)
         self._mask_buf = None
         self.scheduler = Schedule(config.n_timesteps)
         self.skip = self.scheduler.skip
@@ -149,6 +155,8 @@ class Tweediemix:
         self.x_state = torch.zeros(S, 4, self.h, self.w, device=self.device, dtype=F32)
         self.x0_state = torch.zeros_like(self.x_state)
         self._x_backup = torch.zeros_like(self.x_state)
+        # attention_masks with propagate >= 1: the state the last look-ahead call read, which the propagate rounds replay
+        self._x_look = torch.zeros_like(self.x_state) if (self.attention_masks or {}).get("propagate") else None
         self.step_params = torch.zeros(8, device=self.device, dtype=F32)      # {t, sa, s1, sa_next, s1_next, is_last, g, -}
         self._keep = self._keep_bufs = None    # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
         # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it
@@ -262,7 +270,7 @@ class Tweediemix:
             ehs = torch.cat([te[0:1], te[1:2], ts_[1:K]])
             pooled = torch.cat([tp[0:1], tp[1:2], tps[1:K]])
             routed, wsel = False, [0] * (K + 1)
-        elif kind in ("plain", "probe"):
+        elif kind in ("plain", "probe", "propagate"):
             ehs, pooled, routed, wsel = te[0:2], tp[0:2], False, [0, 0]
         else:
             raise ValueError(kind)
@@ -275,6 +283,11 @@ class Tweediemix:
             spec = TokenMapSpec(tuple(am["flat"]), row0=1, row_step=2, n_rows=S, levels=am["levels"])
             return UNetPlan(self.W, B, self.h, self.w, KVCache(self.W, ehs, wsel), pooled, self.add_time_ids.repeat(B, 1),
                             fp8=self.fp8, token_maps=spec)
+        if kind == "propagate":                       # one chain as well; the same rows' maps through every attn1 of the probed levels
+            am = self.attention_masks
+            spec = TokenPropSpec(len(am["flat"]), row0=1, row_step=2, n_rows=S, levels=am["levels"])
+            return UNetPlan(self.W, B, self.h, self.w, KVCache(self.W, ehs, wsel), pooled, self.add_time_ids.repeat(B, 1),
+                            fp8=self.fp8, token_prop=spec)
         if self.n_streams > 1 and B % self.n_streams == 0 and B // self.n_streams >= self.min_rows_per_stream:
             return PlanGroup(self.W, self.h, self.w, ehs, wsel, pooled, self.add_time_ids.repeat(B, 1), routed,
                              self.n_streams, fp8=self.fp8)
@@ -490,11 +503,15 @@ class Tweediemix:
             tt = next_t
             for _ in range(cfg.jumping_steps):
                 a_t = self.alpha(tt)
+                if self._x_look is not None:
+                    self._x_look.copy_(self.x_state)
                 self._run_step(look, L.STEP_PLAIN, tt, a_t, self.alpha(tt - 150))
                 tt = tt - 150
             self.preview_x0 = (self.x0_state if cfg.jumping_steps else self._x_backup_x0()).clone()
             if self.windows is not None:              # the step reconciles x_state only: the estimate is reconciled here, where it is read
                 self.preview_x0 = self._to_canvas(self._consensus(self.preview_x0))
+            if self._x_look is not None:              # after the preview, before the restore: what the rounds write into the state is discarded
+                self._propagate_rounds(tt + 150)
             self.x_state.copy_(self._x_backup)
             if self.attention_masks is not None:
                 m = self._masks_from_attention()
@@ -511,20 +528,38 @@ class Tweediemix:
                                  for i in range(self.n_seeds)]).contiguous()
             self._set_masks(m)
 
+    def _propagate_rounds(self, t):
+        """the token maps pushed propagate times through the self-attention of the last look-ahead call (input _x_look, timestep t): round
+        1 reads the probe plan's maps, round r the result of round r - 1; prop_dst is zeroed before each round.  Moves x_state / x0_state."""
+        prop, probe = self.plan("propagate"), self.plan("probe")
+        for r in range(self.attention_masks["propagate"]):
+            for lvl, dst in prop.prop_dst.items():
+                prop.prop_src[lvl].copy_(probe.token_maps[lvl] if r == 0 else dst)
+                dst.zero_()
+            self.x_state.copy_(self._x_look)
+            self._run_step("propagate", L.STEP_PLAIN, t, self.alpha(t), self.alpha(t - 150))
+
     def _masks_from_attention(self):
-        """[K,1,h,w] (one seed) or [n_seeds,K,1,h,w] from the probe plan's token maps (masks.attention_masks + build_masks)"""
+        """[K,1,h,w] (one seed) or [n_seeds,K,1,h,w] from the probe plan's token maps -- with propagate >= 1 from the propagate plan's
+        result, the raw maps stay in attention_maps -- (masks.attention_masks + build_masks)"""
         from . import masks as M
         am, cfg = self.attention_masks, self.config
         maps = {lvl: m.cpu().numpy() for lvl, m in self.plan("probe").token_maps.items()}
+        pmaps = {lvl: m.cpu().numpy() for lvl, m in self.plan("propagate").prop_dst.items()} if am["propagate"] else None
         n_tok = len(am["flat"])
         idx, k = [], 0
         for c in am["tokens"]:
             idx.append(list(range(k, k + len(c))))
             k += len(c)
         self.attention_maps, self.mask_images, out = [], [], []
+        self.propagated_maps = [] if pmaps is not None else None
         for sd in range(self.n_seeds):
             per = {lvl: m[sd].reshape(n_tok, self.h >> lvl, self.w >> lvl) for lvl, m in maps.items()}
-            imgs = M.attention_masks(per, idx, cfg.resolution_h, cfg.resolution_w, am["threshold"], am["level_weights"])
+            use = per
+            if pmaps is not None:
+                use = {lvl: m[sd].reshape(n_tok, self.h >> lvl, self.w >> lvl) for lvl, m in pmaps.items()}
+                self.propagated_maps.append(use)
+            imgs = M.attention_masks(use, idx, cfg.resolution_h, cfg.resolution_w, am["threshold"], am["level_weights"])
             self.attention_maps.append(per)
             self.mask_images.append(imgs)
             out.append(M.build_masks(imgs, self.h, self.w, self.device))

@@ -378,6 +378,24 @@ class TokenMapSpec:
     levels: tuple | None = None
 
 
+@dataclass
+class TokenPropSpec:
+    """What a propagate plan records (UNetPlan(token_prop=...)): for batch rows row0 + i * row_step, i < n_rows, the n_tok (<= 32) fp32
+    maps in prop_src[level] pushed through every attn1 of the level (tmix_sattn_propagate) and accumulated into prop_dst[level] with
+    weight 1 / (heads * attn1 sites of the level): after one call on a zeroed prop_dst, the mean over heads and modules of P @ src.
+    levels: block indices to propagate on; None = every level that has attention."""
+    n_tok: int
+    row0: int = 1
+    row_step: int = 2
+    n_rows: int = 1
+    levels: tuple | None = None
+
+
+def site_level(pfx: str, nb: int):
+    """the block index (resolution level) of a transformer_sites prefix in a UNet of nb blocks"""
+    return nb - 1 if pfx.startswith("mid") else int(pfx.split(".")[1]) if pfx.startswith("down") else nb - 1 - int(pfx.split(".")[1])
+
+
 def attention_levels(cfg: UNetConfig):
     """block indices whose transformer blocks cross-attend (SDXL: 1 and 2, the 64^2 and 32^2 grids of a 1024^2 image)"""
     return tuple(bi for bi, n in enumerate(cfg.transformer_layers) if n)
@@ -391,14 +409,15 @@ class BlockPlan(LaunchPlan):
     (tests/test_plan_attrs_cpu.py)."""
 
     def __init__(self, W, B: int, h: int, w: int, hints, kv, gn_channels: int, ln_floats: int, *, fp8: bool = False, row_sets=None,
-                 routed: bool = False, lowrank: bool = False, qattn: bool = False, tune_ctx: str = "", token_maps: TokenMapSpec | None = None):
+                 routed: bool = False, lowrank: bool = False, qattn: bool = False, tune_ctx: str = "", token_maps: TokenMapSpec | None = None,
+                 token_prop: TokenPropSpec | None = None):
         """hints: (cap, over) bytes of the weight hints (hint_policy); kv: the cached cross-attention K / V^T (k, vt, Lk, ld);
         gn_channels: widest GroupNorm; ln_floats: size of the LayerNorm row-statistics buffer.
         fp8: the attn1 q/k/v, FF up- and down-projections run as tmix_gemm_fp8 (e4m3 operands, per-row power-of-two scales), the
         convolutions as tmix_conv3x3_nhwc_fp8;  routed: batch row b reads the merged LoRA weight set row_sets[b];  lowrank: the routed
         projections run on SHARED weights over K + 64 input columns instead, and row_sets[b] only decides what tmix_lora_down writes into
         the pad columns of row b (UNetWeights.lora_mode);  qattn: attn2.to_q and the cross-attention behind it as ONE launch where the
-        shapes allow;  tune_ctx: tile-table context ("" / SHARED / ROUTED);  token_maps: a probe plan, see TokenMapSpec."""
+        shapes allow;  tune_ctx: tile-table context ("" / SHARED / ROUTED);  token_maps: a probe plan, see TokenMapSpec;  token_prop: a propagate plan, see TokenPropSpec."""
         super().__init__(W.device, hints)
         self.W, self.cfg, self.B, self.h, self.w, self.kv = W, W.cfg, B, h, w, kv
         env = os.environ.get
@@ -444,6 +463,19 @@ class BlockPlan(LaunchPlan):
             self._tok_arr = ops.token_array(tok)
             for l in lv:
                 self.token_maps[l] = torch.zeros(token_maps.n_rows, len(tok), (h >> l) * (w >> l), device=self.dev, dtype=F32)
+        # propagate plan (token_prop): every attn1 of a chosen level is followed by one tmix_sattn_propagate launch that reads the site's q / k and
+        # prop_src[level] and adds its share of the level's mean into prop_dst[level] (both fp32 [n_rows, n_tok, S_level]).  Without it: nothing changes.
+        self.prop_spec, self.prop_src, self.prop_dst, self._prop_sites = token_prop, {}, {}, {}
+        if token_prop is not None:
+            assert 1 <= token_prop.n_tok <= 32, token_prop
+            lv = attention_levels(self.cfg) if token_prop.levels is None else tuple(token_prop.levels)
+            assert lv and all(l in attention_levels(self.cfg) for l in lv), lv
+            nb = len(self.cfg.block_out_channels)
+            for l in lv:
+                shape = (token_prop.n_rows, token_prop.n_tok, (h >> l) * (w >> l))
+                self.prop_src[l] = torch.zeros(shape, device=self.dev, dtype=F32)
+                self.prop_dst[l] = torch.zeros(shape, device=self.dev, dtype=F32)
+                self._prop_sites[l] = sum(n for pfx, _c, n in transformer_sites(self.cfg) if site_level(pfx, nb) == l)
 
     def refine(self, **kw):
         return refine_group(self, **kw)
@@ -740,6 +772,21 @@ class BlockPlan(LaunchPlan):
                    m.data_ptr(), self.B, H, S, self.kv.Lk, sp.row0, sp.row_step, sp.n_rows, self._tok_arr, m.shape[1], 1,
                    self.cfg.head_dim ** -0.5)
 
+    def _prop_level(self, Hh):
+        """the level a propagate plan works on at an attention site of Hh rows of latent, or None"""
+        if not self.prop_dst:
+            return None
+        lvl = (self.h // Hh).bit_length() - 1
+        return lvl if lvl in self.prop_dst else None
+
+    def _token_prop(self, q, k, H, S, lvl):
+        """one tmix_sattn_propagate launch on the attn1 q / k of this site: prop_dst[lvl] += P @ prop_src[lvl] / (H * sites of the level)"""
+        sp, src, dst = self.prop_spec, self.prop_src[lvl], self.prop_dst[lvl]
+        assert src.shape[2] == S and H * self.cfg.head_dim == q.shape[2] == k.shape[2]
+        self._emit(self.lib.tmix_sattn_propagate, q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
+                   src.data_ptr(), dst.data_ptr(), self.B, H, S, sp.row0, sp.row_step, sp.n_rows, sp.n_tok, 1,
+                   self.cfg.head_dim ** -0.5, 1.0 / (H * self._prop_sites[lvl]))
+
     def _vt_buf(self, Cc, S):
         ld = (S + 7) // 8 * 8
         key = (Cc, ld)
@@ -841,10 +888,11 @@ class BlockPlan(LaunchPlan):
             self._rows_cache[key + suffix] = w[torch.tensor(self.row_sets, device=w.device)].contiguous()
         return self._rows_cache[key + suffix]
 
-    def _attn_out(self, q, k, vt, Skv, a, release, h, S, Cc, st, h8, ao8, pad, lvl=None):
+    def _attn_out(self, q, k, vt, Skv, a, release, h, S, Cc, st, h8, ao8, pad, lvl=None, prop=None):
         """one attention of a transformer block and its out-projection back into the residual stream h: the output goes to the e4m3 copy ao8
         (fp8 plans: the out-projection reads e4m3 operands, no quantiser launch) or to a bf16 buffer (with `pad` columns behind every row
-        for low-rank LoRA); lvl: the probe level whose token maps read q; `release`: the arena tensor q (and k) live in, free once the
+        for low-rank LoRA); lvl: the probe level whose token maps read q; prop: the level
+        whose maps a propagate plan pushes through this (self-)attention; `release`: the arena tensor q (and k) live in, free once the
         attention has read it"""
         B, A = self.B, self.arena
         H = Cc // self.cfg.head_dim
@@ -854,6 +902,8 @@ class BlockPlan(LaunchPlan):
         self._attn(q, k, vt, ao, H, S, Skv, f8_out=ao8)
         if lvl is not None:
             self._token_maps(q, a, H, S, lvl)
+        if prop is not None:
+            self._token_prop(q, k, H, S, prop)
         A.put(release)
         if ao8 is not None:
             self._proj(ao8.q.view(B, S, Cc), a + ".out", h, S, Cc, fp8=True, a8=ao8, **kw)
@@ -889,7 +939,7 @@ class BlockPlan(LaunchPlan):
             # --- self attention; norm1 is folded into the q/k/v projection
             qk = A.get(B, S, 2 * Cc)
             self._proj(h, a1 + ".qkv", qk, S, Cc, ln=st, out_t=vt, n_trans_begin=2 * Cc, fp8=True, a8=h8, a_full=h_full)
-            self._attn_out(qk[:, :, :Cc], qk[:, :, Cc:], vt, S, a1, qk, h, S, Cc, st, h8, ao8, pad)
+            self._attn_out(qk[:, :, :Cc], qk[:, :, Cc:], vt, S, a1, qk, h, S, Cc, st, h8, ao8, pad, prop=self._prop_level(Hh))
             # --- cross attention against the cached K / V^T; norm2 folded into to_q
             # The choice is a function of the IMAGE's shape only, never of the batch (like gn_small_gpw): the one-launch form rounds q and runs its softmax
             # differently from the pair, so a batch-dependent choice would make a co-batched seed differ from its single-seed run.  64 tiles of
@@ -953,7 +1003,8 @@ class UNetPlan(BlockPlan):
 
     def __init__(self, W: UNetWeights, B: int, h: int, w: int, kv: KVCache, pooled: torch.Tensor,
                  time_ids: torch.Tensor, routed: bool = False, autotune: bool = True, row_sets=None,
-                 latent=None, eps=None, shared: bool = False, t_dev=None, fp8: bool = False, token_maps: TokenMapSpec | None = None):
+                 latent=None, eps=None, shared: bool = False, t_dev=None, fp8: bool = False, token_maps: TokenMapSpec | None = None,
+                 token_prop: TokenPropSpec | None = None):
         cfg = W.cfg
         assert kv.B == B
         # LoRA routing: batch row b uses merged weight set row_sets[b] (default: row b of a single seed)
@@ -965,14 +1016,14 @@ class UNetPlan(BlockPlan):
         nb = len(cfg.block_out_channels)
         need = 1                            # the widest LayerNorm site's row statistics
         for pfx, cc, _n in transformer_sites(cfg):
-            lvl = nb - 1 if pfx.startswith("mid") else int(pfx.split(".")[1]) if pfx.startswith("down") else nb - 1 - int(pfx.split(".")[1])
+            lvl = site_level(pfx, nb)
             need = max(need, ((cc + 127) // 128) * B * (h >> lvl) * (w >> lvl) * 2)
         # How much of a LARGE weight tensor a hint names (round 6, profiles/r6_experiments/weight_hint_cap_*.txt): a launch of a single-seed call lasts 20 - 90 us, and
         # touching the 39 MB of a routed q/k/v weight (or FF1's 26 MB) inside it costs the hinting launch more than the hinted one gains -- tensors over 20 MB
         # are named by their first 8 MB there (1 MB ... 12 MB measure the same; 13 MB tensors want all of themselves: capping those loses 0.5 - 1 ms).  The co-batched
         # calls (launches of 0.2 - 1 ms) keep whole-tensor hints.  TMIX_PF_CAP_MB / TMIX_PF_CAP_OVER_MB override (cap 0: whole tensors everywhere).
         super().__init__(W, B, h, w, hint_policy(B, h, w), kv, 4096, need, fp8=fp8, row_sets=row_sets, routed=routed and not lowrank,
-                         lowrank=lowrank, qattn=True, tune_ctx=tune_ctx, token_maps=token_maps)
+                         lowrank=lowrank, qattn=True, tune_ctx=tune_ctx, token_maps=token_maps, token_prop=token_prop)
         dev = self.dev
         # I/O buffers may be views into a larger batch owned by a PlanGroup (row-split execution on several streams)
         self.latent = latent if latent is not None else torch.zeros(B, cfg.in_channels, h, w, device=dev, dtype=F32)
@@ -989,7 +1040,7 @@ class UNetPlan(BlockPlan):
         self._link_ln()
         if autotune:
             self.autotune()
-        for m in self.token_maps.values():      # the tuner ran the forward (map launches included) on its own inputs
+        for m in list(self.token_maps.values()) + list(self.prop_dst.values()):      # the tuner ran the forward (map launches included) on its own inputs
             m.zero_()
 
     # ------------------------------------------------------------------ whole network
