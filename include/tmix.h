@@ -341,6 +341,16 @@ int tmix_conv_out(const void* x_nhwc, const void* w_ohwi, const float* bias, flo
  *   O  [B][Sq][ldo]
  * Rows of K behind Skv and rows of Q behind Sq of a slice may hold any bit pattern, NaN included: key and query indices past the last real row are clamped to
  * it (or not loaded at all) and what they give is masked by selection (the same holds for tmix_gemm_q_cross_attn and tmix_xattn_token_maps).
+ *
+ * scale (all four tmix_attn_fwd* entries): the kernels fold the softmax scale into Q while they form its bf16 MFMA fragments, so no multiply sits
+ * on the score path.  Two forms:
+ *   scale > 0   P = softmax(scale * Q K^T).  Q is multiplied by scale * log2(e) and rounded to bf16 a SECOND time (it arrived rounded once): a
+ *               fresh 2^-9 relative error on every element of Q, i.e. a logit error of about 2^-9 * sqrt(sum_d (q_d k_d)^2) * scale, which
+ *               grows with the logit and is exponentiated by the softmax (unit-Gaussian inputs: invisible; logit std 4: ~1 % of max|O|).
+ *   scale < 0   Q is ALREADY in log2 units -- log2(e) was folded into its producer (weights.q_log2_units: the to_q rows, their bias and
+ *               LayerNorm column sums, before the single cast to bf16) -- and P = softmax2(|scale| * Q K^T), softmax2 = the softmax to base 2.
+ *               |scale| must be a power of two (TMIX_EINVAL otherwise): that product is exact in bf16, so Q stays rounded once.
+ *               The plans launch attn1 of the image UNet and the spatial attn1 of the video UNet with scale = -0.125.
  */
 int tmix_attn_fwd(const void* Q, int64_t ldq, int64_t strideQ, const void* K, int64_t ldk, int64_t strideK,
                   const void* Vt, int64_t ldvt, int64_t strideVt, void* O, int64_t ldo, int64_t strideO,

@@ -106,6 +106,18 @@ def test_argument_errors_are_reported_before_any_launch():
     # round 4 entry points: the e4m3 forms validate before touching the device
     assert l.tmix_attn_fwd_f8(fake, 64, 64, fake, 64, 64, fake, 80, 64 * 80, fake, 64, None, 64, 1, 1, 64, 77, 0.125, None) == lib.EINVAL          # no scale array
     assert l.tmix_attn_fwd_f8(fake, 64, 64, fake, 64, 64, fake, 80, 64 * 80, fake, 32, fake, 64, 1, 1, 64, 77, 0.125, None) == lib.EINVAL          # rows narrower than H * 64
+    # a negative scale says "Q is in log2 units, multiply it by |scale|": only a power of two keeps that product exact in bf16, anything else is refused
+    # by all four entries before the device is touched (a positive scale of any value keeps its meaning and gets past this check)
+    qkv = (fake, 64, 64 * 64, fake, 64, 64 * 77, fake, 80, 64 * 80)
+    shape = (1, 1, 64, 77)
+    for bad in (-0.18, -0.1, -3.0, -1.5 * 2.0 ** -3, -float("inf"), -2.0 ** -70, -1e-45):
+        assert l.tmix_attn_fwd(*qkv, fake, 64, 64 * 64, *shape, bad, None) == lib.EINVAL and b"power of two" in l.tmix_last_error_string(), bad
+        assert l.tmix_attn_fwd_ws(*qkv, fake, 64, 64 * 64, *shape, bad, None, 0, None) == lib.EINVAL and b"power of two" in l.tmix_last_error_string(), bad
+        assert l.tmix_attn_fwd_f8(*qkv, fake, 64, fake, 64, *shape, bad, None) == lib.EINVAL and b"power of two" in l.tmix_last_error_string(), bad
+        assert l.tmix_attn_fwd_f8_ws(*qkv, fake, 64, fake, 64, *shape, bad, None, 0, None) == lib.EINVAL and b"power of two" in l.tmix_last_error_string(), bad
+    # ... and it is checked behind the pointer / shape / alignment rules, which keep their codes whatever the scale says
+    assert l.tmix_attn_fwd(fake, 64, 64 * 64, fake, 64, 64 * 77, fake, 72, 64 * 72, fake, 64, 64 * 64, *shape, -0.3, None) == lib.ESHAPE      # ldvt < Skv rounded up to 8
+    assert l.tmix_attn_fwd(fake, 60, 64 * 64, fake, 64, 64 * 77, fake, 80, 64 * 80, fake, 64, 64 * 64, *shape, -0.3, None) == lib.EALIGN
     cd = lib.ConvDesc()
     cd.X, cd.Wt, cd.Y = 0x1000, 0x2000, 0x3000
     cd.B, cd.H, cd.W, cd.Cin, cd.Cout = 1, 8, 8, 64, 64

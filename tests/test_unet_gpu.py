@@ -14,11 +14,16 @@ def rel_l2(a, b):
     return ((a - b).norm() / b.norm()).item()
 
 
-def make(kind, B, h, w, routed, seed=0, lora_mode="merged", hostile=False):
+def make(kind, B, h, w, routed, seed=0, lora_mode="merged", hostile=False, attn1_gain=None):
+    """attn1_gain = (gq, gk): every attn1's to_q / to_k weight times gq / gk, in the oracle and in the plan alike"""
     from oracle import unet_oracle as UO
     from tweediemix_amd import unet as U, weights as Wt
     cfg = U.TINY
     sd = Wt.synthetic_state_dict(cfg, seed=1234, nontrivial=True, hostile=hostile)
+    if attn1_gain is not None:
+        for name in sd:
+            if name.endswith(".attn1.to_q.weight") or name.endswith(".attn1.to_k.weight"):
+                sd[name] = sd[name] * attn1_gain[name.endswith(".attn1.to_k.weight")]
     K = 3
     con = Wt.synthetic_concepts(cfg, kind, K) if kind != "none" else None
     g = torch.Generator().manual_seed(seed)
@@ -66,6 +71,56 @@ def test_unet_plan_matches_oracle(kind, B, routed, hw):
     # replay is deterministic and allocation-free
     eps2 = plan(x.cuda(), t).float().cpu()
     assert torch.equal(eps, eps2)
+
+
+def _attn1_logit_std_oracle(orc):
+    """orc with a recorder: .logit_std collects, per attn1 call, the std over the keys of the base row's logits (mean over heads and queries)"""
+    class Recording(type(orc)):
+        def _attn(self, x, ehs, name, routed):
+            if ehs is None:
+                H = x.shape[-1] // self.cfg.head_dim
+                q = self._lin(x[:1], name + ".to_q").view(-1, H, self.cfg.head_dim).transpose(0, 1)
+                k = self._lin(x[:1], name + ".to_k").view(-1, H, self.cfg.head_dim).transpose(0, 1)
+                s = q.double() @ k.double().transpose(1, 2) * self.cfg.head_dim ** -0.5
+                self.logit_std.append(float(s.std(dim=-1, unbiased=False).mean()))
+            return super()._attn(x, ehs, name, routed)
+
+    rec = Recording.__new__(Recording)
+    rec.__dict__.update(orc.__dict__)
+    rec.logit_std = []
+    return rec
+
+
+# rel L2 of the tiny UNet's output against the fp32 oracle with attn1 at logit std ~8, LoRA-routed, measured on an MI355X with the same weights:
+#   every attn1 launch in the positive-scale form (Q times scale * log2(e), rounded to bf16 twice; the parent of the log2-unit fold):  ATTN1_STD8_REL_L2_TWICE
+#   to_q in log2 units, launches in the negative-scale form (Q rounded once):                                                         ATTN1_STD8_REL_L2_ONCE
+ATTN1_STD8_GAIN = (4.0, 2.0)
+ATTN1_STD8_REL_L2_TWICE = 0.0036471886560320854
+ATTN1_STD8_REL_L2_ONCE = 0.0036252974532544613
+
+
+def attn1_std8_case():
+    """(rel L2 of the plan against the oracle, the attn1 logit stds the oracle saw)"""
+    orc, plan, x, ehs, pooled, time_ids = make("lora", 4, 16, 16, True, attn1_gain=ATTN1_STD8_GAIN)
+    rec = _attn1_logit_std_oracle(orc)
+    ref = rec.forward(x, 781, ehs, pooled, time_ids, routed=True)
+    eps = plan(x.cuda(), 781).float().cpu()
+    torch.cuda.synchronize()
+    assert torch.isfinite(eps).all()
+    return rel_l2(eps, ref), rec.logit_std
+
+
+def test_attn1_at_logit_std_8_is_no_worse_with_q_in_log2_units():
+    """the log2(e) fold end to end (to_q rows, LayerNorm column sums and bias, the merged LoRA copies of every routed row, the launch's scale): with
+    attn1's to_q / to_k amplified to a logit std of about 8 the plan must be no further from the fp32 oracle than it was with Q rounded twice.  A
+    wrongly wired fold (log2(e) twice, on k, or missing on a LoRA copy) changes every attn1 logit by tens of percent and fails this by orders of
+    magnitude.  Measured: rel L2 3.6472e-3 before the fold (ATTN1_STD8_REL_L2_TWICE, from the commit before it on the same weights), 3.6253e-3 with it
+    (ATTN1_STD8_REL_L2_ONCE); the attn1 logit std of the 17 sites is 6.7 .. 7.7, mean 7.2."""
+    r, stds = attn1_std8_case()
+    mean_std = sum(stds) / len(stds)
+    print(f"attn1 logit std: mean {mean_std:.2f}, sites {min(stds):.2f} .. {max(stds):.2f}; rel_l2 = {r:.4g} (Q rounded twice: {ATTN1_STD8_REL_L2_TWICE})")
+    assert 6.0 <= mean_std <= 11.0, stds
+    assert r <= ATTN1_STD8_REL_L2_TWICE * 1.0, (r, ATTN1_STD8_REL_L2_TWICE)
 
 
 @pytest.mark.parametrize("kind,hw", [("lora", (32, 32)), ("custom", (16, 16))])
@@ -244,8 +299,9 @@ def test_lora_merged_rows():
     for i in range(3):
         for j, nm in enumerate(("q", "k", "v")):
             ref = sd[f"{a1}.to_{nm}.weight"] + con[i][f"{a1}.processor.to_{nm}_lora.up.weight"] @ con[i][f"{a1}.processor.to_{nm}_lora.down.weight"]
+            ref = ref * (Wt.LOG2E if nm == "q" else 1.0)          # attn1's to_q rows are stored in log2 units (weights.q_log2_units), delta included
             torch.testing.assert_close(rows[i + 1, j * Cc:(j + 1) * Cc], ref, rtol=2 ** -7, atol=1e-3)
-    torch.testing.assert_close(rows[0, :Cc], sd[f"{a1}.to_q.weight"], rtol=2 ** -7, atol=1e-3)
+    torch.testing.assert_close(rows[0, :Cc], sd[f"{a1}.to_q.weight"] * Wt.LOG2E, rtol=2 ** -7, atol=1e-3)
 
 
 @pytest.mark.parametrize("scale", [1.0, 0.01])

@@ -631,6 +631,15 @@ static int attn_entry(const void* Q, int64_t ldq, int64_t strideQ, const void* K
         TMIX_FAIL(TMIX_EALIGN, "attn: leading dims / strides must keep 16-byte (Q,K,Vt) / 8-byte (O) alignment");
     if (ldvt < ((Skv + 7) / 8) * 8) TMIX_FAIL(TMIX_ESHAPE, "attn: ldvt=%lld < Skv rounded up to 8", (long long)ldvt);
     if (!aligned16(Q) || !aligned16(K) || !aligned16(Vt) || (((uintptr_t)O) & 7)) TMIX_FAIL(TMIX_EALIGN, "attn: pointer alignment");
+    // the factor the kernels put on Q while they form its fragments.  scale > 0: scale * log2(e), a second bf16 rounding of Q.  scale < 0: Q arrives in log2 units
+    // (log2(e) folded into its producer) and |scale| is a power of two, so the product is exact in bf16 and Q stays rounded once
+    float q_factor = scale * LOG2E;
+    if (scale < 0.f) {
+        int e2 = 0;
+        if (frexpf(-scale, &e2) != 0.5f || e2 < -63 || e2 > 64)
+            TMIX_FAIL(TMIX_EINVAL, "attn: a negative scale (Q in log2 units) must be minus a power of two in [2^-64, 2^63], got %g", (double)scale);
+        q_factor = -scale;
+    }
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_P);
@@ -644,7 +653,7 @@ static int attn_entry(const void* Q, int64_t ldq, int64_t strideQ, const void* K
     p.O = (bf16_t*)O; p.ldo = ldo; p.strideO = strideO;
     p.O8 = (unsigned char*)O8; p.ldo8 = ldo8; p.Sc = (unsigned char*)Sc; p.ldSc = ldSc;
     p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.nq = (Sq + QB - 1) / QB;
-    p.scale_log2e = scale * LOG2E;
+    p.scale_log2e = q_factor;
     p.prof = tmix_prof_take(&p.prof_detail);
     if (Skv <= SK_MAX && !tmix_env(TMIX_ENV_ATTN_GENERAL)) {          // short key set: K / V^T resident in registers, no LDS
         p.nq = (Sq + SQW - 1) / SQW;

@@ -20,7 +20,7 @@ import torch
 from . import lib as L
 from . import ops
 from .unet import BlockPlan, BF16, F32, refine_group, run_chains, SHARED as U_SHARED
-from .weights import fold_layernorm, interleave_geglu
+from .weights import fold_layernorm, interleave_geglu, q_log2_units
 
 
 @dataclass
@@ -106,7 +106,8 @@ class I2VWeights:
         for pfx, _c in t2d:
             tb = pfx + ".transformer_blocks.0"
             a1, a2 = tb + ".attn1", tb + ".attn2"
-            fold(a1 + ".qkv", torch.cat([g(a1 + ".to_q.weight"), g(a1 + ".to_k.weight"), g(a1 + ".to_v.weight")]), tb + ".norm1")
+            # the spatial attn1's to_q in log2 units, as in UNetWeights (BlockPlan._attn launches it with the negative-scale form: Q rounded once)
+            fold(a1 + ".qkv", torch.cat([q_log2_units(g(a1 + ".to_q.weight")), g(a1 + ".to_k.weight").float(), g(a1 + ".to_v.weight").float()]), tb + ".norm1")
             t[a1 + ".out"] = bf(g(a1 + ".to_out.0.weight"))
             fold(a2 + ".q", g(a2 + ".to_q.weight"), tb + ".norm2")
             t[a2 + ".out"] = bf(g(a2 + ".to_out.0.weight"))

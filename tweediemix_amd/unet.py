@@ -28,7 +28,7 @@ import torch
 from . import lib as L
 from . import ops
 from .plan import LaunchPlan, hint_bytes  # noqa: F401  (hint_bytes: part of this module's interface, beside hint_policy)
-from .weights import fold_layernorm, interleave_geglu
+from .weights import LOG2E, fold_layernorm, interleave_geglu, q_log2_units
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -169,10 +169,11 @@ class UNetWeights:
                     rows.append(rows[0])
             return torch.stack(rows)
 
-        def lowrank(key, base, a, whiches, norm=None):
+        def lowrank(key, base, a, whiches, norm=None, q_log2=False):
             """the low-rank form of projection `key` (base weight [N, Kin], already LayerNorm-folded when norm is given): t[key + ".lr"] =
             [W | U | 0] bf16 [N, Kin + 64] and the stacked down matrices D [(1 + K) * P, Kin] (set 0 = base: zeros), P = 4 per fused
-            projection in `whiches`; column Kin + (set * len(whiches) + c) * 4 + r pairs rank r of concept `set`'s projection c."""
+            projection in `whiches`; column Kin + (set * len(whiches) + c) * 4 + r pairs rank r of concept `set`'s projection c.
+            q_log2: the "q" rows of `base` carry log2(e) (q_log2_units), so the q up-projection takes it too."""
             nw, nsets = len(whiches), 1 + len(lora)
             P = 4 * nw
             assert nsets * P <= 64, "low-rank LoRA: (1 + concepts) x 4 x fused projections must fit the 64 pad columns"
@@ -185,7 +186,7 @@ class UNetWeights:
                     kd, ku = f"{a}.processor.to_{which}_lora.down.weight", f"{a}.processor.to_{which}_lora.up.weight"
                     if kd in csd and ku in csd:
                         col = ((si + 1) * nw + c) * 4
-                        U[c * n1:(c + 1) * n1, col:col + 4] = csd[ku].to(dev, F32)
+                        U[c * n1:(c + 1) * n1, col:col + 4] = q_log2_units(csd[ku].to(dev)) if q_log2 and which == "q" else csd[ku].to(dev, F32)
                         Dm[(si + 1) * P + c * 4:(si + 1) * P + c * 4 + 4] = csd[kd].to(dev, F32)
             t[key + ".lr"] = torch.cat([base.to(dev, BF16), U.to(BF16)], dim=1).contiguous()
             if norm is not None:                      # T = LN(x) D^T through the GEMM's folded LayerNorm: see tmix_lora_down
@@ -204,7 +205,9 @@ class UNetWeights:
         for tb, _c in attention_blocks(cfg):
             a1, a2 = tb + ".attn1", tb + ".attn2"
             n1, n2, n3 = tb + ".norm1", tb + ".norm2", tb + ".norm3"
-            fold(a1 + ".qkv", torch.cat([g(a1 + ".to_q.weight"), g(a1 + ".to_k.weight"), g(a1 + ".to_v.weight")]), n1)
+            # attn1's to_q in log2 units (weights.q_log2_units): tmix_attn_fwd* then rounds Q once (BlockPlan._attn, q_log2).  The column sums and the
+            # bias of the folded LayerNorm are derived from the scaled rows, so they carry the factor; k and v are untouched
+            fold(a1 + ".qkv", torch.cat([q_log2_units(g(a1 + ".to_q.weight")), g(a1 + ".to_k.weight").float(), g(a1 + ".to_v.weight").float()]), n1)
             t[a1 + ".out"] = bf(g(a1 + ".to_out.0.weight"))
             fold(a2 + ".q", g(a2 + ".to_q.weight"), n2)
             t[a2 + ".out"] = bf(g(a2 + ".to_out.0.weight"))
@@ -219,12 +222,12 @@ class UNetWeights:
                 mv = merged(g(a2 + ".to_v.weight"), a2, "v")
                 kv_rows = [torch.cat([mk[i], mv[i]]) for i in range(mk.shape[0])]     # attn2 K / V: projected once per call kind (KVCache), merged in fp32
                 if self.lora_mode == "lowrank":
-                    lowrank(a1 + ".qkv", t[a1 + ".qkv"], a1, ("q", "k", "v"), n1)
+                    lowrank(a1 + ".qkv", t[a1 + ".qkv"], a1, ("q", "k", "v"), n1, q_log2=True)
                     lowrank(a1 + ".out", t[a1 + ".out"], a1, ("out",))
                     lowrank(a2 + ".q", t[a2 + ".q"], a2, ("q",), n2)
                     lowrank(a2 + ".out", t[a2 + ".out"], a2, ("out",))
                 else:
-                    fold(a1 + ".qkv_rows", torch.cat([merged(g(a1 + ".to_q.weight"), a1, "q"),
+                    fold(a1 + ".qkv_rows", torch.cat([q_log2_units(merged(g(a1 + ".to_q.weight"), a1, "q")),
                                                       merged(g(a1 + ".to_k.weight"), a1, "k"),
                                                       merged(g(a1 + ".to_v.weight"), a1, "v")], dim=1), n1)
                     t[a1 + ".out_rows"] = bf(merged(g(a1 + ".to_out.0.weight"), a1, "out"))
@@ -738,9 +741,11 @@ class BlockPlan(LaunchPlan):
         self._launch("tmix_gemm_q_cross_attn", (C.byref(d), *args), fl + fla, gemm_flops=fl, desc=d, weight=w, keep=(k, vt, ao))
         return ao
 
-    def _attn(self, q, k, vt, out, H, Sq, Skv, f8_out=None):
+    def _attn(self, q, k, vt, out, H, Sq, Skv, f8_out=None, q_log2=False):
         """f8_out: an ops.F8Copy that receives the output as e4m3 + MX block scales instead of the bf16 tensor `out` (fp8 plans: the out-projection's
-        A operand without a quantiser launch and with half the bytes)"""
+        A operand without a quantiser launch and with half the bytes).  q_log2: q comes from a to_q that carries log2(e) (attn1: weights.q_log2_units),
+        so the launch takes the negative-scale form of tmix_attn_fwd*: Q times a power of two, rounded once"""
+        scale = self.cfg.head_dim ** -0.5
         # TMIX_ATTN_SPLIT: one zeroed workspace per launch shape of this chain (launches of a chain are serial on its stream)
         ws = None
         if self._attn_split:
@@ -753,7 +758,7 @@ class BlockPlan(LaunchPlan):
         else:
             fn, dst = "tmix_attn_fwd_ws", (out.data_ptr(), out.stride(1), out.stride(0))
         args = (q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0), vt.data_ptr(), vt.stride(1), vt.stride(0), *dst,
-                self.B, H, Sq, Skv, self.cfg.head_dim ** -0.5, *((ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)))
+                self.B, H, Sq, Skv, -scale if q_log2 else scale, *((ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)))
         self._launch(fn, args, 4 * self.B * H * Sq * Skv * 64, key=("attn", self.B, H, Sq, Skv), keep=(f8_out,))
         return out
 
@@ -780,12 +785,13 @@ class BlockPlan(LaunchPlan):
         return lvl if lvl in self.prop_dst else None
 
     def _token_prop(self, q, k, H, S, lvl):
-        """one tmix_sattn_propagate launch on the attn1 q / k of this site: prop_dst[lvl] += P @ prop_src[lvl] / (H * sites of the level)"""
+        """one tmix_sattn_propagate launch on the attn1 q / k of this site: prop_dst[lvl] += P @ prop_src[lvl] / (H * sites of the level).
+        attn1's q is in log2 units (weights.q_log2_units); this kernel scales fp32 scores, so it takes scale / log2(e)"""
         sp, src, dst = self.prop_spec, self.prop_src[lvl], self.prop_dst[lvl]
         assert src.shape[2] == S and H * self.cfg.head_dim == q.shape[2] == k.shape[2]
         self._emit(self.lib.tmix_sattn_propagate, q.data_ptr(), q.stride(1), q.stride(0), k.data_ptr(), k.stride(1), k.stride(0),
                    src.data_ptr(), dst.data_ptr(), self.B, H, S, sp.row0, sp.row_step, sp.n_rows, sp.n_tok, 1,
-                   self.cfg.head_dim ** -0.5, 1.0 / (H * self._prop_sites[lvl]))
+                   self.cfg.head_dim ** -0.5 / LOG2E, 1.0 / (H * self._prop_sites[lvl]))
 
     def _vt_buf(self, Cc, S):
         ld = (S + 7) // 8 * 8
@@ -899,7 +905,9 @@ class BlockPlan(LaunchPlan):
         kw = dict(bias=self.W[a + ".to_out.0.bias"], residual=h, stats_out=st, f8_copy=h8)
         ao_full = None if ao8 is not None else A.get(B, S, Cc + pad)
         ao = None if ao8 is not None else ao_full[:, :, :Cc] if pad else ao_full
-        self._attn(q, k, vt, ao, H, S, Skv, f8_out=ao8)
+        q_log2 = a.endswith(".attn1")                # (attn2's to_q is shared with the one-launch form tmix_gemm_q_cross_attn, which scales fp32 values: not folded)
+        assert not (q_log2 and lvl is not None)      # the token-map kernels read attn2's q with the plain scale
+        self._attn(q, k, vt, ao, H, S, Skv, f8_out=ao8, q_log2=q_log2)
         if lvl is not None:
             self._token_maps(q, a, H, S, lvl)
         if prop is not None:

@@ -15,6 +15,16 @@ def interleave_geglu(w: torch.Tensor, b: torch.Tensor | None):
     return w[idx].contiguous(), (None if b is None else b[idx].contiguous())
 
 
+LOG2E = 1.4426950408889634      # exp(x) = exp2(LOG2E * x)
+
+
+def q_log2_units(w: torch.Tensor) -> torch.Tensor:
+    """a to_q weight (or its LoRA up-projection / merged per-concept stack) in fp32 times log2(e), BEFORE its single cast to bf16: the self-attention
+    kernels then read Q in log2 units and multiply it by a power of two only (tmix_attn_fwd with a negative scale), so Q is rounded once.
+    Everything derived from the weight afterwards (folded LayerNorm column sums and bias) carries the factor with it."""
+    return w.float() * LOG2E
+
+
 def fold_layernorm(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: torch.Tensor | None):
     """Linear(LayerNorm(x)) with the norm's affine folded into the Linear (tmix_gemm_desc.ln_*):
     returns (W' = W*gamma as bf16, colsum[n] = sum_k W'[n][k] of the bf16-rounded W', t[n] = W[n]·beta + bias[n]).
