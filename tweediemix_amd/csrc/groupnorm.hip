@@ -27,12 +27,31 @@ __host__ __device__ inline int gn_chunks(int64_t HW) {
 }
 
 // sums (a) and sums of squares (q) of 8 channels over rows r0, r0 + step, ... < r1 of src (ld elements per row): four rows in flight per thread
-// (the loop is latency-bound), added in row order.  I = the caller's row index type: an image of the one-launch form has few rows, and 64-bit
-// row cursors cost that kernel 12 VGPRs.
-template <typename I>
+// (the loop is latency-bound), added in row order.  No fp32 sum runs over more than GN_CHAIN rows: before it would, a and q are flushed into fp64
+// totals (A, Q) and start again from zero; what leaves is the fp64 total rounded ONCE to fp32.  var = E[x^2] - mean^2 loses (mean / std)^2 times
+// the relative error of these sums, and a 512-row fp32 chain -- the VAE decoder's last level at 1024^2, HW * C / 262144 rows per thread of
+// gn_stats_kernel -- cost a group at mean / std = 30 three times the error budget of the whole norm (tests/test_norm_numerics_gpu.py).  A run of
+// at most GN_CHAIN rows never flushes and leaves exactly the fp32 sums it always did (0.0 + a == a).  FLUSH = false: the caller's runs are no
+// longer than GN_CHAIN (gn_small_kernel, by gn_small_gpw; the fp64 totals would cost it 31 VGPRs and three of its seven waves per SIMD).
+// I = the caller's row index type: an image of the one-launch form has few rows, and 64-bit row cursors cost that kernel 12 VGPRs.
+constexpr int GN_CHAIN = 32;
+template <typename I, bool FLUSH>
 __device__ __forceinline__ void gn_accum8(const bf16_t* __restrict__ src, int ld, I r0, int step, I r1, float (&a)[8], float (&q)[8]) {
+    double A[8] = {0, 0, 0, 0, 0, 0, 0, 0}, Q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int n = 0;                                            // rows in a and q since the last flush
+    auto count = [&](int rows) {
+        if constexpr (FLUSH) {
+            if (n + rows > GN_CHAIN) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { A[j] += (double)a[j]; Q[j] += (double)q[j]; a[j] = 0.f; q[j] = 0.f; }
+                n = 0;
+            }
+            n += rows;
+        }
+    };
     I r = r0;
     for (; r + 3 * step < r1; r += 4 * step) {
+        count(4);
         uint4 raw[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) raw[u] = *(const uint4*)(src + (int64_t)(r + u * step) * ld);
@@ -44,9 +63,14 @@ __device__ __forceinline__ void gn_accum8(const bf16_t* __restrict__ src, int ld
         }
     }
     for (; r < r1; r += step) {
+        count(1);
         float f[8]; unpack8(*(const uint4*)(src + (int64_t)r * ld), f);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { a[j] += f[j]; q[j] += f[j] * f[j]; }
+    }
+    if constexpr (FLUSH) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { a[j] = (float)(A[j] + (double)a[j]); q[j] = (float)(Q[j] + (double)q[j]); }
     }
 }
 
@@ -72,7 +96,7 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const bf16_t* __restrict_
     const int64_t p0 = (int64_t)ch * ppc;
     int64_t p1 = p0 + ppc; if (p1 > HW) p1 = HW;
     // fixed vector column per thread so the 8 per-channel sums stay in registers across pixels;
-    // partials land in LDS at [pixel lane][channel] and are reduced in a fixed order (deterministic).
+    // partials land in LDS at [pixel lane][channel] and are reduced in a fixed order (deterministic), in fp64: plane * cpg terms, 60 at 320 channels.
     const int plane = nvec <= 256 ? 256 / nvec : 1;          // pixel lanes per block; plane * C <= 2048
     for (int v0 = 0; v0 < nvec; v0 += 256) {
         const int v = v0 + (nvec <= 256 ? tid % nvec : tid);
@@ -83,18 +107,18 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const bf16_t* __restrict_
             const bf16_t* src; int cs;
             if (c0 < C1) { src = X1 + (int64_t)b * HW * C1 + c0; cs = C1; }
             else         { src = X2 + (int64_t)b * HW * C2 + (c0 - C1); cs = C2; }
-            gn_accum8(src, cs, p0 + pl, plane, p1, a, q);
+            gn_accum8<int64_t, true>(src, cs, p0 + pl, plane, p1, a, q);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { s_sum[pl * C + c0 + j] = a[j]; s_sq[pl * C + c0 + j] = q[j]; }
         }
     }
     __syncthreads();
     if (tid < groups) {
-        float s = 0.f, q = 0.f;
+        double s = 0.0, q = 0.0;
         for (int pl = 0; pl < plane; ++pl)
-            for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { s += s_sum[pl * C + c]; q += s_sq[pl * C + c]; }
+            for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { s += (double)s_sum[pl * C + c]; q += (double)s_sq[pl * C + c]; }
         float* o = ws + (((int64_t)b * chunks + ch) * groups + tid) * 2;
-        o[0] = s; o[1] = q;
+        o[0] = (float)s; o[1] = (float)q;
     }
 }
 
@@ -264,7 +288,7 @@ __global__ void __launch_bounds__(256) gn_small_kernel(const bf16_t* __restrict_
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
     if (active) {
-        gn_accum8(src, ld, slot, rs, HW, s, q);
+        gn_accum8<int, false>(src, ld, slot, rs, HW, s, q);        // <= GN_CHAIN rows: gn_small_gpw
 #pragma unroll
         for (int j = 0; j < 8; ++j) { r_s[slot * cw + v * 8 + j] = s[j]; r_q[slot * cw + v * 8 + j] = q[j]; }
     }
@@ -323,6 +347,8 @@ int gn_small_gpw(int64_t HW, int C, int groups) {
         if (groups % gpw || ((gpw * cpg) & 7)) continue;
         const int cw = gpw * cpg;
         if (cw > GN_SMALL_MAX_CW || HW * cw > GN_SMALL_MAX_ELEMS) return 0;
+        const int rs = 256 / (cw >> 3);                   // row slots of gn_small_kernel: a thread adds every rs-th row in fp32
+        if ((HW + rs - 1) / rs > GN_CHAIN) return 0;      // (36 at most under the limits above, and only at pixel counts such as 1633 .. 1638 x 40 channels)
         return gpw;
     }
     return 0;
