@@ -37,6 +37,17 @@ the loop through the HF hub (checkpoint download) takes local paths here:
   --keep_image FILE      the same with an RGB image of exactly resolution_w x resolution_h: kept is the VAE encoder's mean times the scaling
                          factor (nothing is drawn).  Excludes --keep_latents
   --reroll LIST          the regions sampled anew: '+'-separated --seg_concepts phrases or 0-based indices into them ('a dog', '1', '0+a dog')
+  --mask_feather PX      SOFT REGION MASKS: the blend weights of every mask source (side-car, --mask_source attention, --mask_paths, the
+                         rectangles) come from the distance to each region's border.  PX image pixels (the kernel gets PX / 8 latent
+                         pixels) is the full width of the ramp around the border; --mask_dilate PX grows every region first (negative:
+                         shrinks it); --mask_normalize divides the foreground weights by their sum where regions overlap, so that the
+                         weights are a partition of unity (the reference does not normalise: there the overlap doubles at every fusion
+                         step).  On a canvas the weights are built on the canvas grid.  All defaults (and --mask_feather up to 8 alone) are
+                         today's run bit for bit.  With one of the flags each rank writes the foreground weights it used as
+                         '<seg_concept>_soft.png' (8-bit) into its side-car directory
+  --reroll_feather PX / --reroll_dilate PX  the same for the keep region: they act on the union of the --reroll regions, the kept
+                         weight is 1 - (that union, dilated and feathered).  Where the kept weight is 1 the image still comes back bit for
+                         bit; inside the ramp (0 < weight < 1) it is a blend of the kept image and the new sample and does not
   --canvas_h / --canvas_w  a WIDE CANVAS in pixels (0: the window, i.e. none): the picture is sampled as overlapping windows of
                          resolution_h x resolution_w that share every UNet launch like co-batched seeds and are reconciled after every
                          step; --window_overlap is their minimum overlap in pixels (default: half the smaller window side).  At most 8
@@ -114,6 +125,13 @@ def build_parser():
     p.add_argument('--keep_latents', type=str, default='', help="'.latent.pt' of an earlier run: kept outside the --reroll regions")
     p.add_argument('--keep_image', type=str, default='', help='RGB image of resolution_w x resolution_h: its VAE encoding is kept outside the --reroll regions')
     p.add_argument('--reroll', type=str, default='', help="regions sampled anew: '+'-separated --seg_concepts phrases or 0-based indices into them")
+    p.add_argument('--mask_feather', type=float, default=0.0, help='soft masks: full width in image pixels of the ramp around every region border (>= 0; up to 8 alone: the hard masks)')
+    p.add_argument('--mask_dilate', type=float, default=0.0, help='soft masks: grow every region by this many image pixels before the ramp (negative: shrink)')
+    p.add_argument('--mask_normalize', action='store_true', help='soft masks: where regions overlap, divide the foreground weights by their sum (weights sum to 1 everywhere)')
+    p.add_argument('--reroll_feather', type=float, default=0.0,
+                   help='keep region: ramp width in image pixels around the union of the --reroll regions.  Where the kept weight is 1 the kept image still '
+                        'returns bit for bit; where 0 < weight < 1 it is blended with the new sample and does not')
+    p.add_argument('--reroll_dilate', type=float, default=0.0, help='keep region: grow the union of the --reroll regions by this many image pixels (negative: shrink)')
     p.add_argument('--canvas_h', type=int, default=0, help='canvas height in pixels (0: resolution_h, no canvas)')
     p.add_argument('--canvas_w', type=int, default=0, help='canvas width in pixels (0: resolution_w, no canvas)')
     p.add_argument('--window_overlap', type=int, default=-1, help='minimum overlap of neighbouring windows in pixels (default: half the smaller window side)')
@@ -226,10 +244,15 @@ def parse_reroll(spec, seg_concepts):
     return sorted(out)
 
 
-def keep_weight(masks, reroll):
+def keep_weight(masks, reroll, soft=None):
     """[1,1,h,w] weight of the KEPT part from the blend masks [K,1,h,w] (masks.build_masks: foreground masks, then the background):
-    1 - min(1, sum of the re-rolled regions' foreground masks)"""
-    return (1.0 - masks[list(reroll)].sum(dim=0, keepdim=True).clamp(max=1.0)).contiguous()
+    1 - min(1, sum of the re-rolled regions' foreground masks); with soft = (feather, dilate) in latent pixels that union is dilated and
+    feathered first (masks.soft_region; (0, 0) gives the same bits)"""
+    union = masks[list(reroll)].sum(dim=0, keepdim=True).clamp(max=1.0)
+    if soft is not None:
+        from tweediemix_amd import masks as M
+        union = M.soft_region(union, soft[0], soft[1], device=masks.device)
+    return (1.0 - union).contiguous()
 
 
 def check_propagate_args(opt):
@@ -239,6 +262,43 @@ def check_propagate_args(opt):
         raise SystemExit(f'--attn_mask_propagate {n}: 0..3 rounds through the self-attention')
     if n and opt.mask_source != 'attention':
         raise SystemExit(f'--attn_mask_propagate {n} refines the masks of --mask_source attention: it needs that mask source')
+
+
+def check_soft_args(opt):
+    """(mask_soften dict or None, (feather, dilate) of the keep region in latent pixels or None); refuses bad numbers and --reroll_* flags
+    without a keep region (before anything touches the GPU).  The flags are image pixels, the kernels take latent pixels: / 8."""
+    import math
+    for flag, v in (('--mask_feather', opt.mask_feather), ('--reroll_feather', opt.reroll_feather)):
+        if not (math.isfinite(v) and v >= 0):
+            raise SystemExit(f'{flag} {v}: the width of the ramp in image pixels, a finite number >= 0')
+    for flag, v in (('--mask_dilate', opt.mask_dilate), ('--reroll_dilate', opt.reroll_dilate)):
+        if not math.isfinite(v):
+            raise SystemExit(f'{flag} {v}: a finite number of image pixels (negative shrinks the region)')
+    if (opt.reroll_feather or opt.reroll_dilate) and not (opt.keep_latents or opt.keep_image):
+        raise SystemExit(f'--reroll_feather {opt.reroll_feather} / --reroll_dilate {opt.reroll_dilate} soften the border of a keep region: '
+                         f'they need --keep_latents or --keep_image')
+    soften = None
+    if opt.mask_feather or opt.mask_dilate or opt.mask_normalize:
+        soften = dict(feather=opt.mask_feather / 8.0, dilate=opt.mask_dilate / 8.0, normalize=bool(opt.mask_normalize))
+    reroll = (opt.reroll_feather / 8.0, opt.reroll_dilate / 8.0) if (opt.reroll_feather or opt.reroll_dilate) else None
+    return soften, reroll
+
+
+def save_soft_weights(opt, tw, side_dir):
+    """the soft foreground weights this rank used (those of the last mask set acquired: like the side-car's own files, every acquisition
+    overwrites them) as 8-bit '{side_dir}/{seg_concept}_soft.png', on the grid the masks were built on"""
+    import numpy as np
+    from PIL import Image
+    wts = tw.soft_weights
+    if wts is None:
+        return
+    wts = (wts if wts.dim() == 4 else wts[-1])[:-1, 0].cpu().numpy()
+    os.makedirs(side_dir, exist_ok=True)
+    names = [c for c in opt.seg_concepts.split('+') if c]
+    if len(names) != len(wts):
+        names = [f'concept{i}' for i in range(len(wts))]
+    for name, m in zip(names, wts):
+        Image.fromarray(np.round(m * 255.0).astype(np.uint8)).save(os.path.join(side_dir, name + '_soft.png'))
 
 
 def check_keep_args(opt):
@@ -385,6 +445,7 @@ def main(argv=None):
     if opt.dtype == 'fp8' and opt.lora_mode == 'lowrank':
         raise SystemExit('--dtype fp8 quantises the merged per-concept projection weights: use --lora_mode merged')
     check_propagate_args(opt)
+    soften, reroll_soft = check_soft_args(opt)
     canvas = check_canvas_args(opt)
     keep = check_keep_args(opt)
     from tweediemix_amd import dist as D, launch as LA, masks as M, sampler as S, unet as U, weights as Wt
@@ -492,7 +553,7 @@ def main(argv=None):
 
     tw = S.Tweediemix(opt, W, te, ts, provider, concept_num=K, lora=LORA,
                       strict_reference=strict, use_graphs=not opt.no_graphs, n_seeds=per, n_streams=opt.streams, vae=vae,
-                      fp8=(opt.dtype == 'fp8'), attention_masks=attn,
+                      fp8=(opt.dtype == 'fp8'), attention_masks=attn, mask_soften=soften,
                       **(dict(canvas={k: canvas[k] for k in ('height', 'width', 'overlap')}) if canvas else {}))
     if vae_scaling:                                       # fusion_sampling.py:518 divides by vae.config.scaling_factor
         tw.vae_scaling_factor = float(vae_scaling)
@@ -505,7 +566,7 @@ def main(argv=None):
     if keep is not None:                                  # one kept latent and one weight, shared by every seed of every batch
         keep_x0 = keep['latent'] if keep['latent'] is not None else \
             encode_keep_image(keep['image'], vae, tw.vae_scaling_factor, opt.device, synthetic=opt.synthetic)
-        keep_w = keep_weight(M.build_masks(fg, h, w, opt.device), keep['reroll'])
+        keep_w = keep_weight(M.build_masks(fg, h, w, opt.device), keep['reroll'], reroll_soft)
     lats, imgs = [], []
     for b0 in range(0, len(seeds), per):
         batch = seeds[b0:b0 + per]
@@ -517,6 +578,8 @@ def main(argv=None):
         lats.append(lat_b[:len(batch)])
         if attn is not None:
             save_attention_outputs(opt, tw, side_dir, batch)
+        if soften is not None:
+            save_soft_weights(opt, tw, M.sidecar_layout(opt.output_path, rank, world, local, opt.seg_gpu)[0])
         if vae is not None:                               # fusion_sampling.py:496-528
             imgs.append(tw.decode_final(lat_b)[:len(batch)])
     dev = torch.device(opt.device)

@@ -119,6 +119,23 @@ int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float*
 #define TMIX_MAX_WINDOWS 8
 int tmix_window_consensus(float* x, int groups, int n_win, const int* win_yx, int C, int h, int w, int canvas_h, int canvas_w,
                           const float* weight, void* stream);
+/* SOFT REGION MASKS (no reference counterpart: the reference blends with hard {0, 1} stencils).  Blend weights from the distance to each
+ * region's border, on the grid the masks are built on (DESIGN.md 7g holds the definition).
+ * tmix_mask_edt: exact squared Euclidean distances.  mask [n][h][w] fp32, a pixel is SET where the value is >= 0.5;
+ *   d_set[p]   = min over set pixels q of |p - q|^2 (int32, 0 on set pixels),  d_clear[p] the same towards clear pixels;
+ *   a mask without a set (clear) pixel gives TMIX_EDT_NONE everywhere in d_set (d_clear).  1 <= h, w <= 4096, 1 <= n <= 65535.
+ *   Two launches (columns, then rows through LDS); no workspace, no atomics; integer minima, so independent of order and grid.
+ * tmix_soft_masks: d_set / d_clear [n_sets][K-1][h][w] -> out [n_sets][K][h][w] fp32.  Per pixel and foreground concept k, in fp32, every
+ *   op rounded on its own:   s = d_set == 0 ? -(sqrtf(d_clear) - 0.5f) : sqrtf(d_set) - 0.5f     s' = s - dilate
+ *                            u_k = feather > 0 ? min(max(0.5f - s' / feather, 0), 1) : (s' < 0 ? 1 : 0)
+ *   t = u_1 + ... + u_{K-1} ascending; normalize == 0: w_k = u_k, bg = max(1 - t, 0); normalize != 0: t > 1 ? (w_k = u_k / t, bg = 0) :
+ *   (w_k = u_k, bg = 1 - t).  dilate = 0 with feather <= 1 returns the thresholded mask itself.  feather and dilate in pixels of the grid.
+ * Both: TMIX_EINVAL on a null pointer, on feather < 0 or not finite, on a dilate that is not finite; TMIX_ESHAPE on sizes outside the
+ * ranges above or K < 2.  All checked on the host before any launch; both run on `stream` and are capturable. */
+#define TMIX_EDT_NONE (1 << 30)
+int tmix_mask_edt(const float* mask, int32_t* d_set, int32_t* d_clear, int n, int h, int w, void* stream);
+int tmix_soft_masks(const int32_t* d_set, const int32_t* d_clear, float* out, int n_sets, int K, int h, int w, float feather,
+                    float dilate, int normalize, void* stream);
 
 /* Video sampler (I2VGen-XL loop, BASELINE config #5; replaces video_gen/pipeline_i2vgen_xl.py:699-719):
  *   x [n], v [2n] (uncond rows first), out [n], all of `dtype` (TMIX_F32 / TMIX_F16 / TMIX_BF16); sa = sqrt(alpha(t)) etc. with

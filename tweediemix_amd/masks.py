@@ -5,7 +5,9 @@ segmentation side-car's '<concept>.jpg' (8-bit grey) -> /255 -> threshold 0.5 ->
 latent grid -> masks = [fg_1..fg_{K-1}, clamp(1 - sum fg, 0)].  random_rectangle_masks is the synthetic
 stand-in for the side-car used by the benchmark (run_expand.py:50-51 emits bounding rectangles).  attention_masks is the
 in-process mask source: cross-attention token maps of the look-ahead (UNetPlan token_maps) through the side-car's own
-post-processing (expand_masks).
+post-processing (expand_masks).  soft_masks / soft_region turn the {0, 1} masks of any of these sources into blend weights from the distance
+to each region's border (dilated, feathered, optionally normalised: tmix_mask_edt + tmix_soft_masks); soft_masks_reference
+is their numpy restatement, which the kernels equal bit for bit.
 """
 from __future__ import annotations
 
@@ -32,6 +34,127 @@ def build_masks(fg_sources, h: int, w: int, device="cuda") -> torch.Tensor:
     bg = 1 - torch.sum(fg, dim=0, keepdim=True)
     bg[bg < 0] = 0
     return torch.cat([fg, bg]).contiguous()
+
+
+EDT_NONE = 1 << 30          # TMIX_EDT_NONE (include/tmix.h): squared distance where the mask has no set (clear) pixel at all
+
+
+def _edt_brute(sel):
+    """bool [h,w] -> int32 [h,w]: squared Euclidean distance to the nearest True pixel, by the minimum over all of them (EDT_NONE without one)"""
+    h, w = sel.shape
+    qy, qx = np.nonzero(sel)
+    if qy.size == 0:
+        return np.full((h, w), EDT_NONE, np.int32)
+    out = np.empty((h, w), np.int32)
+    xs = np.arange(w, dtype=np.int64)
+    for y in range(h):                                   # row by row: [w, n_set] at a time
+        out[y] = ((y - qy)[None, :] ** 2 + (xs[:, None] - qx[None, :]) ** 2).min(axis=1)
+    return out
+
+
+def _edt_separable(sel):
+    """the same distances by the two exact passes the kernel makes: along y to the nearest True pixel of the column (capped at 2^14 = none), then
+    min over x' of (x - x')^2 + g[x']^2 along the row.  Integer minima: equal to _edt_brute on every mask (tests/test_soft_masks_cpu.py)."""
+    h, w = sel.shape
+    cap = 1 << 14
+    ys = np.arange(h, dtype=np.int64)
+    g = np.empty((h, w), np.int64)
+    for x in range(w):                                   # column by column: [h, h] at a time
+        g[:, x] = np.where(sel[None, :, x], np.abs(ys[:, None] - ys[None, :]), cap).min(axis=1)
+    g2 = np.where(g >= cap, EDT_NONE, g * g)
+    xs = np.arange(w, dtype=np.int64)
+    dx2 = (xs[:, None] - xs[None, :]) ** 2
+    out = np.empty((h, w), np.int64)
+    for y in range(h):
+        out[y] = (dx2 + g2[y][None, :]).min(axis=1)
+    return np.minimum(out, EDT_NONE).astype(np.int32)
+
+
+def mask_edt_reference(mask, brute=None):
+    """numpy restatement of tmix_mask_edt: mask [..., h, w] (set where >= 0.5) -> (d_set, d_clear) int32 of the same shape.  Brute force up to
+    64 x 64, the separable form above (brute=True / False forces one)."""
+    m = np.asarray(mask, np.float32) >= np.float32(0.5)
+    h, w = m.shape[-2:]
+    if brute is None:
+        brute = h * w <= 64 * 64
+    f = _edt_brute if brute else _edt_separable
+    flat = m.reshape(-1, h, w)
+    d_set = np.stack([f(b) for b in flat]).reshape(m.shape)
+    d_clear = np.stack([f(~b) for b in flat]).reshape(m.shape)
+    return d_set, d_clear
+
+
+def soft_u_reference(d_set, d_clear, feather, dilate):
+    """u of DESIGN.md 7g from the squared distances, every op one fp32 op: signed distance to the border (midway between pixel centres),
+    moved by the dilation, ramped over the feather width"""
+    NF = np.float32
+    f, r = NF(feather), NF(dilate)
+    if not (np.isfinite(f) and f >= 0 and np.isfinite(r)):
+        raise ValueError(f"soft masks: feather={feather} (finite, >= 0) dilate={dilate} (finite)")
+    s = np.where(d_set == 0, -(np.sqrt(d_clear.astype(NF)) - NF(0.5)), np.sqrt(d_set.astype(NF)) - NF(0.5)).astype(NF)
+    sp = (s - r).astype(NF)
+    if f > 0:
+        u = np.minimum(np.maximum((NF(0.5) - (sp / f).astype(NF)).astype(NF), NF(0)), NF(1))
+    else:
+        u = (sp < 0).astype(NF)
+    assert u.dtype == NF
+    return u
+
+
+def soft_weights_reference(d_set, d_clear, feather=0.0, dilate=0.0, normalize=False):
+    """numpy restatement of tmix_soft_masks: squared distances [n,K-1,h,w] int32 -> the K blend weights [n,K,h,w] fp32 (t summed in ascending
+    concept order, every op one fp32 op)"""
+    NF = np.float32
+    u = soft_u_reference(d_set, d_clear, feather, dilate)
+    t = np.zeros(u[:, 0].shape, NF)
+    for k in range(u.shape[1]):
+        t = (t + u[:, k]).astype(NF)
+    if normalize:
+        over = t > 1
+        with np.errstate(divide="ignore", invalid="ignore"):
+            w = np.where(over[:, None], (u / t[:, None]).astype(NF), u)
+        bg = np.where(over, NF(0), (NF(1) - t).astype(NF))
+    else:
+        w, bg = u, np.maximum((NF(1) - t).astype(NF), NF(0))
+    return np.concatenate([w, bg[:, None]], axis=1).astype(NF)
+
+
+def soft_masks_reference(fg, feather=0.0, dilate=0.0, normalize=False, brute=None):
+    """numpy restatement of soft_masks (tmix_mask_edt + tmix_soft_masks), compared with the kernels by equality: fg [K-1,h,w] or [n,K-1,h,w]
+    -> [K,1,h,w] or [n,K,1,h,w] fp32"""
+    fg = np.asarray(fg, np.float32)
+    single = fg.ndim == 3
+    if single:
+        fg = fg[None]
+    d_set, d_clear = mask_edt_reference(fg, brute)
+    out = soft_weights_reference(d_set, d_clear, feather, dilate, normalize)[:, :, None]
+    return out[0] if single else out
+
+
+def soft_masks(fg, feather=0.0, dilate=0.0, normalize=False, device="cuda"):
+    """Soft blend weights of one or several mask sets, through tmix_mask_edt and tmix_soft_masks: fg [K-1,h,w] or [n,K-1,h,w] (tensor or
+    array; thresholded at 0.5 like preprocess_mask) -> [K,1,h,w] or [n,K,1,h,w] fp32 on `device`.  Every foreground region is grown by
+    `dilate` latent pixels (negative: shrunk) and its edge ramped over `feather` latent pixels around the moved border; normalize=True
+    divides the foreground weights by their sum where it exceeds 1, so that the K weights are a partition of unity everywhere.
+    dilate = 0 with feather <= 1 and normalize=False returns build_masks' bits."""
+    from . import ops
+    fg = torch.as_tensor(np.asarray(fg, np.float32) if not torch.is_tensor(fg) else fg).to(device, torch.float32).contiguous()
+    if fg.dim() not in (3, 4) or fg.shape[-3] < 1:
+        raise ValueError(f"soft_masks: fg is {tuple(fg.shape)}, expected [K-1, h, w] or [n, K-1, h, w]")
+    n, km1, h, w = (1,) + tuple(fg.shape) if fg.dim() == 3 else tuple(fg.shape)
+    d_set, d_clear = ops.mask_edt(fg.view(n * km1, h, w))
+    out = ops.soft_masks(d_set.view(n, km1, h, w), d_clear.view(n, km1, h, w), feather, dilate, normalize).unsqueeze(2)
+    return out[0] if fg.dim() == 3 else out
+
+
+def soft_region(region, feather=0.0, dilate=0.0, device="cuda"):
+    """the u of ONE binary region ([..., h, w] with a single map in it, thresholded at 0.5), same shape, fp32 on `device`: what a keep
+    region's weight is made of (1 - soft_region(union of the re-rolled regions))"""
+    region = torch.as_tensor(np.asarray(region, np.float32) if not torch.is_tensor(region) else region)
+    h, w = region.shape[-2:]
+    if region.numel() != h * w:
+        raise ValueError(f"soft_region: one [h, w] map, got {tuple(region.shape)}")
+    return soft_masks(region.reshape(1, h, w), feather, dilate, False, device)[0:1].reshape(region.shape)
 
 
 def random_rectangle_masks(K: int, H: int, W: int, seed: int = 0):

@@ -107,6 +107,37 @@ def window_consensus(x, groups, offsets, canvas_hw, weight=None):
     return x
 
 
+def mask_edt(mask, d_set=None, d_clear=None):
+    """tmix_mask_edt: mask [n, h, w] fp32 (set where >= 0.5) -> (d_set, d_clear) int32 [n, h, w], the exact squared Euclidean distance of
+    every pixel to the nearest set / clear pixel (L.EDT_NONE where the mask has none)."""
+    _need_cuda(mask, d_set, d_clear)
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.dim() == 3, tuple(mask.shape)
+    n, h, w = mask.shape
+    if d_set is None:
+        d_set = torch.empty(n, h, w, dtype=torch.int32, device=mask.device)
+    if d_clear is None:
+        d_clear = torch.empty(n, h, w, dtype=torch.int32, device=mask.device)
+    for d in (d_set, d_clear):
+        assert d.dtype == torch.int32 and d.is_contiguous() and tuple(d.shape) == (n, h, w), tuple(d.shape)
+    L.check(L.load().tmix_mask_edt(_p(mask), _p(d_set), _p(d_clear), n, h, w, _stream()), "tmix_mask_edt")
+    return d_set, d_clear
+
+
+def soft_masks(d_set, d_clear, feather=0.0, dilate=0.0, normalize=False, out=None):
+    """tmix_soft_masks: distances [n_sets, K-1, h, w] int32 (mask_edt) -> blend weights [n_sets, K, h, w] fp32: the K-1 dilated and
+    feathered foreground weights, then the background; feather / dilate in pixels of the grid (include/tmix.h has the formula)."""
+    _need_cuda(d_set, d_clear, out)
+    assert d_set.dtype == torch.int32 and d_set.is_contiguous() and d_set.dim() == 4, tuple(d_set.shape)
+    assert d_clear.dtype == torch.int32 and d_clear.is_contiguous() and d_clear.shape == d_set.shape, tuple(d_clear.shape)
+    n_sets, km1, h, w = d_set.shape
+    if out is None:
+        out = torch.empty(n_sets, km1 + 1, h, w, dtype=torch.float32, device=d_set.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n_sets, km1 + 1, h, w), tuple(out.shape)
+    L.check(L.load().tmix_soft_masks(_p(d_set), _p(d_clear), _p(out), n_sets, km1 + 1, h, w, float(feather), float(dilate),
+                                     int(bool(normalize)), _stream()), "tmix_soft_masks")
+    return out
+
+
 def stats_parts(N, tile_cfg):
     """number of row-statistics partials a GEMM of width N writes with tiling tile_cfg (tmix_gemm_stats_parts)."""
     n = L.load().tmix_gemm_stats_parts(int(N), int(tile_cfg))

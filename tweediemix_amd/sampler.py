@@ -82,11 +82,21 @@ class Tweediemix:
                       gets the assembled preview [1, 4, height / 8, width / 8] and returns [K, 1, height / 8, width / 8], decode_final /
                       decode_latent return [n, 3, height, width].  n_seeds * windows <= 8; not with attention_masks, set_keep or
                       n_streams > 1.  A canvas of the window's size is one window: today's launches and bits.
+    mask_soften       None (the masks of every source are used as they come: no launch, today's bits), or dict(feather=<latent px>,
+                      dilate=<latent px>, normalize=bool): the first K-1 masks of every source -- mask_provider (one call or one per seed),
+                      attention_masks, the canvas's provider -- are thresholded at 0.5 and become blend weights from the distance to each
+                      region's border (masks.soft_masks: tmix_mask_edt + tmix_soft_masks, once per mask acquisition): grown by `dilate`,
+                      ramped over `feather`, and with normalize=True a partition of unity where regions overlap.  On a canvas this
+                      happens on the canvas grid before the masks are cropped, so overlapping windows hold identical weights.
+                      feather <= 1 with dilate = 0 and normalize=False gives the bits of None.  soft_weights holds what the last
+                      acquisition produced ([K,1,H,W] or [n,K,1,H,W] on the grid the masks were built on).  The public `masks` setter stays
+                      raw: what is assigned there is what the fused step reads.
     """
 
     def __init__(self, config, weights: UNetWeights, text_embeds, text_embeds_single, mask_provider,
                  concept_num: int, lora: bool = False, strict_reference: bool = True, use_graphs: bool = False,
-                 n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None):
+                 n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None,
+                 mask_soften=None):
         self.config = config
         self.fp8 = bool(fp8)          # optional: FF / QKV projections on e4m3 operands (tmix_gemm_fp8); default bf16 like the reference's fp16
         self.W = weights
@@ -133,6 +143,17 @@ class Tweediemix:
                 raise ValueError(f"attention_masks: propagate={prop!r}, an integer 0..3 (rounds through the self-attention)")
             self.attention_masks = dict(tokens=toks, flat=flat, threshold=float(am.get("threshold", 0.5)),
                                         levels=am.get("levels"), level_weights=am.get("level_weights"), propagate=prop)
+        self.mask_soften = None
+        self.soft_weights = None           # after a mask acquisition with mask_soften: the weights it produced, on the masks' own grid
+        if mask_soften is not None:
+            import math
+            ms = dict(mask_soften)
+            extra = set(ms) - {"feather", "dilate", "normalize"}
+            f, r = float(ms.get("feather", 0.0)), float(ms.get("dilate", 0.0))
+            if extra or not (math.isfinite(f) and f >= 0.0 and math.isfinite(r)):
+                raise ValueError(f"mask_soften: feather={f} (finite, >= 0) dilate={r} (finite) normalize=bool, in latent pixels"
+                                 + (f"; unknown keys {sorted(extra)}" if extra else ""))
+            self.mask_soften = dict(feather=f, dilate=r, normalize=bool(ms.get("normalize", False)))
         self._mask_buf = None
         self.scheduler = Schedule(config.n_timesteps)
         self.skip = self.scheduler.skip
@@ -322,8 +343,19 @@ class Tweediemix:
             self._mask_buf = torch.empty_like(masks)
         self._mask_buf.copy_(masks)
 
+    def _soften(self, m):
+        """masks of a source ([K,1,H,W] or [n,K,1,H,W], on the grid they were built on) -> the blend weights mask_soften asks for; m itself without it"""
+        if self.mask_soften is None:
+            return m
+        from . import masks as M
+        fg = m[:-1, 0] if m.dim() == 4 else m[:, :-1, 0]
+        self.soft_weights = M.soft_masks(fg, device=self.device, **self.mask_soften)
+        return self.soft_weights
+
     @property
     def masks(self):
+        """the blend weights the fused step reads.  Assigning sets them RAW: mask_soften applies to the masks the sampler acquires itself
+        (mask_provider, attention_masks), not to what is assigned here."""
         return self._mask_buf
 
     @masks.setter
@@ -514,18 +546,19 @@ class Tweediemix:
                 self._propagate_rounds(tt + 150)
             self.x_state.copy_(self._x_backup)
             if self.attention_masks is not None:
-                m = self._masks_from_attention()
+                m = self._soften(self._masks_from_attention())
             elif self.windows is not None:            # one canvas mask set per seed, cropped into one set per window (a crop of a partition is a partition)
                 m = torch.stack([self.mask_provider(self.preview_x0[i:i + 1]).to(self.device, F32) for i in range(self.n_canvas)])
                 if tuple(m.shape[1:]) != (self.concept_num, 1, self.canvas_h, self.canvas_w):
                     raise ValueError(f"canvas masks are {tuple(m.shape[1:])}, expected [{self.concept_num}, 1, {self.canvas_h}, {self.canvas_w}]")
-                m = self._to_windows(m.squeeze(2)).unsqueeze(2)
+                m = self._to_windows(self._soften(m).squeeze(2)).unsqueeze(2)     # softened on the canvas grid: overlapping windows hold identical weights
             elif self.n_seeds == 1:
                 m = self.mask_provider(self.preview_x0).to(self.device, F32).contiguous()
                 assert m.shape[0] == self.concept_num
+                m = self._soften(m)
             else:                                     # one mask set per seed: [n_seeds, K, 1, h, w]
-                m = torch.stack([self.mask_provider(self.preview_x0[i:i + 1]).to(self.device, F32)
-                                 for i in range(self.n_seeds)]).contiguous()
+                m = self._soften(torch.stack([self.mask_provider(self.preview_x0[i:i + 1]).to(self.device, F32)
+                                              for i in range(self.n_seeds)]).contiguous())
             self._set_masks(m)
 
     def _propagate_rounds(self, t):
