@@ -22,7 +22,10 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          tokenizer), or --mask_token_ids '4+7' ('+' between concepts, ',' between positions of one) where
                          there is no tokenizer; --attn_mask_threshold, --save_attention_maps (raw maps as .npy).
                          --attn_mask_propagate N (0..3, default 0) pushes the maps N times through the self-attention of the last
-                         look-ahead call before they are thresholded: a response on part of an object spreads over the object.  Each rank
+                         look-ahead call before they are thresholded: a response on part of an object spreads over the object.
+                         --attn_mask_shape free keeps the object's own outline instead of its bounding rectangle: the largest connected
+                         component of the thresholded score, holes filled (--attn_mask_keep_holes: not), every pixel that several concepts
+                         claim given to the highest score, so the masks of any number of concepts are disjoint.  Each rank
                          writes the masks it used as '<seg_concept>.jpg' into its side-car directory.  --mask_paths and
                          --random_masks still win over it
   --long_prompts         prompts past CLIP's 77 tokens: every prompt row (negative, scene, per-concept) is cut into chunks of 75 tokens at
@@ -119,6 +122,10 @@ def build_parser():
     p.add_argument('--save_attention_maps', action='store_true')
     p.add_argument('--attn_mask_propagate', type=int, default=0,
                    help='--mask_source attention: rounds (0..3) of pushing the token maps through the self-attention before thresholding')
+    p.add_argument('--attn_mask_shape', type=str, default='rect', choices=['rect', 'free'],
+                   help="--mask_source attention: 'rect' the bounding rectangle of every mask (the side-car's rule), 'free' the object's own outline, "
+                        "holes filled, overlaps resolved towards the highest score")
+    p.add_argument('--attn_mask_keep_holes', action='store_true', help='--attn_mask_shape free: do not fill the holes of an outline')
     p.add_argument('--long_prompts', action='store_true',
                    help='chunked prompts: 75-token chunks encoded one by one and concatenated (77 c cross-attention keys, c <= 3)')
     p.add_argument('--synthetic_chunks', type=int, default=1, help='--synthetic with --long_prompts: embeddings of 77 * c keys (c in 1..3)')
@@ -262,6 +269,17 @@ def check_propagate_args(opt):
         raise SystemExit(f'--attn_mask_propagate {n}: 0..3 rounds through the self-attention')
     if n and opt.mask_source != 'attention':
         raise SystemExit(f'--attn_mask_propagate {n} refines the masks of --mask_source attention: it needs that mask source')
+
+
+def check_shape_args(opt):
+    """--attn_mask_shape / --attn_mask_keep_holes: only where the masks come from the attention maps, and holes are kept only in free-form
+    masks (before anything touches the GPU)"""
+    if opt.attn_mask_shape != 'rect' and opt.mask_source != 'attention':
+        raise SystemExit(f'--attn_mask_shape {opt.attn_mask_shape} shapes the masks of --mask_source attention: it needs that mask source')
+    if opt.attn_mask_keep_holes and opt.mask_source != 'attention':
+        raise SystemExit('--attn_mask_keep_holes applies to the masks of --mask_source attention: it needs that mask source')
+    if opt.attn_mask_keep_holes and opt.attn_mask_shape != 'free':
+        raise SystemExit('--attn_mask_keep_holes keeps the holes of free-form masks: it needs --attn_mask_shape free (a rectangle has none)')
 
 
 def check_soft_args(opt):
@@ -445,6 +463,7 @@ def main(argv=None):
     if opt.dtype == 'fp8' and opt.lora_mode == 'lowrank':
         raise SystemExit('--dtype fp8 quantises the merged per-concept projection weights: use --lora_mode merged')
     check_propagate_args(opt)
+    check_shape_args(opt)
     soften, reroll_soft = check_soft_args(opt)
     canvas = check_canvas_args(opt)
     keep = check_keep_args(opt)
@@ -508,7 +527,8 @@ def main(argv=None):
         fg = None
     elif opt.mask_source == 'attention':              # in-process masks: the provider below is never called
         fg = None
-        attn = dict(tokens=attention_token_ids(opt, tokenizer), threshold=opt.attn_mask_threshold, propagate=opt.attn_mask_propagate)
+        attn = dict(tokens=attention_token_ids(opt, tokenizer), threshold=opt.attn_mask_threshold, propagate=opt.attn_mask_propagate,
+                    shape=opt.attn_mask_shape, fill_holes=not opt.attn_mask_keep_holes)
         if opt.long_prompts and max(p for c in attn['tokens'] for p in c) >= n_keys:
             raise SystemExit(f"--mask_token_ids: positions up to {n_keys - 1} ({n_keys // 77} chunks of 77 keys)")
         side_dir = M.sidecar_layout(opt.output_path, rank, world, local, opt.seg_gpu)[0]

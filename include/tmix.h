@@ -136,6 +136,26 @@ int tmix_window_consensus(float* x, int groups, int n_win, const int* win_yx, in
 int tmix_mask_edt(const float* mask, int32_t* d_set, int32_t* d_clear, int n, int h, int w, void* stream);
 int tmix_soft_masks(const int32_t* d_set, const int32_t* d_clear, float* out, int n_sets, int K, int h, int w, float feather,
                     float dilate, int normalize, void* stream);
+/* FREE-FORM ATTENTION MASKS (no reference counterpart: the side-car turns every mask into its bounding rectangle).  Connected components on
+ * the attention grid, 4-connected for set and for clear pixels, pixels in raster order i = y * w + x (DESIGN.md 7h holds the definition).
+ * tmix_mask_label: map [n][h][w] fp32, a pixel is SET where map >= threshold (compared in fp32).  label [n][h][w] int32: for a set pixel
+ *   (invert != 0: for a clear pixel) the smallest raster index of its component, -1 for the pixels of the other kind.
+ * tmix_attn_shapes: score [n_sets][km1][h][w] fp32 -> out [n_sets][km1][h][w] fp32 in {0, 1}.  Per map k: b_k = score_k >= threshold; c_k = the
+ *   component of b_k with the most pixels (equal counts: the smallest label; an empty b_k gives an empty c_k); with TMIX_SHAPE_FILL_HOLES
+ *   f_k = c_k plus every component of the complement OF c_k that has no pixel in row 0, row h-1, column 0 or column w-1 (else f_k = c_k); with
+ *   TMIX_SHAPE_RESOLVE a pixel in several f_k of a set stays only in the k with the largest score there (fp32 >, equal scores: the smallest k;
+ *   nothing is re-labelled afterwards).
+ * One workgroup per map with the labels in LDS (a union-find whose merges only lower labels: every loop is bounded by h * w, no workgroup or
+ * lane waits for another), integer atomics only: results depend on the input alone, not on launch geometry or execution order.  One launch
+ * (tmix_attn_shapes with TMIX_SHAPE_RESOLVE and km1 > 1: two); no workspace.
+ * Both: TMIX_EINVAL on a null pointer, on a threshold that is not finite, on unknown flag bits; TMIX_ESHAPE on h, w, n, n_sets or km1 below 1,
+ * on h * w > TMIX_SHAPE_MAX_PIXELS, on n or n_sets * km1 above 65535.  All checked on the host before any launch; both run on `stream` and
+ * are capturable. */
+#define TMIX_SHAPE_FILL_HOLES 1
+#define TMIX_SHAPE_RESOLVE    2
+#define TMIX_SHAPE_MAX_PIXELS 16384   /* 128 x 128: the attention grid of a 2048^2 image */
+int tmix_mask_label(const float* map, float threshold, int invert, int32_t* label, int n, int h, int w, void* stream);
+int tmix_attn_shapes(const float* score, float* out, int n_sets, int km1, int h, int w, float threshold, int flags, void* stream);
 
 /* Video sampler (I2VGen-XL loop, BASELINE config #5; replaces video_gen/pipeline_i2vgen_xl.py:699-719):
  *   x [n], v [2n] (uncond rows first), out [n], all of `dtype` (TMIX_F32 / TMIX_F16 / TMIX_BF16); sa = sqrt(alpha(t)) etc. with

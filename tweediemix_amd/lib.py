@@ -19,6 +19,7 @@ CONV_S1, CONV_S2, CONV_UP2, CONV_T3, CONV_S2A, CONV_UP2F = 0, 1, 2, 3, 4, 5
 F8_A_BLOCK_SCALES, F8_GEGLU_OUT, F8_COPY_OUT = 1, 2, 4    # tmix_gemm_desc.reserved0 flags (the first two: tmix_gemm_fp8 only)
 MAX_WINDOWS = 8                     # TMIX_MAX_WINDOWS: windows of one canvas (tmix_window_consensus)
 EDT_NONE = 1 << 30                  # TMIX_EDT_NONE: squared distance of a mask without a set (clear) pixel (tmix_mask_edt)
+SHAPE_FILL_HOLES, SHAPE_RESOLVE, SHAPE_MAX_PIXELS = 1, 2, 16384      # TMIX_SHAPE_*: flags and the largest grid of tmix_attn_shapes / tmix_mask_label
 TILE_AUTO, TILE_COUNT = 0, 26     # (csrc/gemm_tilings.h describes every id; what a launch really runs: tmix_gemm_resolve_tile / tmix_conv_resolve_tile)
 TILE_CANDIDATES = (1, 2, 3, 4, 5, 7, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22)          # what the autotuner times by default (16, 17: phase-offset mainloop).  NOT 23: its 16x16x32 MFMAs add up a row's products in another order than the 32x32x16 tilings (which are bit-identical among themselves), so a tuner that picked it for one plan and not for its co-batched twin broke test_two_seeds_co_batched_equal_independent_runs; in situ it is level with 21 anyway.  Nor 24 (256x320 on persistent workgroups, same bits as 14): 5 % ahead hot, 5 % behind in situ
 TILE_EXCLUSIVE = (13, 14, 15, 22, 24)                                  # one workgroup per CU over the whole chip: not beside a sibling chain
@@ -70,6 +71,8 @@ SIGNATURES = {
     "tmix_window_consensus": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "tmix_mask_edt": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "tmix_soft_masks": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, C.c_int, vp]),
+    "tmix_mask_label": (C.c_int, [vp, f32, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "tmix_attn_shapes": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.c_int, vp]),
     "tmix_gemm_bf16": (C.c_int, [C.POINTER(GemmDesc), vp]),
     "tmix_gemm_prefetch_next": (C.c_int, [vp, i64, vp]),
     "tmix_gemm_fp8": (C.c_int, [C.POINTER(GemmDesc), vp, vp, vp]),

@@ -5,7 +5,8 @@ segmentation side-car's '<concept>.jpg' (8-bit grey) -> /255 -> threshold 0.5 ->
 latent grid -> masks = [fg_1..fg_{K-1}, clamp(1 - sum fg, 0)].  random_rectangle_masks is the synthetic
 stand-in for the side-car used by the benchmark (run_expand.py:50-51 emits bounding rectangles).  attention_masks is the
 in-process mask source: cross-attention token maps of the look-ahead (UNetPlan token_maps) through the side-car's own
-post-processing (expand_masks).  soft_masks / soft_region turn the {0, 1} masks of any of these sources into blend weights from the distance
+post-processing (expand_masks), or, with shape="free", as the object's own outline: largest component, holes filled, overlaps resolved towards the
+highest score (tmix_attn_shapes; attn_shapes_reference / mask_label_reference are the numpy restatements the kernels equal).  soft_masks / soft_region turn the {0, 1} masks of any of these sources into blend weights from the distance
 to each region's border (dilated, feathered, optionally normalised: tmix_mask_edt + tmix_soft_masks); soft_masks_reference
 is their numpy restatement, which the kernels equal bit for bit.
 """
@@ -256,16 +257,18 @@ def _upsample_bilinear(m, gh: int, gw: int):
     return r[:, x0] * (1 - fx)[None, :] + r[:, x1] * fx[None, :]
 
 
-def largest_component(mask):
-    """the largest 4-connected component of a bool [h,w] mask (ties: the one reached first in raster order); empty stays empty"""
+def _flood_components(mask):
+    """4-connected components of a bool [h,w] mask by a flood fill from every unlabelled set pixel in raster order: (label int32 [h,w], 1, 2, ...
+    in the order the components are reached and 0 on clear pixels; first = each component's first pixel as a raster index, which is its
+    smallest; size = its pixel count)"""
     mask = np.asarray(mask, bool)
     h, w = mask.shape
     label = np.zeros((h, w), np.int32)
-    best, best_n, n_lab = 0, 0, 0
+    first, size = [], []
     for y0, x0 in zip(*np.nonzero(mask)):
         if label[y0, x0]:
             continue
-        n_lab += 1
+        n_lab = len(first) + 1
         label[y0, x0] = n_lab
         stack, n = [(y0, x0)], 0
         while stack:
@@ -275,23 +278,74 @@ def largest_component(mask):
                 if 0 <= yy < h and 0 <= xx < w and mask[yy, xx] and not label[yy, xx]:
                     label[yy, xx] = n_lab
                     stack.append((yy, xx))
+        first.append(int(y0) * w + int(x0))
+        size.append(n)
+    return label, first, size
+
+
+def largest_component(mask):
+    """the largest 4-connected component of a bool [h,w] mask (ties: the one reached first in raster order); empty stays empty"""
+    mask = np.asarray(mask, bool)
+    label, _, size = _flood_components(mask)
+    best, best_n = 0, 0
+    for i, n in enumerate(size):
         if n > best_n:
-            best, best_n = n_lab, n
+            best, best_n = i + 1, n
     return label == best if best else np.zeros_like(mask)
 
 
-def attention_masks(maps_per_level, tokens_per_concept, H: int, W: int, threshold: float = 0.5, level_weights=None):
-    """Blend masks from cross-attention token maps (the in-process stand-in for the segmentation side-car).
+def mask_label_reference(map, threshold=0.5, invert=False):
+    """numpy restatement of tmix_mask_label: map [..., h, w] -> int32 of the same shape; a pixel is set where fp32(map) >= fp32(threshold);
+    every set pixel (invert: every clear pixel) gets the smallest raster index y * w + x of its 4-connected component, the others -1"""
+    m = np.asarray(map, np.float32) >= np.float32(threshold)
+    if invert:
+        m = ~m
+    h, w = m.shape[-2:]
+    out = np.empty(m.shape, np.int32)
+    for b, o in zip(m.reshape(-1, h, w), out.reshape(-1, h, w)):
+        label, first, _ = _flood_components(b)
+        o[...] = np.array([-1] + first, np.int32)[label]
+    return out
 
-    maps_per_level  {level: [n_tok, h_l, w_l]} (or a sequence of such arrays): one batch row's summed attn2 probabilities on the
-                    token positions (UNetPlan.token_maps of a probe plan, reshaped to the level's grid)
-    tokens_per_concept  K-1 lists of indices into n_tok: which maps belong to foreground concept k
-    level_weights   {level: weight} (or a sequence in the order of maps_per_level); default 1 for every level -- the maps are SUMS
-                    over the level's attn2 modules, so equal weights let every module count once (DESIGN.md)
-    Per concept: mean of its token maps -> bilinear upsampling of every level to the finest level's grid, weighted sum -> min / max
-    normalisation to [0, 1] (a constant map counts as 1 everywhere) -> threshold (>=) -> largest 4-connected component; then the
-    side-car's expand_masks (bounding rectangles, run_expand.py's overlap rule for two concepts) and a nearest upsampling to H x W.
-    Returns K-1 uint8 {0,255} [H,W] arrays: what random_rectangle_masks returns and build_masks consumes."""
+
+def _fill_holes(shape):
+    """bool [h,w] plus its holes: the 4-connected components of its complement without a pixel in the first or last row or column"""
+    shape = np.asarray(shape, bool)
+    label, _, _ = _flood_components(~shape)
+    border = np.unique(np.concatenate([label[0], label[-1], label[:, 0], label[:, -1]]))
+    return shape | ((label > 0) & ~np.isin(label, border))
+
+
+def attn_shapes_reference(score, threshold, fill_holes=True, resolve=True):
+    """numpy restatement of tmix_attn_shapes, compared with the kernels by equality: score [K-1,h,w] or [n_sets,K-1,h,w]
+    (rounded to fp32 here) -> fp32 {0, 1} of the same shape.  Per concept the largest component of fp32(score) >= fp32(threshold)
+    (largest_component's tie rule), with its holes filled (fill_holes); with resolve a pixel that several concepts of a set claim stays
+    with the highest score there (fp32 >, in ascending k: equal scores go to the smallest k)."""
+    score = np.asarray(score, np.float32)
+    if score.ndim not in (3, 4):
+        raise ValueError(f"attn_shapes_reference: score is {score.shape}, expected [K-1, h, w] or [n_sets, K-1, h, w]")
+    sets = score[None] if score.ndim == 3 else score
+    out = np.zeros(sets.shape, np.float32)
+    for s, o in zip(sets, out):
+        f = [largest_component(sk >= np.float32(threshold)) for sk in s]
+        if fill_holes:
+            f = [_fill_holes(c) for c in f]
+        if resolve:
+            owner = np.full(s.shape[1:], -1, np.int64)
+            top = np.zeros(s.shape[1:], np.float32)
+            for k, (c, sk) in enumerate(zip(f, s)):
+                with np.errstate(invalid="ignore"):
+                    take = c & ((owner < 0) | (sk > top))
+                owner[take], top[take] = k, sk[take]
+            f = [c & (owner == k) for k, c in enumerate(f)]
+        o[...] = np.stack(f).astype(np.float32)
+    return out[0] if score.ndim == 3 else out
+
+
+def attention_scores(maps_per_level, tokens_per_concept, level_weights=None):
+    """The per-concept score of attention_masks, fp64 [K-1, gh, gw] on the finest level's grid: mean of the concept's token maps -> bilinear
+    upsampling of every level, weighted sum -> min / max normalisation to [0, 1] (a constant map counts as 1 everywhere).  Arguments as
+    attention_masks."""
     if isinstance(maps_per_level, dict):
         keys = list(maps_per_level)
         maps = [np.asarray(maps_per_level[k], np.float64) for k in keys]
@@ -303,7 +357,7 @@ def attention_masks(maps_per_level, tokens_per_concept, H: int, W: int, threshol
         raise ValueError("attention_masks: no maps, or level weights that do not match the levels")
     gh = max(m.shape[1] for m in maps)
     gw = max(m.shape[2] for m in maps)
-    fg = []
+    score = []
     for toks in tokens_per_concept:
         toks = list(toks)
         if not toks:
@@ -313,12 +367,43 @@ def attention_masks(maps_per_level, tokens_per_concept, H: int, W: int, threshol
             if wt:
                 acc += wt * _upsample_bilinear(m[toks].mean(axis=0), gh, gw)
         lo, hi = acc.min(), acc.max()
-        norm = (acc - lo) / (hi - lo) if hi > lo else np.ones_like(acc)
-        fg.append(largest_component(norm >= threshold))
-    rect = expand_masks(fg)
+        score.append((acc - lo) / (hi - lo) if hi > lo else np.ones_like(acc))
+    return np.stack(score) if score else np.zeros((0, gh, gw), np.float64)
+
+
+def attention_masks(maps_per_level, tokens_per_concept, H: int, W: int, threshold: float = 0.5, level_weights=None, shape="rect",
+                    fill_holes=True, device=None):
+    """Blend masks from cross-attention token maps (the in-process stand-in for the segmentation side-car).
+
+    maps_per_level  {level: [n_tok, h_l, w_l]} (or a sequence of such arrays): one batch row's summed attn2 probabilities on the
+                    token positions (UNetPlan.token_maps of a probe plan, reshaped to the level's grid)
+    tokens_per_concept  K-1 lists of indices into n_tok: which maps belong to foreground concept k
+    level_weights   {level: weight} (or a sequence in the order of maps_per_level); default 1 for every level -- the maps are SUMS
+                    over the level's attn2 modules, so equal weights let every module count once (DESIGN.md)
+    Per concept: mean of its token maps -> bilinear upsampling of every level to the finest level's grid, weighted sum -> min / max
+    normalisation to [0, 1] (a constant map counts as 1 everywhere): attention_scores.  Then
+    shape="rect"  threshold (>=, in fp64) -> largest 4-connected component -> the side-car's expand_masks (bounding rectangles,
+                  run_expand.py's overlap rule for two concepts);
+    shape="free"  the score rounded once to fp32 -> threshold (>=, in fp32) -> largest 4-connected component -> its holes filled
+                  (fill_holes) -> every pixel that several concepts claim goes to the highest score there: the object's own outline, disjoint
+                  for any K.  On a GPU `device` through ops.attn_shapes, with device=None or a CPU device through its numpy
+                  restatement attn_shapes_reference; the two are equal;
+    and a nearest upsampling to H x W.  Returns K-1 uint8 {0,255} [H,W] arrays: what random_rectangle_masks returns and build_masks consumes."""
+    if shape not in ("rect", "free"):
+        raise ValueError(f"attention_masks: shape={shape!r}: 'rect' or 'free'")
+    score = attention_scores(maps_per_level, tokens_per_concept, level_weights)
+    gh, gw = score.shape[1:]
+    if shape == "rect":
+        out = expand_masks([largest_component(s >= threshold) for s in score])
+    elif device is not None and torch.device(device).type != "cpu":
+        from . import ops
+        s32 = torch.from_numpy(score.astype(np.float32)[None]).to(device)
+        out = list(ops.attn_shapes(s32, threshold, fill_holes, True)[0].cpu().numpy() != 0)
+    else:
+        out = list(attn_shapes_reference(score.astype(np.float32), threshold, fill_holes, True) != 0)
     ys = np.minimum((np.arange(H) * gh) // H, gh - 1)
     xs = np.minimum((np.arange(W) * gw) // W, gw - 1)
-    return [np.ascontiguousarray(r[ys][:, xs]).astype(np.uint8) * 255 for r in rect]
+    return [np.ascontiguousarray(r[ys][:, xs]).astype(np.uint8) * 255 for r in out]
 
 
 def sidecar_layout(output_path, rank: int, world: int, local_gpu: int, seg_gpu: int):

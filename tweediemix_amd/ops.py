@@ -138,6 +138,34 @@ def soft_masks(d_set, d_clear, feather=0.0, dilate=0.0, normalize=False, out=Non
     return out
 
 
+def mask_label(map, threshold=0.5, invert=False, out=None):
+    """tmix_mask_label: map [n, h, w] fp32 -> int32 [n, h, w]: for every set pixel (map >= threshold; invert=True: every clear pixel) the
+    smallest raster index of its 4-connected component, -1 for the pixels of the other kind.  h * w <= L.SHAPE_MAX_PIXELS."""
+    _need_cuda(map, out)
+    assert map.dtype == torch.float32 and map.is_contiguous() and map.dim() == 3, tuple(map.shape)
+    n, h, w = map.shape
+    if out is None:
+        out = torch.empty(n, h, w, dtype=torch.int32, device=map.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (n, h, w), tuple(out.shape)
+    L.check(L.load().tmix_mask_label(_p(map), float(threshold), int(bool(invert)), _p(out), n, h, w, _stream()), "tmix_mask_label")
+    return out
+
+
+def attn_shapes(score, threshold, fill_holes=True, resolve=True, out=None):
+    """tmix_attn_shapes: score [n_sets, K-1, h, w] fp32 -> the free-form masks [n_sets, K-1, h, w] fp32 in {0, 1}: per concept the largest
+    4-connected component of score >= threshold, with its holes filled (fill_holes) and, within a set, every pixel that several concepts
+    claim left to the one with the highest score there (resolve).  include/tmix.h has the definition."""
+    _need_cuda(score, out)
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.dim() == 4, tuple(score.shape)
+    n_sets, km1, h, w = score.shape
+    if out is None:
+        out = torch.empty(n_sets, km1, h, w, dtype=torch.float32, device=score.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n_sets, km1, h, w), tuple(out.shape)
+    flags = (L.SHAPE_FILL_HOLES if fill_holes else 0) | (L.SHAPE_RESOLVE if resolve else 0)
+    L.check(L.load().tmix_attn_shapes(_p(score), _p(out), n_sets, km1, h, w, float(threshold), flags, _stream()), "tmix_attn_shapes")
+    return out
+
+
 def stats_parts(N, tile_cfg):
     """number of row-statistics partials a GEMM of width N writes with tiling tile_cfg (tmix_gemm_stats_parts)."""
     n = L.load().tmix_gemm_stats_parts(int(N), int(tile_cfg))

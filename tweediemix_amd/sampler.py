@@ -75,6 +75,9 @@ class Tweediemix:
                       masks.attention_masks; mask_provider is not called.  Needs jumping_steps >= 1.  propagate=N (0..3, default 0):
                       the maps are pushed N times through the self-attention of the last look-ahead call (a "propagate" plan: the
                       "plain" rows plus tmix_sattn_propagate launches, replayed on that call's input) before they are thresholded.
+                      shape="rect" (default: every mask becomes its bounding rectangle, the side-car's rule) or "free": the largest
+                      component's own outline, holes filled (fill_holes=True), overlaps of any number of concepts resolved towards the
+                      highest score (tmix_attn_shapes, once per seed), so that the foreground masks are disjoint.
     canvas            None, or dict(height, width, overlap) in pixels (multiples of 8): a WIDE CANVAS sampled as overlapping windows of
                       resolution_h x resolution_w (canvas.window_layout) that share every UNet launch like co-batched seeds and are
                       reconciled after every step (tmix_window_consensus behind the fused step, inside the captured graph).  run_fusion /
@@ -141,8 +144,12 @@ class Tweediemix:
             prop = am.get("propagate", 0)
             if isinstance(prop, bool) or not isinstance(prop, int) or not 0 <= prop <= 3:
                 raise ValueError(f"attention_masks: propagate={prop!r}, an integer 0..3 (rounds through the self-attention)")
+            shape = am.get("shape", "rect")
+            if shape not in ("rect", "free"):
+                raise ValueError(f"attention_masks: shape={shape!r}: 'rect' (bounding rectangles) or 'free' (the component's own outline)")
             self.attention_masks = dict(tokens=toks, flat=flat, threshold=float(am.get("threshold", 0.5)),
-                                        levels=am.get("levels"), level_weights=am.get("level_weights"), propagate=prop)
+                                        levels=am.get("levels"), level_weights=am.get("level_weights"), propagate=prop,
+                                        shape=shape, fill_holes=bool(am.get("fill_holes", True)))
         self.mask_soften = None
         self.soft_weights = None           # after a mask acquisition with mask_soften: the weights it produced, on the masks' own grid
         if mask_soften is not None:
@@ -592,7 +599,8 @@ class Tweediemix:
             if pmaps is not None:
                 use = {lvl: m[sd].reshape(n_tok, self.h >> lvl, self.w >> lvl) for lvl, m in pmaps.items()}
                 self.propagated_maps.append(use)
-            imgs = M.attention_masks(use, idx, cfg.resolution_h, cfg.resolution_w, am["threshold"], am["level_weights"])
+            imgs = M.attention_masks(use, idx, cfg.resolution_h, cfg.resolution_w, am["threshold"], am["level_weights"],
+                                     shape=am["shape"], fill_holes=am["fill_holes"], device=self.device)
             self.attention_maps.append(per)
             self.mask_images.append(imgs)
             out.append(M.build_masks(imgs, self.h, self.w, self.device))
