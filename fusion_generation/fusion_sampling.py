@@ -56,6 +56,11 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          step; --window_overlap is their minimum overlap in pixels (default: half the smaller window side).  At most 8
                          windows; masks (--mask_paths, --random_masks, the synthetic rectangles) are built on the canvas grid, the
                          '.latent.pt' and '.png' are canvas-sized.  Not with --keep_*, --mask_source attention or --streams 2
+  --solver dpmpp2m       every trajectory step behind the first timestep is a DPM-Solver++(2M) step on the blended Tweedie estimate (second
+                         order from the second step of a phase on; no extra UNet call); --timestep_spacing logsnr places
+                         the n_timesteps uniformly in log-SNR between the 'leading' grid's first timestep and t = 1, the fusion window
+                         keeping its noise range.  Meant for a small --n_timesteps (10 .. 20); the defaults (ddim, leading) are today's
+                         run bit for bit.  --solver dpmpp2m does not combine with --keep_latents / --keep_image
   --num_seeds N          N trajectories, seeds seed..seed+N-1 (trajectory i is exactly what `--seed seed+i` alone produces: its
                          x_T comes from its own generator), co-batched --seeds_per_batch at a time
   --gpus G               shard those seeds round-robin over G GPUs of this node: the script starts one process per GPU itself
@@ -142,6 +147,10 @@ def build_parser():
     p.add_argument('--canvas_h', type=int, default=0, help='canvas height in pixels (0: resolution_h, no canvas)')
     p.add_argument('--canvas_w', type=int, default=0, help='canvas width in pixels (0: resolution_w, no canvas)')
     p.add_argument('--window_overlap', type=int, default=-1, help='minimum overlap of neighbouring windows in pixels (default: half the smaller window side)')
+    p.add_argument('--solver', type=str, default='ddim', choices=['ddim', 'dpmpp2m'],
+                   help='dpmpp2m: second-order multistep steps on the blended Tweedie estimate behind the first timestep (ddim: the reference\'s steps)')
+    p.add_argument('--timestep_spacing', type=str, default='leading', choices=['leading', 'logsnr'],
+                   help="logsnr: n_timesteps uniform in log-SNR from the 'leading' grid's first timestep down to t = 1")
     p.add_argument('--num_seeds', type=int, default=1, help='trajectories to sample: seeds seed..seed+n-1')
     p.add_argument('--seeds_per_batch', type=int, default=0, help='seeds co-batched into every UNet launch (0: all of this rank\'s seeds, at most 4)')
     p.add_argument('--gpus', type=int, default=1, help='shard the seeds over this many GPUs (one process per GPU, started by this script)')
@@ -319,6 +328,19 @@ def save_soft_weights(opt, tw, side_dir):
         Image.fromarray(np.round(m * 255.0).astype(np.uint8)).save(os.path.join(side_dir, name + '_soft.png'))
 
 
+def check_solver_args(opt):
+    """--solver / --timestep_spacing: refuses what the sampler would refuse, before anything touches the GPU"""
+    if opt.solver != 'ddim' and (opt.keep_latents or opt.keep_image):
+        flag = '--keep_latents' if opt.keep_latents else '--keep_image'
+        raise SystemExit(f'--solver {opt.solver} does not combine with {flag}: the keep region exists on the --solver ddim step only')
+    if opt.timestep_spacing == 'logsnr':
+        from tweediemix_amd.schedule import Schedule
+        try:
+            Schedule(opt.n_timesteps, spacing='logsnr')
+        except ValueError as e:
+            raise SystemExit(f'--timestep_spacing logsnr with --n_timesteps {opt.n_timesteps}: {e}')
+
+
 def check_keep_args(opt):
     """None for a run without a keep region, else dict(reroll=[indices], latent=[1,4,h,w] or None, image=PIL RGB or None); refuses what
     such a run cannot do (before anything touches the GPU)."""
@@ -467,6 +489,7 @@ def main(argv=None):
     soften, reroll_soft = check_soft_args(opt)
     canvas = check_canvas_args(opt)
     keep = check_keep_args(opt)
+    check_solver_args(opt)
     from tweediemix_amd import dist as D, launch as LA, masks as M, sampler as S, unet as U, weights as Wt
     if opt.gpus > 1 and not LA.launched():
         return LA.self_launch(opt.gpus)
@@ -574,6 +597,7 @@ def main(argv=None):
     tw = S.Tweediemix(opt, W, te, ts, provider, concept_num=K, lora=LORA,
                       strict_reference=strict, use_graphs=not opt.no_graphs, n_seeds=per, n_streams=opt.streams, vae=vae,
                       fp8=(opt.dtype == 'fp8'), attention_masks=attn, mask_soften=soften,
+                      solver=opt.solver, timestep_spacing=opt.timestep_spacing,
                       **(dict(canvas={k: canvas[k] for k in ('height', 'width', 'overlap')}) if canvas else {}))
     if vae_scaling:                                       # fusion_sampling.py:518 divides by vae.config.scaling_factor
         tw.vae_scaling_factor = float(vae_scaling)

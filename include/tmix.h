@@ -98,6 +98,22 @@ int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps, int eps_dt
                                      int64_t hw, int mode, int rows, int seeds, const float* params,
                                      const float* keep_x0, int64_t keep_x0_seed_stride, const float* keep_eps,
                                      int64_t keep_eps_seed_stride, const float* keep_w, int64_t keep_w_seed_stride, void* stream);
+/* tmix_fused_tweedie_step_dev with a SECOND-ORDER MULTISTEP move (no reference counterpart: the reference is first-order DDIM): the
+ * DPM-Solver++(2M) update in data-prediction form on the mode's x0 -- in FUSION mode the blended estimate -- and the x0 of the step before.
+ *   params   fp32 {t, sa, s1, cx, c0, c1, is_last (0/1), g}: sa = sqrt(at), s1 = sqrt(1-at) of the CURRENT timestep (what x0 needs);
+ *            cx = s1_next/s1, c0, c1 the solver's coefficients, computed by the host in fp64 and rounded once (solver.multistep_coeffs);
+ *            c1 = 0 is a first-order step.  NOT the layout of tmix_fused_tweedie_step_dev's params: g is the last float here.
+ *   x0_prev  [seeds][n] fp32, read AND written: the history buffer.  It aliases no other argument.
+ * Everything else is tmix_fused_tweedie_step_dev's argument of that name.  x0 is computed by that entry's operations in that order, so
+ * out_x0 is bit-identical to its out_x0.  Then per element i, in fp32, every product and sum its own operation (not contracted):
+ *   p = x0_prev[i]        m = c0*x0;  if (c1 != 0) m = m + c1*p        out_x[i] = is_last ? x0 : cx*x[i] + m
+ *   x0_prev[i] = x0       out_x0[i] = x0 (when given)
+ * p is not used when c1 == 0: a first-order step may be run on a history buffer that holds anything, NaN included.  x may alias out_x.
+ * modes FUSION and PLAIN; TMIX_EINVAL for RESAMPLE (its re-noising half moves away from the data, which the formula does not cover) and for
+ * a null x0_prev; otherwise the checks of tmix_fused_tweedie_step_dev. */
+int tmix_fused_tweedie_step_ms_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                   int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
+                                   int64_t hw, int mode, int rows, int seeds, const float* params, void* stream);
 /* Head of the captured step (fusion_sampling.py:324-327, `latent_model_input = torch.cat([x] * rows)`, and the timestep
  * argument of the UNet call :340): latent[(s*rows + r)][n] = x[s][n] for every row r, t_dev[s*rows + r] = params[0]. */
 int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,

@@ -1,0 +1,104 @@
+// solver_step.hip -- fused CFG + Tweedie x0 + mask blend + DPM-Solver++(2M) update on the blended estimate (one HBM pass).
+// The x0 part repeats tweedie_step.hip's tweedie_step_kernel operation for operation (rnd<DT> included), so out_x0 is that kernel's out_x0
+// bit for bit; the move is the data-prediction form x_next = cx x + c0 x0 + c1 x0_prev with the history buffer x0_prev read and rewritten in
+// the same pass.  Per element and seed it reads (rows) eps values + x + K mask values + 1 history value and writes 2-3 floats.
+// Compiled with -ffp-contract=off so fp32 results are bit-identical to the numpy restatement (solver.multistep_step_reference).
+#include "common.h"
+
+namespace {
+
+template <int DT> struct EpsT;
+template <> struct EpsT<TMIX_F32>  { typedef float  T; static __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; } };
+template <> struct EpsT<TMIX_F16>  { typedef __half T; static __device__ __forceinline__ float ld(const __half* p, int64_t i) { return __half2float(p[i]); } };
+template <> struct EpsT<TMIX_BF16> { typedef bf16_t T; static __device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); } };
+
+// rounding point of the reference's autocast path (only when eps is fp16): the fp32 RESULT is rounded to fp16; the empty asm keeps LLVM from
+// folding mul+convert into the single-rounding v_fma_mixlo_f16 (as in tweedie_step.hip)
+template <int DT> __device__ __forceinline__ float rnd(float v) {
+    if constexpr (DT == TMIX_F16) {
+        asm volatile("" : "+v"(v));
+        return __half2float(__float2half_rn(v));
+    } else return v;
+}
+
+template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float g) {
+    const float d = rnd<DT>(ec - eu);
+    const float gd = rnd<DT>(g * d);
+    return rnd<DT>(eu + gd);
+}
+
+// prm = {t, sa, s1, cx, c0, c1, is_last, g} in device memory (one captured launch serves every timestep and both orders); blockIdx.y walks
+// co-batched seeds (x / out_x / out_x0 / x0_prev: [seeds][n], eps: [seeds][rows][n], masks: [seeds][K][hw] or shared).  x may alias out_x:
+// every array is read at i before it is written at i.  x0_prev is read AND written, so it carries no __restrict__.
+template <int DT, int MODE>
+__global__ void __launch_bounds__(256)
+solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps, const float* __restrict__ masks, float* out_x,
+                   float* __restrict__ out_x0, float* x0_prev, int K, int64_t n, int64_t hw, const float* __restrict__ prm, int rows,
+                   int64_t mask_seed_stride) {
+    const float sa = prm[1], s1 = prm[2], cx = prm[3], c0 = prm[4], c1 = prm[5], g = prm[7];
+    const bool is_last = prm[6] != 0.0f;
+    const int64_t sd = blockIdx.y;
+    x += sd * n; out_x += sd * n; x0_prev += sd * n; eps += sd * rows * n; masks += sd * mask_seed_stride;
+    if (out_x0) out_x0 += sd * n;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float xv = x[i];
+        const float p = x0_prev[i];
+        const float eu = EpsT<DT>::ld(eps, i);
+        float x0;
+        if constexpr (MODE == TMIX_STEP_FUSION) {
+            const int64_t px = i % hw;
+            x0 = 0.0f;
+            for (int c = 0; c < K; ++c) {
+                const float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
+                const float t = (xv - rnd<DT>(s1 * e)) / sa;
+                x0 = x0 + masks[(int64_t)c * hw + px] * t;
+            }
+        } else {
+            const float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+            x0 = (xv - rnd<DT>(s1 * e)) / sa;
+        }
+        float m = c0 * x0;
+        if (c1 != 0.0f) m = m + c1 * p;          // a first-order step never touches the history value: a NaN left there stays out
+        out_x[i] = is_last ? x0 : cx * xv + m;
+        x0_prev[i] = x0;
+        if (out_x0) out_x0[i] = x0;
+    }
+}
+
+template <int DT>
+int launch_ms(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, float* x0_prev, int K, int64_t n,
+              int64_t hw, int mode, int rows, int seeds, const float* prm, hipStream_t st) {
+    typedef typename EpsT<DT>::T T;
+    int64_t bx = (n + 255) / 256; if (bx > 2048) bx = 2048;
+    const dim3 grid((unsigned)bx, (unsigned)seeds);
+    const T* e = (const T*)eps;
+    if (mode == TMIX_STEP_FUSION)
+        solver_step_kernel<DT, TMIX_STEP_FUSION><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss);
+    else
+        solver_step_kernel<DT, TMIX_STEP_PLAIN><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+}  // namespace
+
+extern "C" int tmix_fused_tweedie_step_ms_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                              int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
+                                              int64_t hw, int mode, int rows, int seeds, const float* params, void* stream) {
+    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: null pointer");
+    if (!x0_prev) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: null x0_prev (the history buffer is read and written by every step)");
+    if (mode != TMIX_STEP_FUSION && mode != TMIX_STEP_PLAIN) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: bad mode %d (FUSION or PLAIN)", mode);
+    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: FUSION needs masks and K>=1");
+    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
+    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
+    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
+    const int64_t n = (int64_t)channels * hw;
+    hipStream_t st = (hipStream_t)stream;
+    switch (eps_dtype) {
+    case TMIX_F32:  return launch_ms<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st);
+    case TMIX_F16:  return launch_ms<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st);
+    case TMIX_BF16: return launch_ms<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st);
+    }
+    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: bad eps dtype %d", eps_dtype);
+}

@@ -91,6 +91,29 @@ def fused_tweedie_step_keep_dev(x, eps, masks, mode, K, params, keep_x0, keep_ep
     return out_x
 
 
+def fused_tweedie_step_ms_dev(x, eps, masks, mode, K, params, x0_prev, out_x=None, out_x0=None):
+    """tmix_fused_tweedie_step_ms_dev: x [S,C,h,w] fp32, eps [S*rows,C,h,w] f32|f16|bf16, masks [K,1,h,w] or [S,K,1,h,w] (FUSION), params the
+    device buffer {t, sa, s1, cx, c0, c1, is_last, g} (solver.multistep_coeffs), x0_prev [S,C,h,w] fp32 the history buffer, read and
+    rewritten with this step's x0.  out_x may be x itself (in place).  Returns out_x."""
+    _need_cuda(x, eps, masks, params, x0_prev)
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and params.dtype == torch.float32 and params.numel() >= 8
+    assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.shape == x.shape, tuple(x0_prev.shape)
+    S, Cc, h, w = x.shape
+    hw = h * w
+    assert eps.shape[0] % S == 0
+    rows = eps.shape[0] // S
+    mss = 0
+    if mode == L.STEP_FUSION:
+        assert masks is not None and masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() in (K * hw, S * K * hw)
+        mss = 0 if masks.numel() == K * hw else K * hw
+    if out_x is None:
+        out_x = torch.empty_like(x)
+    L.check(L.load().tmix_fused_tweedie_step_ms_dev(
+        _p(x), _p(eps), _EPS_DT[eps.dtype], _p(masks), mss, _p(out_x), _p(out_x0), _p(x0_prev), K, Cc, hw, mode, rows, S, _p(params),
+        _stream()), "tmix_fused_tweedie_step_ms_dev")
+    return out_x
+
+
 def window_consensus(x, groups, offsets, canvas_hw, weight=None):
     """tmix_window_consensus, in place on x [groups * n_win, C, h, w] fp32 (group-major: b = group * n_win + window): every canvas pixel
     that several windows cover becomes their weighted mean in all of them.  offsets [(oy, ox), ...] the windows' corners on the canvas

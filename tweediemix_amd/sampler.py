@@ -12,6 +12,8 @@ Same method names, argument meaning and step semantics as fusion_generation/fusi
   state in place,
 * optionally a KEEP REGION (set_keep / clear_keep): part of the latent held at a given clean latent, re-noised inside the same kernel
   (tmix_fused_tweedie_step_keep_dev) to the level of every state the loop writes,
+* optionally (solver="dpmpp2m") a second-order multistep move on the blended estimate behind the first timestep
+  (tmix_fused_tweedie_step_ms_dev), on an optional log-SNR timestep grid (timestep_spacing="logsnr"),
 * ONE hipGraph per (call kind, step mode) holding the whole step -- latent broadcast + timestep
   (tmix_step_prologue), the UNet launch chains, the fused step for all co-batched seeds: a timestep is one 32-byte
   parameter upload and one graph replay.
@@ -30,6 +32,7 @@ import torch
 from . import lib as L
 from . import ops
 from .schedule import Schedule
+from .solver import SOLVERS, multistep_coeffs
 from .unet import KVCache, PlanGroup, TokenMapSpec, TokenPropSpec, UNetPlan, UNetWeights
 
 F32 = torch.float32
@@ -94,13 +97,25 @@ class Tweediemix:
                       feather <= 1 with dilate = 0 and normalize=False gives the bits of None.  soft_weights holds what the last
                       acquisition produced ([K,1,H,W] or [n,K,1,H,W] on the grid the masks were built on).  The public `masks` setter stays
                       raw: what is assigned there is what the fused step reads.
+    solver            "ddim" (the reference's first-order steps: today's launches and bits) or "dpmpp2m": every trajectory step behind the first
+                      timestep is a DPM-Solver++(2M) step on the blended Tweedie estimate (tmix_fused_tweedie_step_ms_dev: x' = cx x + c0 x0 +
+                      c1 x0_prev, coefficients from solver.multistep_coeffs), second order exactly when the previous call ran a solver step of
+                      the same mode on the preceding schedule entry.  The first timestep, the look-ahead and the propagate rounds stay on the
+                      DDIM entry.  Not with set_keep.  DESIGN.md 7i.
+    timestep_spacing  "leading" (the reference's grid) or "logsnr": n_timesteps uniform in log-SNR from the 'leading' grid's first timestep to
+                      t = 1 (schedule.Schedule(spacing="logsnr")); skip is then None, and t_cond / t_stop keep their noise range
+                      (_window_index).  Independent of `solver`.
     """
 
     def __init__(self, config, weights: UNetWeights, text_embeds, text_embeds_single, mask_provider,
                  concept_num: int, lora: bool = False, strict_reference: bool = True, use_graphs: bool = False,
                  n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None,
-                 mask_soften=None):
+                 mask_soften=None, solver: str = "ddim", timestep_spacing: str = "leading"):
         self.config = config
+        if solver not in SOLVERS:
+            raise ValueError(f"solver={solver!r}: one of {SOLVERS}")
+        self.solver = solver
+        self.timestep_spacing = timestep_spacing
         self.fp8 = bool(fp8)          # optional: FF / QKV projections on e4m3 operands (tmix_gemm_fp8); default bf16 like the reference's fp16
         self.W = weights
         self.device = weights.device
@@ -162,8 +177,8 @@ class Tweediemix:
                                  + (f"; unknown keys {sorted(extra)}" if extra else ""))
             self.mask_soften = dict(feather=f, dilate=r, normalize=bool(ms.get("normalize", False)))
         self._mask_buf = None
-        self.scheduler = Schedule(config.n_timesteps)
-        self.skip = self.scheduler.skip
+        self.scheduler = Schedule(config.n_timesteps, spacing=timestep_spacing)
+        self.skip = self.scheduler.skip    # None on the "logsnr" grid: the loop asks scheduler.next_t(t)
         self.final_alpha_cumprod = self.scheduler.final_alpha_cumprod
         self.h, self.w = config.resolution_h // 8, config.resolution_w // 8
         self.canvas_h, self.canvas_w = self.h, self.w
@@ -186,6 +201,10 @@ class Tweediemix:
         # attention_masks with propagate >= 1: the state the last look-ahead call read, which the propagate rounds replay
         self._x_look = torch.zeros_like(self.x_state) if (self.attention_masks or {}).get("propagate") else None
         self.step_params = torch.zeros(8, device=self.device, dtype=F32)      # {t, sa, s1, sa_next, s1_next, is_last, g, -}
+        # solver="dpmpp2m": the blended estimate of the solver step before (tmix_fused_tweedie_step_ms_dev reads and rewrites it; its steps
+        # upload {t, sa, s1, cx, c0, c1, is_last, g} into step_params instead) and which step wrote it: (schedule index, step mode) or None
+        self._x0_prev = torch.zeros_like(self.x_state) if solver != "ddim" else None
+        self._ms_last = None
         self._keep = self._keep_bufs = None    # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
         # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it
         # has completed (the host runs ahead of the device by whole steps)
@@ -248,6 +267,8 @@ class Tweediemix:
         the fixed noise of every seed's kept part.  From the next run_fusion / sample_loop on every step writes
         weight * (sa' x0 + s1' eps) + (1 - weight) * (its own result), with sa' / s1' of the state it writes (tmix_fused_tweedie_step_keep_dev),
         x_T is composited the same way once, and the final latent holds x0 itself.  The tensors are copied: captured steps read these buffers."""
+        if self.solver != "ddim":        # the keep term needs sa_next / s1_next, which the multistep entry's eight floats do not carry
+            raise ValueError(f"set_keep: not with solver={self.solver!r} (the keep region exists on the solver='ddim' step only)")
         if self.windows is not None:     # the mean of equal values is not always that value bit for bit: the kept region's promise would break
             raise ValueError(f"set_keep: not on a canvas ({len(self.windows)} windows on {self.canvas_w * 8} x {self.canvas_h * 8}): "
                              f"reconciling the windows would change the kept bits")
@@ -372,8 +393,8 @@ class Tweediemix:
         else:
             self._set_masks(m)
 
-    def _enqueue_step(self, kind, mode):
-        """the launches of one denoising step on the current stream: prologue, UNet chains, fused step (in place)."""
+    def _enqueue_step(self, kind, mode, ms=False):
+        """the launches of one denoising step on the current stream: prologue, UNet chains, fused step (in place; ms: the multistep entry)."""
         p = self.plan(kind)
         S = self.n_seeds
         rows = p.B // S
@@ -383,18 +404,22 @@ class Tweediemix:
         L.check(lib.tmix_step_prologue(self.x_state.data_ptr(), p.latent.data_ptr(), p.t_dev.data_ptr(),
                                        self.step_params.data_ptr(), S, rows, n, st), "tmix_step_prologue")
         p.run()
-        self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st)
+        self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st, ms)
         if self.windows is not None:
             self._consensus(self.x_state)
 
-    def _fused_step(self, eps_ptr, eps_dt, rows, mode, st):
-        """the fused step for every seed, in place on x_state; with a keep region set (set_keep) through the entry that holds it"""
+    def _fused_step(self, eps_ptr, eps_dt, rows, mode, st, ms=False):
+        """the fused step for every seed, in place on x_state; with a keep region set (set_keep) through the entry that holds it; ms: the
+        multistep entry, which also reads and rewrites the history buffer"""
         lib = L.load()
         m = self._mask_buf if mode == L.STEP_FUSION else None
         mss = 0 if (m is None or m.dim() == 4) else self.concept_num * self.h * self.w
         hw = self.h * self.w
         head = (self.x_state.data_ptr(), eps_ptr, eps_dt, None if m is None else m.data_ptr(), mss, self.x_state.data_ptr(),
                 self.x0_state.data_ptr(), self.concept_num, 4, hw, mode, rows, self.n_seeds, self.step_params.data_ptr())
+        if ms:
+            L.check(lib.tmix_fused_tweedie_step_ms_dev(*head[:7], self._x0_prev.data_ptr(), *head[7:], st), "tmix_fused_tweedie_step_ms_dev")
+            return
         if self._keep is None:
             L.check(lib.tmix_fused_tweedie_step_dev(*head, st), "tmix_fused_tweedie_step_dev")
             return
@@ -402,8 +427,9 @@ class Tweediemix:
         L.check(lib.tmix_fused_tweedie_step_keep_dev(*head, kx.data_ptr(), 0 if kx.shape[0] == 1 else 4 * hw, ke.data_ptr(), 4 * hw,
                                                      kw.data_ptr(), 0 if kw.shape[0] == 1 else hw, st), "tmix_fused_tweedie_step_keep_dev")
 
-    def _run_step(self, kind, mode, t, at, at_next, is_last=False):
-        """x_state <- step(x_state) for every seed; x0_state <- the Tweedie estimate.  Host work per step: eight floats."""
+    def _run_step(self, kind, mode, t, at, at_next, is_last=False, ms=None):
+        """x_state <- step(x_state) for every seed; x0_state <- the Tweedie estimate.  Host work per step: eight floats.
+        ms = (cx, c0, c1): a multistep solver step (at_next is then not read: the move is in the coefficients)."""
         if "_unet" not in vars(self):
             self.unet_calls.append((kind, self.plan(kind).B // self.n_seeds, int(t)))
         sa, s1, san, s1n = ops.step_coeffs(at, at_next)
@@ -412,8 +438,12 @@ class Tweediemix:
         if self._hp_ev[i] is not None:
             self._hp_ev[i].synchronize()
         hp = self._hp[i]
-        hp[0], hp[1], hp[2], hp[3], hp[4] = float(t), sa, s1, san, s1n
-        hp[5], hp[6] = (1.0 if is_last else 0.0), float(self.config.guidance_scale)
+        if ms is None:
+            hp[0], hp[1], hp[2], hp[3], hp[4] = float(t), sa, s1, san, s1n
+            hp[5], hp[6] = (1.0 if is_last else 0.0), float(self.config.guidance_scale)
+        else:
+            hp[0], hp[1], hp[2], hp[3], hp[4], hp[5] = float(t), sa, s1, ms[0], ms[1], ms[2]
+            hp[6], hp[7] = (1.0 if is_last else 0.0), float(self.config.guidance_scale)
         self.step_params.copy_(hp, non_blocking=True)
         if self.device.type == "cuda":
             self._hp_ev[i] = torch.cuda.Event()
@@ -425,23 +455,24 @@ class Tweediemix:
             # module in): the same fused step, eagerly, on whatever eps dtype the stand-in returns
             eps = self._unet(kind, self.x_state, t).contiguous()
             self._fused_step(eps.data_ptr(), ops._EPS_DT[eps.dtype], eps.shape[0] // self.n_seeds, mode,
-                             torch.cuda.current_stream().cuda_stream)
+                             torch.cuda.current_stream().cuda_stream, ms is not None)
             if self.windows is not None:
                 self._consensus(self.x_state)
             return
         if not self.use_graphs:
-            self._enqueue_step(kind, mode)
+            self._enqueue_step(kind, mode, ms is not None)
             return
         # a step captured with a keep region is another graph (another kernel, three more pointers): the ones captured without it stay valid
-        gkey = (kind, mode) if self._keep is None else (kind, mode, "keep")
+        # and so is a multistep step (another kernel, one more pointer): one graph serves both orders, the order is in the uploaded coefficients
+        gkey = (kind, mode, "ms") if ms is not None else (kind, mode) if self._keep is None else (kind, mode, "keep")
         g = self.graphs.get(gkey)
         if g is None:
-            self._enqueue_step(kind, mode)                # warm-up outside capture (kernel attributes, lazy module load);
+            self._enqueue_step(kind, mode, ms is not None)    # warm-up outside capture (kernel attributes, lazy module load);
             torch.cuda.synchronize()                      # it has already performed this step, so no replay now
             g = torch.cuda.CUDAGraph()
             keep = self.x_state.clone()
             with torch.cuda.graph(g):
-                self._enqueue_step(kind, mode)
+                self._enqueue_step(kind, mode, ms is not None)
             self.x_state.copy_(keep)                      # capture does not execute, but keep the state explicit
             self.graphs[gkey] = g
             return
@@ -518,10 +549,15 @@ class Tweediemix:
         """one scheduler timestep on x_state (fusion_sampling.py:309-474)."""
         t = int(t)
         cfg = self.config
-        next_t = t - self.skip
+        next_t = self.scheduler.next_t(t)
         at, at_next = self.alpha(t), self.alpha(next_t)
         last = t == 1
-        if self._in_fusion(t):
+        solver_step = self.solver != "ddim" and t != self.start_t
+        if not solver_step:
+            self._ms_last = None                        # a timestep on the DDIM entry leaves no history for a second-order step to use
+        if solver_step:
+            self._solver_step(t, at, at_next, last)
+        elif self._in_fusion(t):
             kind = "fusion" if (t in self._window) else "fusion_base"
             self._run_step(kind, L.STEP_FUSION, t, at, at_next, last)
         elif t == self.start_t:
@@ -567,6 +603,25 @@ class Tweediemix:
                 m = self._soften(torch.stack([self.mask_provider(self.preview_x0[i:i + 1]).to(self.device, F32)
                                               for i in range(self.n_seeds)]).contiguous())
             self._set_masks(m)
+
+    def _solver_step(self, t, at, at_next, last):
+        """one trajectory step behind the first timestep through the multistep entry.  Second order exactly when the previous
+        _denoise_inplace call ran a solver step of the same mode on the preceding schedule entry -- so the first solver step, the first fusion
+        step, the first plain step behind a LoRA t_stop and any step asked for out of order are first order.  The whole first timestep, the
+        look-ahead and the propagate rounds run the DDIM entry and leave the history buffer alone."""
+        ts = self.scheduler.timesteps
+        if t not in ts:
+            raise ValueError(f"solver={self.solver!r}: t = {t} is not one of the schedule's timesteps {ts}")
+        i = ts.index(t)
+        if self._in_fusion(t):
+            kind, mode = ("fusion" if (t in self._window) else "fusion_base"), L.STEP_FUSION
+        else:
+            kind, mode = "plain", L.STEP_PLAIN
+        second = self._ms_last == (i - 1, mode)
+        # the last step writes x0 itself: its move (to alpha = 1, or on the 'leading' grid to the alpha it stands on) has no finite h
+        ms = (0.0, 1.0, 0.0) if last else multistep_coeffs(self.alpha(ts[i - 1]), at, at_next, second)
+        self._run_step(kind, mode, t, at, at_next, last, ms=ms)
+        self._ms_last = (i, mode)
 
     def _propagate_rounds(self, t):
         """the token maps pushed propagate times through the self-attention of the last look-ahead call (input _x_look, timestep t): round
@@ -616,11 +671,19 @@ class Tweediemix:
         self._denoise_inplace(t)
         return self._to_canvas(self.x_state)
 
+    def _window_index(self, frac):
+        """schedule index of the window fraction frac (t_cond / t_stop).  The 'logsnr' grid keeps the window's NOISE range, not its index
+        range: the index of the first timestep at or below the one the 'leading' grid of the same n has at int(n * frac)."""
+        i = int(self.config.n_timesteps * frac)
+        if self.timestep_spacing == "leading":
+            return i
+        return self.scheduler.index_at_or_below(Schedule(self.config.n_timesteps).timesteps[i])
+
     def run_fusion(self, x=None, decode=False):
         cfg = self.config
-        t_cond = int(cfg.n_timesteps * cfg.t_cond)
+        t_cond = self._window_index(cfg.t_cond)
         if self.lora:
-            self.init_fusion(t_cond, int(cfg.n_timesteps * cfg.t_stop))
+            self.init_fusion(t_cond, self._window_index(cfg.t_stop))
         else:
             self.init_fusion(t_cond)
         if x is None:      # drawn on the CPU like the reference (fusion_sampling.py:488): device-independent seeds

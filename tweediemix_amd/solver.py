@@ -1,0 +1,93 @@
+"""DPM-Solver++(2M) on the blended Tweedie estimate: host-side coefficients and the numpy restatement of the step kernel.
+
+The sampler's x0 (in fusion mode the mask blend of the concepts' Tweedie estimates) is the "data prediction" of DPM-Solver++ (Lu et al. 2022,
+arXiv:2211.01095, algorithm 2).  With lambda = log(sqrt(a) / sqrt(1 - a)), h = lambda_next - lambda and r = (lambda - lambda_prev) / h the
+multistep update is
+
+    x_next = (s1_next / s1) x + sa_next (1 - e^-h) [ (1 + 1/(2r)) x0 - 1/(2r) x0_prev ]  =  cx x + c0 x0 + c1 x0_prev,
+
+first order (c1 = 0) where no usable previous estimate exists.  Everything here is host code: the kernel (csrc/solver_step.hip) sees cx, c0, c1.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+F32 = np.float32
+SOLVERS = ("ddim", "dpmpp2m")
+STEP_FUSION, STEP_PLAIN = 0, 1        # TMIX_STEP_FUSION / TMIX_STEP_PLAIN (lib.py's values; this module loads no library)
+
+
+def _sa_s1_lam(a):
+    a = float(F32(a))
+    sa, s1 = math.sqrt(a), math.sqrt(1.0 - a)
+    return sa, s1, math.log(sa / s1)
+
+
+def multistep_coeffs64(a_prev, a, a_next, second_order):
+    """(cx, c0, c1) of the step from alpha a to a_next in fp64 from the fp32 alphas; a_prev (the alpha of the step before, lambda_prev <
+    lambda) is read only when second_order"""
+    sa, s1, lam = _sa_s1_lam(a)
+    san, s1n, lam_n = _sa_s1_lam(a_next)
+    h = lam_n - lam
+    if not h > 0.0:
+        raise ValueError(f"multistep_coeffs: alpha {a} -> {a_next} does not move towards the data (h = {h})")
+    E = -math.expm1(-h)
+    cx = s1n / s1
+    if second_order:
+        lam_p = _sa_s1_lam(a_prev)[2]
+        r = (lam - lam_p) / h
+        if not r > 0.0:
+            raise ValueError(f"multistep_coeffs: previous alpha {a_prev} is not noisier than {a}")
+        c0, c1 = san * E * (1.0 + 1.0 / (2.0 * r)), -san * E / (2.0 * r)
+    else:
+        c0, c1 = san * E, 0.0
+    return cx, c0, c1
+
+
+def multistep_coeffs(a_prev, a, a_next, second_order):
+    """multistep_coeffs64 rounded ONCE to fp32: what the sampler uploads (Python floats that hold fp32 values)"""
+    return tuple(float(F32(v)) for v in multistep_coeffs64(a_prev, a, a_next, second_order))
+
+
+def _h(a, lowp):
+    return a.astype(lowp).astype(F32) if lowp is not None else a
+
+
+def _cfg(eu, ec, g, lowp):
+    d = _h(ec - eu, lowp)
+    return _h(eu + _h(F32(g) * d, lowp), lowp)
+
+
+def _tweedie(x, e, sa, s1, lowp):
+    return ((x - _h(F32(s1) * e, lowp)) / F32(sa)).astype(F32)
+
+
+def blended_x0_reference(mode, x, eps, masks, g, sa, s1, lowp=None):
+    """the x0 of tweedie_step_kernel (FUSION / PLAIN), operation for operation: x [1,C,h,w], eps [rows,C,h,w] fp32 values of the eps dtype,
+    masks [K,1,h,w]; sa, s1 fp32; lowp = np.float16 for fp16 eps (its rounding points), else None"""
+    x, eps = np.asarray(x, F32), np.asarray(eps, F32)
+    eu = eps[:1]
+    if mode == STEP_PLAIN:
+        return _tweedie(x, _cfg(eu, eps[1:2], g, lowp), sa, s1, lowp)
+    if mode != STEP_FUSION:
+        raise ValueError(f"multistep step: mode {mode} (FUSION or PLAIN)")
+    masks = np.asarray(masks, F32)
+    x0 = np.zeros_like(x, dtype=F32)
+    for c in range(masks.shape[0]):
+        x0 = (x0 + masks[c][None] * _tweedie(x, _cfg(eu, eps[1 + c:2 + c], g, lowp), sa, s1, lowp)).astype(F32)
+    return x0
+
+
+def multistep_step_reference(mode, x, eps, masks, x0_prev, g, sa, s1, cx, c0, c1, is_last, lowp=None):
+    """numpy fp32 restatement of tmix_fused_tweedie_step_ms_dev for one seed -> (out_x, x0); x0 is also the new history.  The kernel is
+    compared with this by equality.  Products and sums are separate fp32 operations (the kernel is built with -ffp-contract=off);
+    x0_prev is used only when c1 != 0."""
+    x = np.asarray(x, F32)
+    x0 = blended_x0_reference(mode, x, eps, masks, g, sa, s1, lowp)
+    m = (F32(c0) * x0).astype(F32)
+    if F32(c1) != 0:
+        m = (m + (F32(c1) * np.asarray(x0_prev, F32)).astype(F32)).astype(F32)
+    out = x0 if is_last else ((F32(cx) * x).astype(F32) + m).astype(F32)
+    return out, x0
