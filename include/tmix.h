@@ -194,6 +194,22 @@ int tmix_video_step_prologue(const float* x, float* x_u, int64_t clip_stride_u, 
                              void* stream);
 int tmix_vpred_step_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
                         const float* params, int videos, int channels, int frames, int64_t hw, void* stream);
+/* DPM-Solver++(2M) form of the video step (no reference counterpart).  With v' and x0 = sa x - s1 v' formed exactly as in
+ * tmix_vpred_step (the same operations in the same order, so x0 is that kernel's x0 bit for bit), p = x0_prev[i] read first:
+ *   m = c0 x0; if (c1 != 0) m = m + c1 p; out[i] = cx x + m; x0_prev[i] = x0
+ * -- every binary operation a separate one, rounded as in tmix_vpred_step for TMIX_F16.  cx, c0, c1 come from the host (solver.py); c1 == 0
+ * is a first-order step and p then never reaches the output (a NaN-filled history is fine).
+ * tmix_vpred_step_ms: x [n], v [2n] (uncond rows first), out [n] of `dtype`; x0_prev [n] is ALWAYS fp32, is read and written and aliases
+ *   nothing; out may alias x.
+ * tmix_vpred_step_ms_dev: the TMIX_F32 form for `videos` videos, in place on x [videos][channels][frames][hw] with x0_prev of the same layout and
+ *   v_u / v_c read from the halves' prediction rows exactly as tmix_vpred_step_dev reads them; params = {t, sa, s1, cx, c0, c1, g, 0} (fp32, device;
+ *   NOT tmix_vpred_step_dev's layout; params[0] stays t, so tmix_video_step_prologue is shared).  Bit-identical to the scalar form per element.
+ * Both: TMIX_EINVAL on a null pointer (x0_prev included) or a bad dtype, TMIX_ESHAPE on an empty shape or a clip stride shorter than one clip,
+ * all checked on the host before any launch; one launch on `stream`, capturable; no workspace. */
+int tmix_vpred_step_ms(const void* x, const void* v, void* out, float* x0_prev, int dtype, int64_t n, float g,
+                       float sa, float s1, float cx, float c0, float c1, void* stream);
+int tmix_vpred_step_ms_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
+                           const float* params, int videos, int channels, int frames, int64_t hw, void* stream);
 /* First-frame feature injection of the patched ResnetBlock2D.forward (video_gen/utils_attn.py:433-455), in place on
  * x [clips][frames][per_frame]: frames 1.. <- frame 0 (hard) or interp*frame0 + one_minus_interp*frame. */
 int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,

@@ -25,7 +25,12 @@ Many videos per run (a video is one (image, seed) pair; the videos are the image
   --output_dir D            where the files go (default .)
 Every run, one video or many, goes through tweediemix_amd.video.VideoSampler: the whole step of S videos on the device
 (tmix_video_step_prologue -> both CFG chains -> tmix_vpred_step_dev), one parameter upload and one graph replay per timestep;
-frames are decoded in batches (vae.decode_in_groups), so a video's GIF does not depend on whether it ran alone or in a batch."""
+frames are decoded in batches (vae.decode_in_groups), so a video's GIF does not depend on whether it ran alone or in a batch.
+
+Few-step sampling (no reference counterpart):
+  --solver dpmpp2m          every step is a DPM-Solver++(2M) step on the x0 of the v-prediction (tmix_vpred_step_ms_dev)
+  --timestep_spacing logsnr the num_inference_steps timesteps uniform in log-SNR from the leading grid's first timestep to 1
+Without them (ddim, leading) the run is the reference's loop; an n the grid or the solver cannot take is refused before the GPU is touched."""
 import argparse
 import os
 import sys
@@ -68,6 +73,9 @@ def build_parser():
     p.add_argument("--seeds_per_batch", type=int, default=0, help="videos co-batched into every UNet call (0: all of this rank's videos, at most 4)")
     p.add_argument("--gpus", type=int, default=1, help="shard the videos over this many GPUs (one process per GPU, started by this script; at most 8)")
     p.add_argument("--output_dir", default=".")
+    # few-step sampling; the defaults are the reference's loop
+    p.add_argument("--solver", default="ddim", choices=["ddim", "dpmpp2m"], help="dpmpp2m: every step is a DPM-Solver++(2M) step on the x0 of the v-prediction")
+    p.add_argument("--timestep_spacing", default="leading", choices=["leading", "logsnr"], help="logsnr: timesteps uniform in log-SNR from the leading grid's first timestep to 1")
     return p
 
 
@@ -189,7 +197,24 @@ def video_schedule(opt):
                   "i2vgen-xl settings (squaredcos_cap_v2, rescale_betas_zero_snr, steps_offset 1, set_alpha_to_one False)")
         acp, sch_kw = V.alphas_from_scheduler_config(dict(beta_schedule="squaredcos_cap_v2", rescale_betas_zero_snr=True,
                                                           steps_offset=1, set_alpha_to_one=False))
-    return V.VideoSchedule(acp, opt.num_inference_steps, **sch_kw)
+    return V.VideoSchedule(acp, opt.num_inference_steps, **sch_kw, spacing=opt.timestep_spacing)
+
+
+def checked_schedule(opt):
+    """the schedule of a run with --solver / --timestep_spacing, built on the host before anything touches the GPU: an n the grid or the solver
+    cannot take is refused here.  A run without the flags never comes here: it builds its schedule where it always did."""
+    from tweediemix_amd import video as V
+    if opt.num_inference_steps < 1:
+        raise SystemExit("--num_inference_steps must be >= 1")
+    try:
+        sch = video_schedule(opt)
+        if opt.solver != "ddim":                           # every step's coefficients exist (a zero alpha has no log-SNR)
+            phase = V.SolverPhase(sch)
+            for t in sch.timesteps:
+                phase.coeffs(int(t))
+    except ValueError as e:
+        raise SystemExit(f"--solver {opt.solver} --timestep_spacing {opt.timestep_spacing} with --num_inference_steps {opt.num_inference_steps}: {e}")
+    return sch
 
 
 def vae_decoder(opt):
@@ -216,8 +241,12 @@ def main(argv=None):
     opt = build_parser().parse_args(argv)
     images, videos = check_args(opt)
     from tweediemix_amd import dist as D, i2vgen as I, launch as LA, video as V
+    few_step = (opt.solver, opt.timestep_spacing) != ("ddim", "leading")
     if opt.gpus > 1 and not LA.launched():
-        return LA.self_launch(opt.gpus)
+        if few_step:
+            checked_schedule(opt)                                        # an impossible n is refused before any rank starts
+        return LA.self_launch(opt.gpus)                                  # every rank re-reads the same command line, these flags included
+    sch = checked_schedule(opt) if few_step else None                    # host only: refusals come before the GPU is touched
     rank, local, world = LA.rank_env()
     if world > 1:
         single = bool(os.environ.get("TMIX_SINGLE_GPU_DIST_TEST"))      # tests: all ranks on GPU 0, gloo
@@ -258,7 +287,8 @@ def main(argv=None):
         conds.append(c)
         xs.append(torch.randn(1, 4, Fr, h, w, generator=gen))          # latents * init_noise_sigma (= 1 for DDIM)
     Wt = I.I2VWeights(cfg, sd)
-    sch = video_schedule(opt)
+    if sch is None:
+        sch = video_schedule(opt)                                        # the defaults: built here, as always
     per = opt.seeds_per_batch or min(max(len(mine), 1), 4)
     lats = []
     smp = plan = None
@@ -270,7 +300,7 @@ def main(argv=None):
         smp = plan = None                                            # the previous batch's plan and graphs go before the next are built
         plan = I.I2VVideoPlan(Wt, S, Fr, h, w, fe, ctx, ilf, streams=opt.streams, interp=opt.interp_ratio)
         inj = V.FeatureInjector(sch.injection_schedule(opt.injection_timestep), opt.interp_ratio, clips=2 * S, frames=Fr)
-        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs)
+        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs, solver=opt.solver)
         lats.append(smp.sample(torch.cat([xs[i] for i in batch]).to(dev))[:n_real])
     smp = plan = None
     lat = torch.cat(lats) if lats else torch.zeros(0, 4, Fr, h, w, device=dev)

@@ -166,11 +166,7 @@ step_prologue_kernel(const float* __restrict__ x, float* __restrict__ latent, fl
     if (blockIdx.x == 0 && threadIdx.x < rows) t_dev[sd * rows + threadIdx.x] = prm[0];
 }
 
-// ------------------------------------------------------------------ video sampler (I2VGen-XL loop, config #5)
-template <int DT> struct StT;
-template <> struct StT<TMIX_F32>  { static __device__ __forceinline__ void st(float* p, int64_t i, float v) { p[i] = v; } };
-template <> struct StT<TMIX_F16>  { static __device__ __forceinline__ void st(__half* p, int64_t i, float v) { p[i] = __float2half_rn(v); } };
-template <> struct StT<TMIX_BF16> { static __device__ __forceinline__ void st(bf16_t* p, int64_t i, float v) { p[i] = f2bf(v); } };
+// ------------------------------------------------------------------ video sampler (I2VGen-XL loop, config #5); StT<DT>::st: common.h
 
 // video_gen/pipeline_i2vgen_xl.py:699-719 in one pass: CFG on the v-prediction, eps / x0 from (x, v), DDIM move.
 // Latents and predictions share the model dtype in that loop, so in fp16 mode EVERY binary op rounds (rnd<DT>).
@@ -204,17 +200,7 @@ frame_inject_kernel(typename EpsT<DT>::T* __restrict__ x, int64_t per_frame, int
     }
 }
 
-// ------------------------------------------------------------------ batched video step (S videos, both CFG halves)
-// index i of the pipeline-layout state [S][C][F][hw] -> offset of (video s, frame f, channel c, pixel p) in a per-row plan buffer
-// [(clip*F + f)][row_channels][hw] whose clip s starts at s * clip_stride
-__device__ __forceinline__ int64_t video_row_offset(int64_t i, int C, int F, int64_t hw, int row_channels, int64_t clip_stride) {
-    const int64_t p = i % hw;
-    int64_t r = i / hw;
-    const int64_t f = r % F; r /= F;
-    const int64_t c = r % C;
-    const int64_t s = r / C;
-    return s * clip_stride + (f * row_channels + c) * hw + p;
-}
+// ------------------------------------------------------------------ batched video step (S videos, both CFG halves); video_row_offset: common.h
 
 // head of the captured video step: the state goes into channels [0, C) of the frame rows of both CFG halves' inputs (the image-latent
 // channels [C, row_channels) are not touched) and prm[0] = t into both halves' per-clip timestep inputs

@@ -114,6 +114,8 @@ SIGNATURES = {
     "tmix_frame_inject": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, f32, f32, vp]),
     "tmix_video_step_prologue": (C.c_int, [vp, vp, i64, vp, vp, i64, vp, vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp]),
     "tmix_vpred_step_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_int, C.c_int, i64, vp]),
+    "tmix_vpred_step_ms": (C.c_int, [vp, vp, vp, vp, C.c_int, i64, f32, f32, f32, f32, f32, f32, vp]),
+    "tmix_vpred_step_ms_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, C.c_int, C.c_int, C.c_int, i64, vp]),
     "tmix_gemm_tile_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tmix_gemm_stats_parts": (C.c_int, [C.c_int, C.c_int]),
     "tmix_gemm_resolve_tile": (C.c_int, [C.POINTER(GemmDesc), C.c_int]),

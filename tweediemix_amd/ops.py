@@ -857,6 +857,50 @@ def video_step_params(t, g, at, at_next, out=None):
     return out
 
 
+def vpred_step_ms(x, v, g, at, coeffs, x0_prev, out=None):
+    """DPM-Solver++(2M) form of vpred_step (tmix_vpred_step_ms): x [B,...], v [2B,...] of one dtype, x0_prev fp32 of x's shape
+    (read and rewritten with this step's x0); at from the un-shifted alpha table (sa, s1 formed as vpred_step forms them), coeffs = (cx, c0, c1)
+    from solver.video_multistep_coeffs.  out may be x.  Returns the next latents (same dtype)."""
+    _need_cuda(x, v, x0_prev)
+    sa, s1 = np.sqrt(np.float32(at)), np.sqrt(np.float32(1) - np.float32(at))
+    cx, c0, c1 = coeffs
+    assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
+    assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
+    out = torch.empty_like(x) if out is None else out
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    L.check(L.load().tmix_vpred_step_ms(_p(x), _p(v), _p(out), _p(x0_prev), _EPS_DT[x.dtype], x.numel(), float(g), float(sa), float(s1),
+                                        float(cx), float(c0), float(c1), _stream()), "tmix_vpred_step_ms")
+    return out
+
+
+def vpred_step_ms_dev(x, v_u, v_c, x0_prev, params, clip_stride_u=None, clip_stride_c=None):
+    """vpred_step_ms for S videos in place on x [S,C,F,h,w] fp32 (x0_prev: the same shape), the CFG halves' predictions read from the plans'
+    frame rows as in vpred_step_dev and the coefficients from params {t, sa, s1, cx, c0, c1, g, 0} (video_step_params_ms)."""
+    _need_cuda(x, v_u, v_c, x0_prev, params)
+    assert x.dtype == v_u.dtype == v_c.dtype == x0_prev.dtype == torch.float32 and x.is_contiguous()
+    assert x0_prev.is_contiguous() and x0_prev.numel() == x.numel() and params.numel() >= 8
+    S, Cc, Fr, h, w = x.shape
+    su = clip_stride_u or Fr * Cc * h * w
+    sc = clip_stride_c or Fr * Cc * h * w
+    for buf, st in ((v_u, su), (v_c, sc)):
+        assert buf.is_contiguous() and buf.numel() >= (S - 1) * st + Fr * Cc * h * w
+    L.check(L.load().tmix_vpred_step_ms_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(x0_prev), _p(params), S, Cc, Fr, h * w, _stream()),
+            "tmix_vpred_step_ms_dev")
+    return x
+
+
+def video_step_params_ms(t, g, at, coeffs, out=None):
+    """the 8 floats {t, sa, s1, cx, c0, c1, g, 0} the batched solver step reads: sa, s1 as vpred_step computes them, coeffs = (cx, c0, c1)."""
+    f = np.float32
+    cx, c0, c1 = coeffs
+    vals = [float(t), float(np.sqrt(f(at))), float(np.sqrt(f(1) - f(at))), float(f(cx)), float(f(c0)), float(f(c1)), float(g), 0.0]
+    if out is None:
+        return torch.tensor(vals, dtype=torch.float32)
+    for i, v in enumerate(vals):
+        out[i] = v
+    return out
+
+
 def frame_inject(x, clips, frames, interp=None):
     """first-frame feature injection (video_gen/utils_attn.py:433-455), in place on x [(clips*frames), ...] contiguous."""
     _need_cuda(x)

@@ -7,6 +7,8 @@ multistep update is
     x_next = (s1_next / s1) x + sa_next (1 - e^-h) [ (1 + 1/(2r)) x0 - 1/(2r) x0_prev ]  =  cx x + c0 x0 + c1 x0_prev,
 
 first order (c1 = 0) where no usable previous estimate exists.  Everything here is host code: the kernel (csrc/solver_step.hip) sees cx, c0, c1.
+
+The video sampler's v-prediction step takes the same move on x0 = sa x - s1 v': video_multistep_coeffs, vpred_multistep_reference.
 """
 from __future__ import annotations
 
@@ -90,4 +92,48 @@ def multistep_step_reference(mode, x, eps, masks, x0_prev, g, sa, s1, cx, c0, c1
     if F32(c1) != 0:
         m = (m + (F32(c1) * np.asarray(x0_prev, F32)).astype(F32)).astype(F32)
     out = x0 if is_last else ((F32(cx) * x).astype(F32) + m).astype(F32)
+    return out, x0
+
+
+# ------------------------------------------------------------------------------------------------ video sampler (v-prediction)
+def video_multistep_coeffs(t, a_prev, a, a_next, second_order):
+    """(cx, c0, c1) of the video step at timestep t from alpha a to a_next, rounded once to fp32 (multistep_coeffs), on the video table's edge
+    cases: a_next == 1 (a checkpoint with set_alpha_to_one behind the last entry; lambda = +inf) is (0, 1, 0), the DDIM result x0, first order by
+    definition; a == 0 (the zero-terminal-SNR table's t = 999, or a timestep outside the table) has no lambda and is a ValueError"""
+    if not float(F32(a)) > 0.0:
+        raise ValueError(f"video solver step: alpha({int(t)}) = {float(a)} has no log-SNR (zero terminal SNR or a timestep outside the table); "
+                         f"the grid must start below it")
+    if float(F32(a_next)) >= 1.0:
+        return 0.0, 1.0, 0.0
+    return multistep_coeffs(a_prev, a, a_next, second_order)
+
+
+def _bf16_round(a):
+    """fp32 -> the nearest bf16 value (ties to even), as fp32: the one rounding of a TMIX_BF16 store"""
+    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32)
+    out = r.view(F32).copy()
+    nan = np.isnan(a)
+    out[nan] = a[nan]
+    return out
+
+
+def vpred_multistep_reference(x, v, x0_prev, g, sa, s1, cx, c0, c1, lowp=None):
+    """numpy restatement of tmix_vpred_step_ms (and, with lowp None, of tmix_vpred_step_ms_dev per video) -> (out, x0); x0 is also the new
+    history.  x [B,...], v [2B,...] (uncond rows first) hold fp32 copies of values of the model dtype, x0_prev [B,...] is fp32.  The kernels
+    are compared with this by equality: every product and sum is a separate fp32 operation (-ffp-contract=off).  lowp = np.float16: every
+    operation's result is rounded to fp16, as the DDIM kernel does for TMIX_F16 (x0 included, so the history holds fp16 values in fp32);
+    lowp = "bf16": fp32 arithmetic throughout and ONE rounding of out to bf16 at the store, as the DDIM kernel does for TMIX_BF16 (x0 stays
+    fp32).  x0_prev is used only when c1 != 0."""
+    x, v = np.asarray(x, F32), np.asarray(v, F32)
+    B = x.shape[0]
+    lp = None if lowp == "bf16" else lowp
+    vv = _cfg(v[:B], v[B:], g, lp)
+    x0 = _h(_h(F32(sa) * x, lp) - _h(F32(s1) * vv, lp), lp).astype(F32)
+    m = _h(F32(c0) * x0, lp)
+    if F32(c1) != 0:
+        m = _h(m + _h(F32(c1) * np.asarray(x0_prev, F32), lp), lp)
+    out = _h(_h(F32(cx) * x, lp) + m, lp).astype(F32)
+    if lowp == "bf16":
+        out = _bf16_round(out)
     return out, x0

@@ -16,23 +16,103 @@ import torch
 from . import ops
 
 
+SPACINGS = ("leading", "logsnr")
+SOLVERS = ("ddim", "dpmpp2m")
+
+
 class VideoSchedule:
     """alphas_cumprod [1000] (from the checkpoint's scheduler), leading timesteps with steps_offset (diffusers DDIMScheduler
-    set_timesteps as configured for i2vgen-xl), skip = 1000 // n."""
+    set_timesteps as configured for i2vgen-xl), skip = 1000 // n.
 
-    def __init__(self, alphas_cumprod, n_steps: int, steps_offset: int = 1, set_alpha_to_one: bool = False):
+    spacing="logsnr" (no reference counterpart) keeps the table and the first timestep of the 'leading' grid and places the n
+    timesteps uniformly in lambda(t) = log(sqrt(a) / sqrt(1 - a)) on the UN-shifted table (the construction of
+    schedule.Schedule._logsnr_timesteps); skip is then None and next_alpha(t) is the following entry's alpha."""
+
+    def __init__(self, alphas_cumprod, n_steps: int, steps_offset: int = 1, set_alpha_to_one: bool = False, spacing: str = "leading"):
+        if spacing not in SPACINGS:
+            raise ValueError(f"timestep spacing {spacing!r}: one of {SPACINGS}")
         self.acp = np.asarray(alphas_cumprod, np.float32)
         self.final_alpha_cumprod = np.float32(1.0) if set_alpha_to_one else self.acp[0]
         self.n = n_steps
+        self.spacing = spacing
         self.skip = len(self.acp) // n_steps
         self.timesteps = (np.arange(0, n_steps) * self.skip).round()[::-1].astype(np.int64) + steps_offset
+        self._leading = self.timesteps                     # the injection schedule's noise range is defined on this grid
+        if spacing == "logsnr":
+            self.timesteps = self._logsnr_timesteps(int(self.timesteps[0]))
+            self.skip = None                               # the grid has no constant stride
+        self._index = {int(t): i for i, t in enumerate(self.timesteps)}
+
+    def index(self, t: int):
+        """the position of timestep t on the grid, None off it"""
+        return self._index.get(int(t))
+
+    def _logsnr_timesteps(self, t_hi: int):
+        """n strictly decreasing integers from t_hi to 1, each the timestep whose lambda is nearest its uniform target (ties: the smaller t)"""
+        n = int(self.n)
+        if n < 2 or n > t_hi:
+            raise ValueError(f"timestep spacing 'logsnr': n = {n} timesteps, 2 .. {t_hi} fit between t = {t_hi} and t = 1")
+        if t_hi >= len(self.acp) or not 0.0 < float(self.acp[t_hi]) or not float(self.acp[1]) < 1.0:
+            raise ValueError(f"timestep spacing 'logsnr': the alpha table has no finite log-SNR at t = {t_hi} or t = 1")
+        a = self.acp[1:t_hi + 1].astype(np.float64)
+        lam = 0.5 * np.log(a / (1.0 - a))                          # lam[t - 1] = lambda(t), decreasing in t
+        target = lam[-1] + np.arange(n) * (lam[0] - lam[-1]) / (n - 1)
+        ts = [int(np.argmin(np.abs(lam - tg))) + 1 for tg in target]    # argmin takes the first minimum
+        ts[0] = t_hi
+        for i in range(1, n):
+            ts[i] = min(ts[i], ts[i - 1] - 1)
+        ts[n - 1] = 1
+        for i in range(n - 2, -1, -1):
+            ts[i] = max(ts[i], ts[i + 1] + 1)
+        return np.asarray(ts, np.int64)
 
     def alpha(self, t: int):
         return self.acp[int(t)] if t >= 0 else self.final_alpha_cumprod
 
+    def next_alpha(self, t: int):
+        """the alpha a step from t moves to: alpha(t - skip) on the 'leading' grid (also off the grid), the following entry's alpha on the
+        'logsnr' grid, final_alpha_cumprod behind its last entry"""
+        t = int(t)
+        if self.skip is not None:
+            return self.alpha(t - self.skip)
+        i = self.index(t)
+        if i is None:                                      # this spacing has no stride to fall back on
+            raise ValueError(f"timestep {t} is not on the 'logsnr' grid")
+        return self.alpha(int(self.timesteps[i + 1])) if i + 1 < len(self.timesteps) else self.final_alpha_cumprod
+
     def injection_schedule(self, ratio: float):
         k = int(self.n * ratio)
+        if self.skip is None:                              # 'logsnr': the NOISE range of the leading grid's first k timesteps
+            if k <= 0:
+                return set()
+            floor = int(self._leading[min(k, len(self._leading)) - 1])
+            return set(int(t) for t in self.timesteps if int(t) >= floor)
         return set(int(t) for t in self.timesteps[:k]) if k >= 0 else set()
+
+
+class SolverPhase:
+    """the host's bookkeeping of solver="dpmpp2m": coeffs(t) -> the (cx, c0, c1) of the step at t and remembers it.  A step is second order
+    exactly when the previous coeffs() call was for the preceding schedule entry, first order otherwise (the first step, any out-of-order or
+    off-grid call); the injection state does not enter."""
+
+    def __init__(self, schedule: VideoSchedule):
+        self.schedule, self.prev = schedule, None
+
+    def set_previous(self, t):
+        """declare the step that ran last: the one for timestep t (its x0 is what the history buffer holds), or None for no usable history.
+        For callers that put a state and a history in place themselves (tools/video_solver_cost.py times a second-order step this way)."""
+        self.prev = None if t is None else self.schedule.index(t)
+
+    def coeffs(self, t: int):
+        from .solver import video_multistep_coeffs
+        sch, t = self.schedule, int(t)
+        i = sch.index(t)
+        second = i is not None and i > 0 and self.prev == i - 1
+        self.prev = None                                   # a refused step leaves no history behind
+        a = sch.alpha(t) if 0 <= t < len(sch.acp) else 0.0
+        out = video_multistep_coeffs(t, sch.alpha(int(sch.timesteps[i - 1])) if second else None, a, sch.next_alpha(t) if float(a) > 0 else 0.0, second)
+        self.prev = i
+        return out
 
 
 def alphas_from_scheduler_config(cfg: dict):
@@ -90,17 +170,31 @@ class FeatureInjector:
         return features
 
 
+def _check_solver(solver):
+    if solver not in SOLVERS:
+        raise ValueError(f"solver={solver!r}: one of {SOLVERS}")
+    return solver != "ddim"
+
+
 @torch.no_grad()
-def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None):
+def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None,
+                solver: str = "ddim"):
     """pipeline_i2vgen_xl.py:680-719.  unet(latent_model_input [2B,C,F,H,W], t) -> v-prediction of the same shape (the
     caller closes over prompt/image conditioning; an i2vgen plan behind it needs its `inject` flag set for t, from
-    injection_active); latents [B,C,F,H,W] on the GPU in the model dtype."""
+    injection_active); latents [B,C,F,H,W] on the GPU in the model dtype.  solver="dpmpp2m": every step is tmix_vpred_step_ms on the
+    model dtype with an fp32 history of x0."""
+    ms = _check_solver(solver)
     x = latents.contiguous()
+    if ms:
+        phase, hist = SolverPhase(schedule), torch.zeros_like(x, dtype=torch.float32)
     for t in schedule.timesteps:
         if injector is not None:
             injector.register_time(t)
         v = unet(torch.cat([x, x]), int(t)).contiguous()
-        x = ops.vpred_step(x, v, guidance_scale, schedule.alpha(int(t)), schedule.alpha(int(t) - schedule.skip))
+        if ms:
+            x = ops.vpred_step_ms(x, v, guidance_scale, schedule.alpha(int(t)), phase.coeffs(int(t)), hist)
+        else:
+            x = ops.vpred_step(x, v, guidance_scale, schedule.alpha(int(t)), schedule.next_alpha(int(t)))
     return x
 
 
@@ -111,35 +205,50 @@ class VideoSampler:
     device parameter buffer).  With graphs (default) that sequence is captured once per injection state (the injection ops are
     decided at record time) and a timestep is one 32-byte upload from a pinned staging ring plus one replay; use_graphs=False issues
     the same launches eagerly.  Video s of a batch is bit for bit what sample_loop gives for it alone (tmix_vpred_step_dev is
-    tmix_vpred_step per element)."""
+    tmix_vpred_step per element).
 
-    def __init__(self, plan, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None, use_graphs: bool = True):
+    solver="dpmpp2m" (DESIGN.md 7j): the step ends in tmix_vpred_step_ms_dev instead, on one fp32 history buffer `x0_prev` of the state's
+    shape; params is then {t, sa, s1, cx, c0, c1, g, 0} and the graphs are keyed (inject, "ms").  The order of a step sits in the uploaded
+    coefficients (SolverPhase), so one graph serves both orders and a step stays one 32-byte upload and one replay."""
+
+    def __init__(self, plan, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None, use_graphs: bool = True,
+                 solver: str = "ddim"):
         self.plan, self.schedule, self.g, self.injector, self.use_graphs = plan, schedule, float(guidance_scale), injector, use_graphs
+        self.solver, self.ms = solver, _check_solver(solver)
         cfg = plan.cfg
         dev = plan.plans[0].dev
         self.state = torch.zeros(plan.videos, cfg.in_channels, plan.frames, plan.h, plan.w, device=dev, dtype=torch.float32)
-        self.params = torch.zeros(8, device=dev, dtype=torch.float32)           # {t, sa, s1, sa_next, s1_next, g, -, -}
+        self.params = torch.zeros(8, device=dev, dtype=torch.float32)           # {t, sa, s1, sa_next, s1_next, g, -, -}; solver: {t, sa, s1, cx, c0, c1, g, -}
         # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it has
         # completed (as the image sampler's step_params)
         self._hp = torch.zeros(64, 8, dtype=torch.float32).pin_memory()
         self._hp_ev = [None] * self._hp.shape[0]
         self._hp_i = 0
         self.graphs = {}
+        self.x0_prev = torch.zeros_like(self.state) if self.ms else None
+        self.phase = SolverPhase(schedule) if self.ms else None
 
     def _enqueue(self):
         (xu, tu, eu), (xc, tc, ec) = self.plan.halves
         ops.video_step_prologue(self.state, xu, tu, xc, tc, self.params)
         self.plan.run()
-        ops.vpred_step_dev(self.state, eu, ec, self.params)
+        if self.ms:
+            ops.vpred_step_ms_dev(self.state, eu, ec, self.x0_prev, self.params)
+        else:
+            ops.vpred_step_dev(self.state, eu, ec, self.params)
 
     def _upload(self, t):
         sch = self.schedule
+        coeffs = self.phase.coeffs(t) if self.ms else None          # first: a refused step rewrites no staging slot
         i = self._hp_i
         self._hp_i = (i + 1) % self._hp.shape[0]
         if self._hp_ev[i] is not None:
             self._hp_ev[i].synchronize()
         hp = self._hp[i]
-        ops.video_step_params(t, self.g, sch.alpha(int(t)), sch.alpha(int(t) - sch.skip), out=hp)
+        if self.ms:
+            ops.video_step_params_ms(t, self.g, sch.alpha(int(t)), coeffs, out=hp)
+        else:
+            ops.video_step_params(t, self.g, sch.alpha(int(t)), sch.next_alpha(int(t)), out=hp)
         self.params.copy_(hp, non_blocking=True)
         self._hp_ev[i] = torch.cuda.Event()
         self._hp_ev[i].record()
@@ -154,16 +263,20 @@ class VideoSampler:
         if not self.use_graphs:
             self._enqueue()
             return
-        g = self.graphs.get(inject)
+        key = (inject, "ms") if self.ms else inject
+        g = self.graphs.get(key)
         if g is None:
             self._enqueue()                               # warm-up outside capture; it has already performed this step
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             keep = self.state.clone()
+            keep_h = self.x0_prev.clone() if self.ms else None
             with torch.cuda.graph(g):
                 self._enqueue()
             self.state.copy_(keep)
-            self.graphs[inject] = g
+            if self.ms:
+                self.x0_prev.copy_(keep_h)
+            self.graphs[key] = g
             return
         g.replay()
 
