@@ -61,6 +61,10 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          the n_timesteps uniformly in log-SNR between the 'leading' grid's first timestep and t = 1, the fusion window
                          keeping its noise range.  Meant for a small --n_timesteps (10 .. 20); the defaults (ddim, leading) are today's
                          run bit for bit.  --solver dpmpp2m does not combine with --keep_latents / --keep_image
+  --guidance_rescale PHI std-matched CFG (arXiv:2305.08891 section 3.4, diffusers' guidance_rescale): in every step each concept row's guided
+                         prediction is scaled by PHI * sd(conditional) / sd(guided) + (1 - PHI), per UNet row (on a canvas: per window), against
+                         the over-exposed look of a high --guidance_scale.  0 (default): off, today's run bit for bit; 0.7 is the paper's
+                         value.  Two small launches per step, no UNet call.  Does not combine with --keep_latents / --keep_image
   --num_seeds N          N trajectories, seeds seed..seed+N-1 (trajectory i is exactly what `--seed seed+i` alone produces: its
                          x_T comes from its own generator), co-batched --seeds_per_batch at a time
   --gpus G               shard those seeds round-robin over G GPUs of this node: the script starts one process per GPU itself
@@ -149,6 +153,9 @@ def build_parser():
     p.add_argument('--window_overlap', type=int, default=-1, help='minimum overlap of neighbouring windows in pixels (default: half the smaller window side)')
     p.add_argument('--solver', type=str, default='ddim', choices=['ddim', 'dpmpp2m'],
                    help='dpmpp2m: second-order multistep steps on the blended Tweedie estimate behind the first timestep (ddim: the reference\'s steps)')
+    p.add_argument('--guidance_rescale', type=float, default=0.0,
+                   help='PHI in [0, 1]: scale every guided prediction back towards the standard deviation of its conditional one '
+                        '(0: off; 0.7 is the value of arXiv:2305.08891)')
     p.add_argument('--timestep_spacing', type=str, default='leading', choices=['leading', 'logsnr'],
                    help="logsnr: n_timesteps uniform in log-SNR from the 'leading' grid's first timestep down to t = 1")
     p.add_argument('--num_seeds', type=int, default=1, help='trajectories to sample: seeds seed..seed+n-1')
@@ -329,10 +336,18 @@ def save_soft_weights(opt, tw, side_dir):
 
 
 def check_solver_args(opt):
-    """--solver / --timestep_spacing: refuses what the sampler would refuse, before anything touches the GPU"""
+    """--solver / --timestep_spacing / --guidance_rescale: refuses what the sampler would refuse, before anything touches the GPU"""
     if opt.solver != 'ddim' and (opt.keep_latents or opt.keep_image):
         flag = '--keep_latents' if opt.keep_latents else '--keep_image'
         raise SystemExit(f'--solver {opt.solver} does not combine with {flag}: the keep region exists on the --solver ddim step only')
+    from tweediemix_amd.guidance import validate_phi
+    try:
+        phi = validate_phi(opt.guidance_rescale, '--guidance_rescale')
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if phi > 0.0 and (opt.keep_latents or opt.keep_image):
+        flag = '--keep_latents' if opt.keep_latents else '--keep_image'
+        raise SystemExit(f'--guidance_rescale {phi} does not combine with {flag}: the keep region exists on the unscaled step only')
     if opt.timestep_spacing == 'logsnr':
         from tweediemix_amd.schedule import Schedule
         try:
@@ -597,7 +612,7 @@ def main(argv=None):
     tw = S.Tweediemix(opt, W, te, ts, provider, concept_num=K, lora=LORA,
                       strict_reference=strict, use_graphs=not opt.no_graphs, n_seeds=per, n_streams=opt.streams, vae=vae,
                       fp8=(opt.dtype == 'fp8'), attention_masks=attn, mask_soften=soften,
-                      solver=opt.solver, timestep_spacing=opt.timestep_spacing,
+                      solver=opt.solver, timestep_spacing=opt.timestep_spacing, guidance_rescale=opt.guidance_rescale,
                       **(dict(canvas={k: canvas[k] for k in ('height', 'width', 'overlap')}) if canvas else {}))
     if vae_scaling:                                       # fusion_sampling.py:518 divides by vae.config.scaling_factor
         tw.vae_scaling_factor = float(vae_scaling)

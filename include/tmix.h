@@ -114,6 +114,34 @@ int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps, int eps_dt
 int tmix_fused_tweedie_step_ms_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
                                    int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
                                    int64_t hw, int mode, int rows, int seeds, const float* params, void* stream);
+/* GUIDANCE RESCALE (no reference counterpart; Lin et al., arXiv:2305.08891, section 3.4, diffusers' `guidance_rescale`): every guided prediction
+ * e_r = cfg(eps_0, eps_r, g) a step forms is scaled back towards the standard deviation of the conditional prediction eps_r it came from.
+ * tmix_cfg_rescale_factors writes, for `seeds` seeds over eps [seeds][rows][n] (n = channels*hw), factors [seeds][rows-1] fp32:
+ *   e_r[i]  = the step kernels' cfg (three operations, each rounded to fp16 when eps_dtype is TMIX_F16), g = params[g_slot] read ON THE DEVICE
+ *             (g_slot 6: the params of tmix_fused_tweedie_step_dev, 7: of tmix_fused_tweedie_step_ms_dev; params holds >= 8 floats)
+ *   sd_c, sd_e  the standard deviations of eps_r and of e_r over the row's n elements (denominator n - 1), in fp64
+ *   factors[s][r-1] = fp32( phi*sd_c/sd_e + (1 - phi) ), evaluated in fp64 and rounded once;
+ *                     1.0f where sd_e is zero or a variance is not finite (OUR choice: diffusers produces inf / nan there)
+ * for the rows the mode reads -- PLAIN: r = 1; FUSION and RESAMPLE: r = 1..K -- and 1.0f for every other r.  Statistics are per UNet row.
+ *   ws      device workspace of tmix_cfg_rescale_ws_doubles(rows, seeds) doubles (0: rows outside 2..256 or seeds outside 1..65535), 8-byte
+ *           aligned; no initial contents required (every slot is written before it is read)
+ * Two launches on `stream`: partial sums over a fixed partition of every row (independent of the data, no atomics), then one lane per
+ * (seed, row) adds them in index order -- the factors are bit-reproducible run to run.  eps and params are only read.
+ * TMIX_EINVAL: a null pointer, bad eps_dtype / mode, K < 1 (FUSION, RESAMPLE), g_slot outside 0..7, phi outside [0, 1] or not finite.
+ * TMIX_ESHAPE: n < 2, rows below the mode's need (PLAIN 2, else K + 1) or above 256, seeds outside 1..65535.  All before any launch.
+ * tmix_fused_tweedie_step_rs_dev / _ms_rs_dev: tmix_fused_tweedie_step_dev / _ms_dev with one more argument, `factors` [seeds][rows-1] (behind
+ * params): wherever the step uses e_r it uses rnd(factors[s][r-1] * e_r) (rnd: to fp16 for TMIX_F16, else nothing) -- FUSION rows 1..K, PLAIN
+ * row 1, RESAMPLE the multi-concept row 1 and the single rows 2..K.  The move's noise term stays eps_0; everything else is the parent entry's.
+ * With all factors 1.0f the results are the parent entry's bit for bit.  TMIX_EINVAL on null factors; otherwise the parent's checks. */
+int64_t tmix_cfg_rescale_ws_doubles(int rows, int seeds);
+int tmix_cfg_rescale_factors(const void* eps, int eps_dtype, float* factors, double* ws, int K, int channels, int64_t hw, int mode,
+                             int rows, int seeds, const float* params, int g_slot, float phi, void* stream);
+int tmix_fused_tweedie_step_rs_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                   int64_t mask_seed_stride, float* out_x, float* out_x0, int K, int channels,
+                                   int64_t hw, int mode, int rows, int seeds, const float* params, const float* factors, void* stream);
+int tmix_fused_tweedie_step_ms_rs_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                      int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
+                                      int64_t hw, int mode, int rows, int seeds, const float* params, const float* factors, void* stream);
 /* Head of the captured step (fusion_sampling.py:324-327, `latent_model_input = torch.cat([x] * rows)`, and the timestep
  * argument of the UNet call :340): latent[(s*rows + r)][n] = x[s][n] for every row r, t_dev[s*rows + r] = params[0]. */
 int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,

@@ -1,0 +1,136 @@
+// cfg_rescale.hip -- guidance rescale (Lin et al., arXiv:2305.08891, section 3.4): per eps row the factor that brings the guided prediction
+// e_r = cfg(eu, ec_r, g) back to the standard deviation of the conditional one, f_r = phi sd(ec_r) / sd(e_r) + (1 - phi)  (DESIGN.md 7k).
+// Two launches, back to back on the caller's stream: partial sums over a FIXED partition of the row (RS_P workgroups, whatever the data), then one
+// lane per (seed, row) adds the partials in index order.  No atomics, no workgroup waits for another, every workspace slot is written before it is
+// read, and the summation order is a function of (n, RS_P, RS_THREADS) alone: the factors are the same bits run after run.
+// e_r is formed by tweedie_step.hip's cfg<DT> operation for operation (rnd<DT> included; compiled with -ffp-contract=off like that file), so the
+// statistics are those of the very values the step kernel will scale.
+#include "common.h"
+
+namespace {
+
+template <int DT> struct EpsT;
+template <> struct EpsT<TMIX_F32>  { typedef float  T; static __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; } };
+template <> struct EpsT<TMIX_F16>  { typedef __half T; static __device__ __forceinline__ float ld(const __half* p, int64_t i) { return __half2float(p[i]); } };
+template <> struct EpsT<TMIX_BF16> { typedef bf16_t T; static __device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); } };
+
+// rounding point of the reference's autocast path (only when eps is fp16), as in tweedie_step.hip: the fp32 RESULT is rounded to fp16; the empty
+// asm keeps LLVM from folding mul+convert into the single-rounding v_fma_mixlo_f16
+template <int DT> __device__ __forceinline__ float rnd(float v) {
+    if constexpr (DT == TMIX_F16) {
+        asm volatile("" : "+v"(v));
+        return __half2float(__float2half_rn(v));
+    } else return v;
+}
+
+template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float g) {
+    const float d = rnd<DT>(ec - eu);
+    const float gd = rnd<DT>(g * d);
+    return rnd<DT>(eu + gd);
+}
+
+constexpr int RS_P = 32;            // workgroups per (row, seed): fixed, so the partition (and with it the bits of the factors) never depends on the data
+constexpr int RS_THREADS = 256;
+constexpr int RS_WAVES = RS_THREADS / 64;
+
+__device__ __forceinline__ double wave_sum(double v) {      // wave64 butterfly: every lane ends with the same sum, added in the same order
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// grid (RS_P, rows - 1, seeds).  Workgroup (p, r - 1, s) reads elements p * RS_THREADS + tid + k * RS_P * RS_THREADS of eu and ec_r once and writes
+// {S_c, Q_c, S_e, Q_e} to slot ws[s][r - 1][p]: sum and sum of squares of ec_r and of e_r, in fp64, of the values MINUS the row's element 0 (the
+// difference of two fp32 values in fp64; the variance does not see the shift).  The shift keeps a constant row at S = Q = 0 exactly and takes the
+// mean^2 / variance term out of the one-pass formula's error.  Rows the mode does not read (r > used) are left alone: finalise does not read them.
+template <int DT>
+__global__ void __launch_bounds__(RS_THREADS)
+rescale_partials_kernel(const typename EpsT<DT>::T* __restrict__ eps, double* __restrict__ ws, int64_t n, int rows, int used,
+                        const float* __restrict__ prm, int g_slot) {
+    const int r = blockIdx.y + 1;
+    if (r > used) return;
+    const int64_t sd = blockIdx.z;
+    const float g = prm[g_slot];
+    const typename EpsT<DT>::T* eu = eps + sd * rows * n;
+    const typename EpsT<DT>::T* ec = eu + (int64_t)r * n;
+    const float c0 = EpsT<DT>::ld(ec, 0);
+    const float e0 = cfg<DT>(EpsT<DT>::ld(eu, 0), c0, g);
+    double sc = 0.0, qc = 0.0, se = 0.0, qe = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x; i < n; i += (int64_t)RS_P * RS_THREADS) {
+        const float c = EpsT<DT>::ld(ec, i);
+        const float e = cfg<DT>(EpsT<DT>::ld(eu, i), c, g);
+        const double dc = (double)c - (double)c0, de = (double)e - (double)e0;
+        sc = sc + dc; qc = qc + dc * dc;
+        se = se + de; qe = qe + de * de;
+    }
+    sc = wave_sum(sc); qc = wave_sum(qc); se = wave_sum(se); qe = wave_sum(qe);
+    __shared__ double part[RS_WAVES][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { part[wave][0] = sc; part[wave][1] = qc; part[wave][2] = se; part[wave][3] = qe; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double a = part[0][threadIdx.x];
+        for (int w = 1; w < RS_WAVES; ++w) a = a + part[w][threadIdx.x];
+        ws[((sd * (rows - 1) + (r - 1)) * RS_P + blockIdx.x) * 4 + threadIdx.x] = a;
+    }
+}
+
+// one lane per (seed, row): the RS_P partials in index order, the variances (Q - S*S/n) / (n - 1), the factor in fp64 rounded once to fp32.
+// f = 1 where sd_e is zero or a variance is not finite (diffusers would give inf / nan there), and for the rows the mode does not read.
+__global__ void __launch_bounds__(RS_THREADS)
+rescale_finalise_kernel(const double* __restrict__ ws, float* __restrict__ factors, int64_t n, int rows, int used, int seeds, float phi) {
+    const int idx = blockIdx.x * RS_THREADS + threadIdx.x;
+    if (idx >= seeds * (rows - 1)) return;
+    float f = 1.0f;
+    if (idx % (rows - 1) < used) {
+        const double* p = ws + (int64_t)idx * RS_P * 4;
+        double sc = 0.0, qc = 0.0, se = 0.0, qe = 0.0;
+        for (int k = 0; k < RS_P; ++k) { sc = sc + p[4 * k]; qc = qc + p[4 * k + 1]; se = se + p[4 * k + 2]; qe = qe + p[4 * k + 3]; }
+        const double dn = (double)n;
+        const double vc = (qc - sc * sc / dn) / (dn - 1.0), ve = (qe - se * se / dn) / (dn - 1.0);
+        if (isfinite(vc) && isfinite(ve) && ve > 0.0) {
+            const double ph = (double)phi;
+            f = (float)(ph * sqrt(vc > 0.0 ? vc : 0.0) / sqrt(ve) + (1.0 - ph));
+        }
+    }
+    factors[idx] = f;
+}
+
+template <int DT>
+int launch_rescale(const void* eps, float* factors, double* ws, int64_t n, int rows, int used, int seeds, const float* prm, int g_slot, float phi,
+                   hipStream_t st) {
+    typedef typename EpsT<DT>::T T;
+    rescale_partials_kernel<DT><<<dim3(RS_P, (unsigned)(rows - 1), (unsigned)seeds), RS_THREADS, 0, st>>>((const T*)eps, ws, n, rows, used, prm, g_slot);
+    TMIX_LAUNCH_CHECK();
+    const int lanes = seeds * (rows - 1);
+    rescale_finalise_kernel<<<(unsigned)((lanes + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(ws, factors, n, rows, used, seeds, phi);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t tmix_cfg_rescale_ws_doubles(int rows, int seeds) {
+    if (rows < 2 || rows > 256 || seeds < 1 || seeds > 65535) return 0;
+    return (int64_t)seeds * (rows - 1) * RS_P * 4;
+}
+
+extern "C" int tmix_cfg_rescale_factors(const void* eps, int eps_dtype, float* factors, double* ws, int K, int channels, int64_t hw, int mode,
+                                        int rows, int seeds, const float* params, int g_slot, float phi, void* stream) {
+    if (!eps || !factors || !ws || !params) TMIX_FAIL(TMIX_EINVAL, "cfg_rescale_factors: null pointer");
+    if (eps_dtype != TMIX_F32 && eps_dtype != TMIX_F16 && eps_dtype != TMIX_BF16) TMIX_FAIL(TMIX_EINVAL, "cfg_rescale_factors: bad eps dtype %d", eps_dtype);
+    if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "cfg_rescale_factors: bad mode %d", mode);
+    if (mode != TMIX_STEP_PLAIN && K < 1) TMIX_FAIL(TMIX_EINVAL, "cfg_rescale_factors: mode %d needs K>=1", mode);
+    if (g_slot < 0 || g_slot > 7) TMIX_FAIL(TMIX_EINVAL, "cfg_rescale_factors: g_slot %d outside 0..7", g_slot);
+    if (!(phi >= 0.0f && phi <= 1.0f)) TMIX_FAIL(TMIX_EINVAL, "cfg_rescale_factors: phi %g outside [0, 1]", (double)phi);
+    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "cfg_rescale_factors: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
+    const int64_t n = (int64_t)channels * hw;
+    if (n < 2) TMIX_FAIL(TMIX_ESHAPE, "cfg_rescale_factors: a standard deviation needs n >= 2 elements, got %lld", (long long)n);
+    const int used = mode == TMIX_STEP_PLAIN ? 1 : K;
+    if (rows < used + 1 || rows > 256) TMIX_FAIL(TMIX_ESHAPE, "cfg_rescale_factors: mode %d needs %d..256 eps rows per seed, got %d", mode, used + 1, rows);
+    hipStream_t st = (hipStream_t)stream;
+    switch (eps_dtype) {
+    case TMIX_F32:  return launch_rescale<TMIX_F32>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, st);
+    case TMIX_F16:  return launch_rescale<TMIX_F16>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, st);
+    default:        return launch_rescale<TMIX_BF16>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, st);
+    }
+}

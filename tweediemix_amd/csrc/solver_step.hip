@@ -31,11 +31,20 @@ template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float
 // prm = {t, sa, s1, cx, c0, c1, is_last, g} in device memory (one captured launch serves every timestep and both orders); blockIdx.y walks
 // co-batched seeds (x / out_x / out_x0 / x0_prev: [seeds][n], eps: [seeds][rows][n], masks: [seeds][K][hw] or shared).  x may alias out_x:
 // every array is read at i before it is written at i.  x0_prev is read AND written, so it carries no __restrict__.
-template <int DT, int MODE>
+// RESCALE: the presence of ONE trailing RescaleArgs kernel argument (the pack RsT is empty or {RescaleArgs}, tweedie_step.hip's KeepArgs mechanism):
+// every guided prediction e_r becomes rnd<DT>(f_r * e_r) with f_r = fac[seed][r - 1] (layout [seeds][rows - 1]), exactly as in that
+// file's kernel; without it the kernel has the arguments, and compiles to the instructions, it had before.
+struct RescaleArgs { const float* fac; };
+__device__ __forceinline__ RescaleArgs rescale_args(const RescaleArgs& r) { return r; }
+
+template <int DT, int MODE, typename... RsT>
 __global__ void __launch_bounds__(256)
 solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps, const float* __restrict__ masks, float* out_x,
                    float* __restrict__ out_x0, float* x0_prev, int K, int64_t n, int64_t hw, const float* __restrict__ prm, int rows,
-                   int64_t mask_seed_stride) {
+                   int64_t mask_seed_stride, RsT... rs) {
+    constexpr bool RS = sizeof...(RsT) != 0;
+    const float* fac = nullptr;
+    if constexpr (RS) fac = rescale_args(rs...).fac + (int64_t)blockIdx.y * (rows - 1);
     const float sa = prm[1], s1 = prm[2], cx = prm[3], c0 = prm[4], c1 = prm[5], g = prm[7];
     const bool is_last = prm[6] != 0.0f;
     const int64_t sd = blockIdx.y;
@@ -51,12 +60,14 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
             const int64_t px = i % hw;
             x0 = 0.0f;
             for (int c = 0; c < K; ++c) {
-                const float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
+                float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
+                if constexpr (RS) e = rnd<DT>(fac[c] * e);
                 const float t = (xv - rnd<DT>(s1 * e)) / sa;
                 x0 = x0 + masks[(int64_t)c * hw + px] * t;
             }
         } else {
-            const float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+            float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+            if constexpr (RS) e = rnd<DT>(fac[0] * e);
             x0 = (xv - rnd<DT>(s1 * e)) / sa;
         }
         float m = c0 * x0;
@@ -67,17 +78,17 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
     }
 }
 
-template <int DT>
+template <int DT, typename... RsT>      // RsT: empty, or {RescaleArgs}
 int launch_ms(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, float* x0_prev, int K, int64_t n,
-              int64_t hw, int mode, int rows, int seeds, const float* prm, hipStream_t st) {
+              int64_t hw, int mode, int rows, int seeds, const float* prm, hipStream_t st, RsT... rs) {
     typedef typename EpsT<DT>::T T;
     int64_t bx = (n + 255) / 256; if (bx > 2048) bx = 2048;
     const dim3 grid((unsigned)bx, (unsigned)seeds);
     const T* e = (const T*)eps;
     if (mode == TMIX_STEP_FUSION)
-        solver_step_kernel<DT, TMIX_STEP_FUSION><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss);
+        solver_step_kernel<DT, TMIX_STEP_FUSION, RsT...><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss, rs...);
     else
-        solver_step_kernel<DT, TMIX_STEP_PLAIN><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss);
+        solver_step_kernel<DT, TMIX_STEP_PLAIN, RsT...><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss, rs...);
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
 }
@@ -192,4 +203,26 @@ extern "C" int tmix_fused_tweedie_step_ms_dev(const float* x, const void* eps, i
     case TMIX_BF16: return launch_ms<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st);
     }
     TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: bad eps dtype %d", eps_dtype);
+}
+
+extern "C" int tmix_fused_tweedie_step_ms_rs_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                                 int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
+                                                 int64_t hw, int mode, int rows, int seeds, const float* params, const float* factors, void* stream) {
+    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: null pointer");
+    if (!x0_prev) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: null x0_prev (the history buffer is read and written by every step)");
+    if (!factors) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: null factors");
+    if (mode != TMIX_STEP_FUSION && mode != TMIX_STEP_PLAIN) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: bad mode %d (FUSION or PLAIN)", mode);
+    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: FUSION needs masks and K>=1");
+    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_rs_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
+    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
+    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_rs_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
+    const int64_t n = (int64_t)channels * hw;
+    const RescaleArgs rs = {factors};
+    hipStream_t st = (hipStream_t)stream;
+    switch (eps_dtype) {
+    case TMIX_F32:  return launch_ms<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st, rs);
+    case TMIX_F16:  return launch_ms<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st, rs);
+    case TMIX_BF16: return launch_ms<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st, rs);
+    }
+    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: bad eps dtype %d", eps_dtype);
 }

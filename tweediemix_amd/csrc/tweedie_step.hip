@@ -38,6 +38,12 @@ template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float
 // the instructions, it had before the keep region existed.
 struct KeepArgs { const float* x0; const float* eps; const float* w; int64_t x0_stride, eps_stride, w_stride; };
 __device__ __forceinline__ KeepArgs keep_args(const KeepArgs& k) { return k; }
+// RESCALE (with DEV; the same mechanism, the other type of the ONE trailing argument): every guided prediction e_r the mode forms becomes
+// rnd<DT>(f_r * e_r) with f_r = fac[seed][r - 1] (layout [seeds][rows - 1]; tmix_cfg_rescale_factors writes it: DESIGN.md 7k).  f_r = 1.0f gives e_r back
+// bit for bit.  The move's noise term stays the unconditional eu.
+struct RescaleArgs { const float* fac; };
+__device__ __forceinline__ RescaleArgs rescale_args(const RescaleArgs& r) { return r; }
+template <typename A, typename... T> constexpr bool pack_is = sizeof...(T) == 1 && (__is_same(T, A) && ...);
 
 template <int DT, int MODE, int DEV = 0, typename... KeepT>
 __global__ void __launch_bounds__(256)
@@ -45,16 +51,19 @@ tweedie_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps
                     const float* __restrict__ masks, float* out_x, float* __restrict__ out_x0,
                     int K, int64_t n, int64_t hw, float g, float sa, float s1, float sa_n, float s1_n, int is_last,
                     const float* __restrict__ prm = nullptr, int rows = 0, int64_t mask_seed_stride = 0, KeepT... keep) {
-    constexpr bool KEEP = sizeof...(KeepT) != 0;
-    static_assert(!KEEP || DEV, "the keep region exists in the device-parameter form only");
+    constexpr bool KEEP = pack_is<KeepArgs, KeepT...>, RS = pack_is<RescaleArgs, KeepT...>;
+    static_assert(sizeof...(KeepT) == 0 || ((KEEP || RS) && DEV), "the keep region and the rescale factors exist in the device-parameter form only");
     KeepArgs kp = {};
     if constexpr (KEEP) kp = keep_args(keep...);
+    const float* fac = nullptr;
+    if constexpr (RS) fac = rescale_args(keep...).fac;
     if constexpr (DEV) {
         sa = prm[1]; s1 = prm[2]; sa_n = prm[3]; s1_n = prm[4]; is_last = prm[5] != 0.0f; g = prm[6];
         const int64_t sd = blockIdx.y;
         x += sd * n; out_x += sd * n; eps += sd * rows * n; masks += sd * mask_seed_stride;
         if (out_x0) out_x0 += sd * n;
         if constexpr (KEEP) { kp.x0 += sd * kp.x0_stride; kp.eps += sd * kp.eps_stride; kp.w += sd * kp.w_stride; }
+        if constexpr (RS) fac += sd * (rows - 1);
     }
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -65,18 +74,22 @@ tweedie_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps
             const int64_t p = i % hw;
             x0 = 0.0f;
             for (int c = 0; c < K; ++c) {
-                const float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
+                float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
+                if constexpr (RS) e = rnd<DT>(fac[c] * e);
                 const float t = (xv - rnd<DT>(s1 * e)) / sa;
                 x0 = x0 + masks[(int64_t)c * hw + p] * t;
             }
         } else if constexpr (MODE == TMIX_STEP_PLAIN) {
-            const float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+            float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+            if constexpr (RS) e = rnd<DT>(fac[0] * e);
             x0 = (xv - rnd<DT>(s1 * e)) / sa;
         } else {   // RESAMPLE: (K-1)*x0_multi - sum_{c<K-1} x0_single_c
-            const float em = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+            float em = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+            if constexpr (RS) em = rnd<DT>(fac[0] * em);
             x0 = (float)(K - 1) * ((xv - rnd<DT>(s1 * em)) / sa);
             for (int c = 0; c < K - 1; ++c) {
-                const float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(2 + c) * n + i), g);
+                float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(2 + c) * n + i), g);
+                if constexpr (RS) e = rnd<DT>(fac[1 + c] * e);
                 x0 = x0 - (xv - rnd<DT>(s1 * e)) / sa;
             }
         }
@@ -133,9 +146,9 @@ int launch_dev(const float* x, const void* eps, const float* masks, int64_t mss,
     return TMIX_OK;
 }
 
-template <int DT>
-int launch_keep(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, int K, int64_t n,
-                int64_t hw, int mode, int rows, int seeds, const float* prm, const KeepArgs& kp, hipStream_t st) {
+template <int DT, typename ExtraT>      // ExtraT: KeepArgs or RescaleArgs, the one trailing kernel argument
+int launch_extra(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, int K, int64_t n,
+                int64_t hw, int mode, int rows, int seeds, const float* prm, const ExtraT& kp, hipStream_t st) {
     typedef typename EpsT<DT>::T T;
     int64_t bx = (n + 255) / 256; if (bx > 2048) bx = 2048;
     const dim3 grid((unsigned)bx, (unsigned)seeds);
@@ -345,11 +358,33 @@ extern "C" int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps,
     const KeepArgs kp = {keep_x0, keep_eps, keep_w, keep_x0_seed_stride, keep_eps_seed_stride, keep_w_seed_stride};
     hipStream_t st = (hipStream_t)stream;
     switch (eps_dtype) {
-    case TMIX_F32:  return launch_keep<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
-    case TMIX_F16:  return launch_keep<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
-    case TMIX_BF16: return launch_keep<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
+    case TMIX_F32:  return launch_extra<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
+    case TMIX_F16:  return launch_extra<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
+    case TMIX_BF16: return launch_extra<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
     }
     TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: bad eps dtype %d", eps_dtype);
+}
+
+extern "C" int tmix_fused_tweedie_step_rs_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
+                                              int64_t mask_seed_stride, float* out_x, float* out_x0, int K, int channels,
+                                              int64_t hw, int mode, int rows, int seeds, const float* params, const float* factors, void* stream) {
+    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: null pointer");
+    if (!factors) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: null factors");
+    if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: bad mode %d", mode);
+    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: FUSION needs masks and K>=1");
+    if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: RESAMPLE needs K>=1");
+    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_rs_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
+    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
+    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_rs_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
+    const int64_t n = (int64_t)channels * hw;
+    const RescaleArgs rs = {factors};
+    hipStream_t st = (hipStream_t)stream;
+    switch (eps_dtype) {
+    case TMIX_F32:  return launch_extra<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, rs, st);
+    case TMIX_F16:  return launch_extra<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, rs, st);
+    case TMIX_BF16: return launch_extra<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, rs, st);
+    }
+    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: bad eps dtype %d", eps_dtype);
 }
 
 extern "C" int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,

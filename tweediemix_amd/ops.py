@@ -114,6 +114,59 @@ def fused_tweedie_step_ms_dev(x, eps, masks, mode, K, params, x0_prev, out_x=Non
     return out_x
 
 
+def cfg_rescale_ws(rows, seeds, device):
+    """the fp64 workspace tmix_cfg_rescale_factors needs for `seeds` seeds of `rows` eps rows (contents irrelevant: written before read)"""
+    nd = int(L.load().tmix_cfg_rescale_ws_doubles(int(rows), int(seeds)))
+    if nd < 1:
+        raise L.TmixError(f"cfg_rescale_ws: rows={rows} (2..256) seeds={seeds} (1..65535)")
+    return torch.empty(nd, device=device, dtype=torch.float64)
+
+
+def cfg_rescale_factors(eps, seeds, mode, K, params, g_slot, phi, out=None, ws=None):
+    """tmix_cfg_rescale_factors: eps [S*rows,C,h,w] f32|f16|bf16, params the step's device buffer (>= 8 floats) with g in slot g_slot (6: the
+    DDIM layout, 7: the multistep layout), phi in [0, 1] -> factors [S, rows-1] fp32 (guidance.rescale_factors_reference per seed)."""
+    from .guidance import validate_phi
+    _need_cuda(eps, params, out, ws)
+    assert eps.is_contiguous() and eps.dim() == 4 and eps.shape[0] % seeds == 0 and params.dtype == torch.float32 and params.numel() >= 8
+    rows = eps.shape[0] // seeds
+    Cc, h, w = eps.shape[1:]
+    if out is None:
+        out = torch.empty(seeds, rows - 1, device=eps.device, dtype=torch.float32)
+    if ws is None:
+        ws = cfg_rescale_ws(rows, seeds, eps.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == seeds * (rows - 1), tuple(out.shape)
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= L.load().tmix_cfg_rescale_ws_doubles(rows, seeds)
+    L.check(L.load().tmix_cfg_rescale_factors(_p(eps), _EPS_DT[eps.dtype], _p(out), _p(ws), K, Cc, h * w, mode, rows, seeds, _p(params),
+                                              int(g_slot), validate_phi(phi, "phi"), _stream()), "tmix_cfg_rescale_factors")
+    return out
+
+
+def fused_tweedie_step_rs_dev(x, eps, masks, mode, K, params, factors, out_x=None, out_x0=None, x0_prev=None):
+    """tmix_fused_tweedie_step_rs_dev, or with x0_prev (the history buffer) tmix_fused_tweedie_step_ms_rs_dev: the arguments of
+    fused_tweedie_step_ms_dev plus factors [S, rows-1] fp32 (cfg_rescale_factors).  out_x may be x itself (in place).  Returns out_x."""
+    _need_cuda(x, eps, masks, params, factors, x0_prev)
+    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and params.dtype == torch.float32 and params.numel() >= 8
+    S, Cc, h, w = x.shape
+    hw = h * w
+    assert eps.shape[0] % S == 0
+    rows = eps.shape[0] // S
+    assert factors.dtype == torch.float32 and factors.is_contiguous() and factors.numel() == S * (rows - 1), tuple(factors.shape)
+    mss = 0
+    if mode == L.STEP_FUSION:
+        assert masks is not None and masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() in (K * hw, S * K * hw)
+        mss = 0 if masks.numel() == K * hw else K * hw
+    if out_x is None:
+        out_x = torch.empty_like(x)
+    head = (_p(x), _p(eps), _EPS_DT[eps.dtype], _p(masks), mss, _p(out_x), _p(out_x0))
+    tail = (K, Cc, hw, mode, rows, S, _p(params), _p(factors), _stream())
+    if x0_prev is None:
+        L.check(L.load().tmix_fused_tweedie_step_rs_dev(*head, *tail), "tmix_fused_tweedie_step_rs_dev")
+    else:
+        assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.shape == x.shape, tuple(x0_prev.shape)
+        L.check(L.load().tmix_fused_tweedie_step_ms_rs_dev(*head, _p(x0_prev), *tail), "tmix_fused_tweedie_step_ms_rs_dev")
+    return out_x
+
+
 def window_consensus(x, groups, offsets, canvas_hw, weight=None):
     """tmix_window_consensus, in place on x [groups * n_win, C, h, w] fp32 (group-major: b = group * n_win + window): every canvas pixel
     that several windows cover becomes their weighted mean in all of them.  offsets [(oy, ox), ...] the windows' corners on the canvas

@@ -14,6 +14,8 @@ Same method names, argument meaning and step semantics as fusion_generation/fusi
   (tmix_fused_tweedie_step_keep_dev) to the level of every state the loop writes,
 * optionally (solver="dpmpp2m") a second-order multistep move on the blended estimate behind the first timestep
   (tmix_fused_tweedie_step_ms_dev), on an optional log-SNR timestep grid (timestep_spacing="logsnr"),
+* optionally (guidance_rescale=phi > 0) the guided prediction of every concept row scaled back towards the standard deviation of its
+  conditional prediction (tmix_cfg_rescale_factors in front of the *_rs_dev form of whichever step entry runs), in every step of every phase,
 * ONE hipGraph per (call kind, step mode) holding the whole step -- latent broadcast + timestep
   (tmix_step_prologue), the UNet launch chains, the fused step for all co-batched seeds: a timestep is one 32-byte
   parameter upload and one graph replay.
@@ -32,6 +34,7 @@ import torch
 from . import lib as L
 from . import ops
 from .schedule import Schedule
+from .guidance import validate_phi
 from .solver import SOLVERS, multistep_coeffs
 from .unet import KVCache, PlanGroup, TokenMapSpec, TokenPropSpec, UNetPlan, UNetWeights
 
@@ -105,13 +108,21 @@ class Tweediemix:
     timestep_spacing  "leading" (the reference's grid) or "logsnr": n_timesteps uniform in log-SNR from the 'leading' grid's first timestep to
                       t = 1 (schedule.Schedule(spacing="logsnr")); skip is then None, and t_cond / t_stop keep their noise range
                       (_window_index).  Independent of `solver`.
+    guidance_rescale  phi in [0, 1], default 0.0 = off (today's entries, launches, graph keys and bits).  phi > 0: in EVERY step -- start phase,
+                      resampling, look-ahead, probe, propagate rounds, fusion and plain steps, DDIM and solver entries, eager, captured and
+                      with a stand-in UNet -- each guided prediction e_r = eu + g (ec_r - eu) is replaced by f_r e_r with
+                      f_r = phi sd(ec_r) / sd(e_r) + (1 - phi) (arXiv:2305.08891 section 3.4; 0.7 is the paper's value): tmix_cfg_rescale_factors
+                      (two small launches on the eps rows the plan has just written) and then tmix_fused_tweedie_step_rs_dev / _ms_rs_dev in place
+                      of the step, in the same captured graph (keys get "rs" appended).  Statistics are per UNet row: on a canvas per window.
+                      Not with set_keep.  DESIGN.md 7k.
     """
 
     def __init__(self, config, weights: UNetWeights, text_embeds, text_embeds_single, mask_provider,
                  concept_num: int, lora: bool = False, strict_reference: bool = True, use_graphs: bool = False,
                  n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None,
-                 mask_soften=None, solver: str = "ddim", timestep_spacing: str = "leading"):
+                 mask_soften=None, solver: str = "ddim", timestep_spacing: str = "leading", guidance_rescale: float = 0.0):
         self.config = config
+        self.guidance_rescale = validate_phi(guidance_rescale)
         if solver not in SOLVERS:
             raise ValueError(f"solver={solver!r}: one of {SOLVERS}")
         self.solver = solver
@@ -205,6 +216,13 @@ class Tweediemix:
         # upload {t, sa, s1, cx, c0, c1, is_last, g} into step_params instead) and which step wrote it: (schedule index, step mode) or None
         self._x0_prev = torch.zeros_like(self.x_state) if solver != "ddim" else None
         self._ms_last = None
+        # guidance_rescale > 0: the factors [seeds][rows - 1] of the step being run and the fp64 workspace of their reduction, allocated once for
+        # the widest call (K + 1 rows; the two-row calls use the front of both) at addresses the captured steps keep
+        self._rs_rows = max(self.concept_num + 1, 2)
+        self._rs_factors = self._rs_ws = None
+        if self.guidance_rescale > 0.0:
+            self._rs_factors = torch.ones(S * (self._rs_rows - 1), device=self.device, dtype=F32)
+            self._rs_ws = ops.cfg_rescale_ws(self._rs_rows, S, self.device)
         self._keep = self._keep_bufs = None    # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
         # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it
         # has completed (the host runs ahead of the device by whole steps)
@@ -267,6 +285,8 @@ class Tweediemix:
         the fixed noise of every seed's kept part.  From the next run_fusion / sample_loop on every step writes
         weight * (sa' x0 + s1' eps) + (1 - weight) * (its own result), with sa' / s1' of the state it writes (tmix_fused_tweedie_step_keep_dev),
         x_T is composited the same way once, and the final latent holds x0 itself.  The tensors are copied: captured steps read these buffers."""
+        if self.guidance_rescale > 0.0:  # a keep entry that takes factors does not exist (yet)
+            raise ValueError(f"set_keep: not with guidance_rescale={self.guidance_rescale} (the keep region exists on the unscaled step only)")
         if self.solver != "ddim":        # the keep term needs sa_next / s1_next, which the multistep entry's eight floats do not carry
             raise ValueError(f"set_keep: not with solver={self.solver!r} (the keep region exists on the solver='ddim' step only)")
         if self.windows is not None:     # the mean of equal values is not always that value bit for bit: the kept region's promise would break
@@ -417,6 +437,18 @@ class Tweediemix:
         hw = self.h * self.w
         head = (self.x_state.data_ptr(), eps_ptr, eps_dt, None if m is None else m.data_ptr(), mss, self.x_state.data_ptr(),
                 self.x0_state.data_ptr(), self.concept_num, 4, hw, mode, rows, self.n_seeds, self.step_params.data_ptr())
+        if self.guidance_rescale > 0.0:  # the factors of these eps rows (g read on the device from the layout the step uploaded), then the rs form of the step
+            if rows > self._rs_rows:
+                raise ValueError(f"guidance_rescale: {rows} eps rows per seed, the buffers were sized for {self._rs_rows}")
+            L.check(lib.tmix_cfg_rescale_factors(eps_ptr, eps_dt, self._rs_factors.data_ptr(), self._rs_ws.data_ptr(), self.concept_num, 4, hw, mode,
+                                                 rows, self.n_seeds, self.step_params.data_ptr(), 7 if ms else 6, self.guidance_rescale, st),
+                    "tmix_cfg_rescale_factors")
+            if ms:
+                L.check(lib.tmix_fused_tweedie_step_ms_rs_dev(*head[:7], self._x0_prev.data_ptr(), *head[7:], self._rs_factors.data_ptr(), st),
+                        "tmix_fused_tweedie_step_ms_rs_dev")
+            else:
+                L.check(lib.tmix_fused_tweedie_step_rs_dev(*head, self._rs_factors.data_ptr(), st), "tmix_fused_tweedie_step_rs_dev")
+            return
         if ms:
             L.check(lib.tmix_fused_tweedie_step_ms_dev(*head[:7], self._x0_prev.data_ptr(), *head[7:], st), "tmix_fused_tweedie_step_ms_dev")
             return
@@ -465,6 +497,8 @@ class Tweediemix:
         # a step captured with a keep region is another graph (another kernel, three more pointers): the ones captured without it stay valid
         # and so is a multistep step (another kernel, one more pointer): one graph serves both orders, the order is in the uploaded coefficients
         gkey = (kind, mode, "ms") if ms is not None else (kind, mode) if self._keep is None else (kind, mode, "keep")
+        if self.guidance_rescale > 0.0:                   # two more launches and another step kernel: graphs of their own
+            gkey = gkey + ("rs",)
         g = self.graphs.get(gkey)
         if g is None:
             self._enqueue_step(kind, mode, ms is not None)    # warm-up outside capture (kernel attributes, lazy module load);
