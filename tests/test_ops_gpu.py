@@ -3,6 +3,7 @@
 
 Tolerances: kernels read bf16 operands and accumulate in fp32; outputs are rounded to bf16 once, so
 |err| <= 2 bf16 ulp of the result (rtol 2^-7) plus an absolute term for cancellation.
+The rounding itself (and anything below the global maximum) is held in test_gemm_numerics_gpu.py: bit-exact and fp64 per-element checks of the GEMM / conv family.
 """
 import numpy as np
 import os
