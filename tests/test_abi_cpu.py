@@ -55,6 +55,54 @@ def test_ops_refuse_cpu_tensors():
         ops.gemm(torch.zeros(64, 64, dtype=torch.bfloat16), torch.zeros(64, 64, dtype=torch.bfloat16))
 
 
+def test_dev_step_entries_validate_alike():
+    """the five device-parameter step entries answer the same bad argument with the same code, each under its own name; RESAMPLE is a bad
+    mode for the two multistep entries only.  No call here is valid as a whole: none gets as far as a launch."""
+    import ctypes as C
+    from tweediemix_amd import lib
+    l = lib.load()
+    f = C.c_void_p(0x1000)                      # never dereferenced: validation fails first
+    # (short name, RESAMPLE allowed, added pointers, call): h is the 14-argument head the entries share, prev / fac / keep the pointers some add
+    entries = [
+        ("tweedie_step_dev", True, (), lambda h, prev=f, fac=f, keep=f: l.tmix_fused_tweedie_step_dev(*h, None)),
+        ("tweedie_step_keep_dev", True, ("keep",), lambda h, prev=f, fac=f, keep=f: l.tmix_fused_tweedie_step_keep_dev(*h, keep, 0, keep, 0, keep, 0, None)),
+        ("tweedie_step_rs_dev", True, ("fac",), lambda h, prev=f, fac=f, keep=f: l.tmix_fused_tweedie_step_rs_dev(*h, fac, None)),
+        ("tweedie_step_ms_dev", False, ("prev",), lambda h, prev=f, fac=f, keep=f: l.tmix_fused_tweedie_step_ms_dev(*h[:7], prev, *h[7:], None)),
+        ("tweedie_step_ms_rs_dev", False, ("prev", "fac"), lambda h, prev=f, fac=f, keep=f: l.tmix_fused_tweedie_step_ms_rs_dev(*h[:7], prev, *h[7:], fac, None)),
+    ]
+    ok = dict(x=f, eps=f, dt=lib.F32, masks=f, mss=0, out_x=f, out_x0=None, K=3, C=4, hw=64, mode=lib.STEP_FUSION, rows=4, seeds=1, prm=f)
+    head = lambda **kw: tuple(dict(ok, **kw).values())
+    bad = [(dict(x=None), lib.EINVAL, b"null pointer"), (dict(eps=None), lib.EINVAL, b"null pointer"),
+           (dict(out_x=None), lib.EINVAL, b"null pointer"), (dict(prm=None), lib.EINVAL, b"null pointer"),
+           (dict(mode=-1), lib.EINVAL, b"bad mode -1"), (dict(mode=3), lib.EINVAL, b"bad mode 3"),
+           (dict(masks=None), lib.EINVAL, b"FUSION needs masks and K>=1"), (dict(K=0), lib.EINVAL, b"FUSION needs masks and K>=1"),
+           (dict(C=0), lib.ESHAPE, b"channels=0 hw=64 seeds=1"), (dict(hw=0), lib.ESHAPE, b"channels=4 hw=0 seeds=1"),
+           (dict(seeds=0), lib.ESHAPE, b"channels=4 hw=64 seeds=0"), (dict(seeds=65536), lib.ESHAPE, b"channels=4 hw=64 seeds=65536"),
+           (dict(rows=3), lib.ESHAPE, b"mode 0 needs 4 eps rows per seed, got 3"),
+           (dict(mode=lib.STEP_PLAIN, rows=1, masks=None), lib.ESHAPE, b"mode 1 needs 2 eps rows per seed, got 1"),
+           (dict(dt=7), lib.EINVAL, b"bad eps dtype 7")]
+    err = l.tmix_last_error_string
+    words = dict(prev=b"null x0_prev", fac=b"null factors", keep=b"null keep pointer")
+    for name, resample, extras, call in entries:
+        own = name.encode() + b": "
+        for kw, code, text in bad:
+            assert call(head(**kw)) == code, (name, kw)
+            assert err().startswith(own + text), (name, kw, err())
+        # RESAMPLE: the DDIM forms take it past the mode check (and stop at the row count here), the multistep forms refuse the mode
+        rs = dict(mode=lib.STEP_RESAMPLE, rows=3)
+        if resample:
+            assert call(head(**rs)) == lib.ESHAPE and err().startswith(own + b"mode 2 needs 4 eps rows per seed, got 3"), (name, err())
+            assert call(head(K=0, **rs)) == lib.EINVAL and err().startswith(own + b"RESAMPLE needs K>=1"), (name, err())
+        else:
+            assert call(head(**rs)) == lib.EINVAL and err().startswith(own + b"bad mode 2 (FUSION or PLAIN)"), (name, err())
+        # the pointers an entry adds: checked behind the null-pointer check and in front of the mode check, x0_prev in front of factors
+        for extra in extras:
+            assert call(head(mode=3), **{extra: None}) == lib.EINVAL and err().startswith(own + words[extra]), (name, extra, err())
+            assert call(head(x=None), **{extra: None}) == lib.EINVAL and err().startswith(own + b"null pointer"), (name, extra, err())
+        if extras:
+            assert call(head(mode=3), **dict.fromkeys(extras)) == lib.EINVAL and err().startswith(own + words[extras[0]]), (name, err())
+
+
 def test_argument_errors_are_reported_before_any_launch():
     """every entry point validates its arguments first and returns a TMIX_E* code with a message (no GPU needed to see that)."""
     import ctypes as C

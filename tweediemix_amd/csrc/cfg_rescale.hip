@@ -3,31 +3,11 @@
 // Two launches, back to back on the caller's stream: partial sums over a FIXED partition of the row (RS_P workgroups, whatever the data), then one
 // lane per (seed, row) adds the partials in index order.  No atomics, no workgroup waits for another, every workspace slot is written before it is
 // read, and the summation order is a function of (n, RS_P, RS_THREADS) alone: the factors are the same bits run after run.
-// e_r is formed by tweedie_step.hip's cfg<DT> operation for operation (rnd<DT> included; compiled with -ffp-contract=off like that file), so the
-// statistics are those of the very values the step kernel will scale.
-#include "common.h"
+// e_r is formed by the step kernels' own cfg<DT> (step_core.h; compiled with -ffp-contract=off like them), so the statistics are those of the
+// very values the step kernel will scale.
+#include "step_core.h"
 
 namespace {
-
-template <int DT> struct EpsT;
-template <> struct EpsT<TMIX_F32>  { typedef float  T; static __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; } };
-template <> struct EpsT<TMIX_F16>  { typedef __half T; static __device__ __forceinline__ float ld(const __half* p, int64_t i) { return __half2float(p[i]); } };
-template <> struct EpsT<TMIX_BF16> { typedef bf16_t T; static __device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); } };
-
-// rounding point of the reference's autocast path (only when eps is fp16), as in tweedie_step.hip: the fp32 RESULT is rounded to fp16; the empty
-// asm keeps LLVM from folding mul+convert into the single-rounding v_fma_mixlo_f16
-template <int DT> __device__ __forceinline__ float rnd(float v) {
-    if constexpr (DT == TMIX_F16) {
-        asm volatile("" : "+v"(v));
-        return __half2float(__float2half_rn(v));
-    } else return v;
-}
-
-template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float g) {
-    const float d = rnd<DT>(ec - eu);
-    const float gd = rnd<DT>(g * d);
-    return rnd<DT>(eu + gd);
-}
 
 constexpr int RS_P = 32;            // workgroups per (row, seed): fixed, so the partition (and with it the bits of the factors) never depends on the data
 constexpr int RS_THREADS = 256;
@@ -127,10 +107,7 @@ extern "C" int tmix_cfg_rescale_factors(const void* eps, int eps_dtype, float* f
     if (n < 2) TMIX_FAIL(TMIX_ESHAPE, "cfg_rescale_factors: a standard deviation needs n >= 2 elements, got %lld", (long long)n);
     const int used = mode == TMIX_STEP_PLAIN ? 1 : K;
     if (rows < used + 1 || rows > 256) TMIX_FAIL(TMIX_ESHAPE, "cfg_rescale_factors: mode %d needs %d..256 eps rows per seed, got %d", mode, used + 1, rows);
-    hipStream_t st = (hipStream_t)stream;
-    switch (eps_dtype) {
-    case TMIX_F32:  return launch_rescale<TMIX_F32>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, st);
-    case TMIX_F16:  return launch_rescale<TMIX_F16>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, st);
-    default:        return launch_rescale<TMIX_BF16>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, st);
-    }
+    return for_dtype(eps_dtype, "cfg_rescale_factors", "eps dtype", [&](auto dt) {
+        return launch_rescale<dt()>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, (hipStream_t)stream);
+    });
 }

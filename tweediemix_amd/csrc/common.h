@@ -90,23 +90,6 @@ __device__ __forceinline__ float silu_fast(float x) {     // x * sigmoid(x) with
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * x));
 }
 
-// ---- the video step kernels' shared pieces (tweedie_step.hip: the DDIM forms, solver_step.hip: the DPM-Solver++(2M) forms): ONE definition each
-// store of an fp32 value as the element type of TMIX_F32 / TMIX_F16 / TMIX_BF16 (one rounding to nearest even)
-template <int DT> struct StT;
-template <> struct StT<TMIX_F32>  { static __device__ __forceinline__ void st(float* p, int64_t i, float v) { p[i] = v; } };
-template <> struct StT<TMIX_F16>  { static __device__ __forceinline__ void st(__half* p, int64_t i, float v) { p[i] = __float2half_rn(v); } };
-template <> struct StT<TMIX_BF16> { static __device__ __forceinline__ void st(bf16_t* p, int64_t i, float v) { p[i] = f2bf(v); } };
-// index i of the pipeline-layout state [S][C][F][hw] -> offset of (video s, frame f, channel c, pixel p) in a per-row plan buffer
-// [(clip*F + f)][row_channels][hw] whose clip s starts at s * clip_stride
-__device__ __forceinline__ int64_t video_row_offset(int64_t i, int C, int F, int64_t hw, int row_channels, int64_t clip_stride) {
-    const int64_t p = i % hw;
-    int64_t r = i / hw;
-    const int64_t f = r % F; r /= F;
-    const int64_t c = r % C;
-    const int64_t s = r / C;
-    return s * clip_stride + (f * row_channels + c) * hw + p;
-}
-
 // thread-local error string (host side)
 void tmix_set_error(const char* fmt, ...);
 

@@ -1,42 +1,18 @@
 // solver_step.hip -- fused CFG + Tweedie x0 + mask blend + DPM-Solver++(2M) update on the blended estimate (one HBM pass).
-// The x0 part repeats tweedie_step.hip's tweedie_step_kernel operation for operation (rnd<DT> included), so out_x0 is that kernel's out_x0
-// bit for bit; the move is the data-prediction form x_next = cx x + c0 x0 + c1 x0_prev with the history buffer x0_prev read and rewritten in
-// the same pass.  Per element and seed it reads (rows) eps values + x + K mask values + 1 history value and writes 2-3 floats.
+// The x0 part IS tweedie_step.hip's: both kernels call step_core.h's blended_x0, so out_x0 is that kernel's out_x0 bit for bit; the move is the
+// data-prediction form x_next = cx x + c0 x0 + c1 x0_prev with the history buffer x0_prev read and rewritten in the same pass.  Per element and
+// seed it reads (rows) eps values + x + K mask values + 1 history value and writes 2-3 floats.
 // Compiled with -ffp-contract=off so fp32 results are bit-identical to the numpy restatement (solver.multistep_step_reference).
 // Second half: the same move for the video sampler's v-prediction step (tmix_vpred_step_ms / _ms_dev; solver.vpred_multistep_reference).
-#include "common.h"
+#include "step_core.h"
 
 namespace {
-
-template <int DT> struct EpsT;
-template <> struct EpsT<TMIX_F32>  { typedef float  T; static __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; } };
-template <> struct EpsT<TMIX_F16>  { typedef __half T; static __device__ __forceinline__ float ld(const __half* p, int64_t i) { return __half2float(p[i]); } };
-template <> struct EpsT<TMIX_BF16> { typedef bf16_t T; static __device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); } };
-
-// rounding point of the reference's autocast path (only when eps is fp16): the fp32 RESULT is rounded to fp16; the empty asm keeps LLVM from
-// folding mul+convert into the single-rounding v_fma_mixlo_f16 (as in tweedie_step.hip)
-template <int DT> __device__ __forceinline__ float rnd(float v) {
-    if constexpr (DT == TMIX_F16) {
-        asm volatile("" : "+v"(v));
-        return __half2float(__float2half_rn(v));
-    } else return v;
-}
-
-template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float g) {
-    const float d = rnd<DT>(ec - eu);
-    const float gd = rnd<DT>(g * d);
-    return rnd<DT>(eu + gd);
-}
 
 // prm = {t, sa, s1, cx, c0, c1, is_last, g} in device memory (one captured launch serves every timestep and both orders); blockIdx.y walks
 // co-batched seeds (x / out_x / out_x0 / x0_prev: [seeds][n], eps: [seeds][rows][n], masks: [seeds][K][hw] or shared).  x may alias out_x:
 // every array is read at i before it is written at i.  x0_prev is read AND written, so it carries no __restrict__.
-// RESCALE: the presence of ONE trailing RescaleArgs kernel argument (the pack RsT is empty or {RescaleArgs}, tweedie_step.hip's KeepArgs mechanism):
-// every guided prediction e_r becomes rnd<DT>(f_r * e_r) with f_r = fac[seed][r - 1] (layout [seeds][rows - 1]), exactly as in that
-// file's kernel; without it the kernel has the arguments, and compiles to the instructions, it had before.
-struct RescaleArgs { const float* fac; };
-__device__ __forceinline__ RescaleArgs rescale_args(const RescaleArgs& r) { return r; }
-
+// RESCALE: the presence of ONE trailing RescaleArgs kernel argument (step_core.h; the pack RsT is empty or {RescaleArgs}, tweedie_step.hip's KeepArgs
+// mechanism); without it the kernel has the arguments it had before.
 template <int DT, int MODE, typename... RsT>
 __global__ void __launch_bounds__(256)
 solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps, const float* __restrict__ masks, float* out_x,
@@ -55,21 +31,7 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
         const float xv = x[i];
         const float p = x0_prev[i];
         const float eu = EpsT<DT>::ld(eps, i);
-        float x0;
-        if constexpr (MODE == TMIX_STEP_FUSION) {
-            const int64_t px = i % hw;
-            x0 = 0.0f;
-            for (int c = 0; c < K; ++c) {
-                float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
-                if constexpr (RS) e = rnd<DT>(fac[c] * e);
-                const float t = (xv - rnd<DT>(s1 * e)) / sa;
-                x0 = x0 + masks[(int64_t)c * hw + px] * t;
-            }
-        } else {
-            float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
-            if constexpr (RS) e = rnd<DT>(fac[0] * e);
-            x0 = (xv - rnd<DT>(s1 * e)) / sa;
-        }
+        const float x0 = blended_x0<DT, MODE, RS>(eps, masks, fac, K, n, hw, i, xv, eu, g, sa, s1);
         float m = c0 * x0;
         if (c1 != 0.0f) m = m + c1 * p;          // a first-order step never touches the history value: a NaN left there stays out
         out_x[i] = is_last ? x0 : cx * xv + m;
@@ -94,16 +56,15 @@ int launch_ms(const float* x, const void* eps, const float* masks, int64_t mss, 
 }
 
 // ------------------------------------------------------------------ video sampler (I2VGen-XL loop): the same move on the v-prediction
-// StT<DT>::st and video_row_offset are common.h's, shared with the DDIM forms in tweedie_step.hip
+// StT<DT>::st, video_row_offset and the element's x0 (vpred_x0) are step_core.h's, shared with the DDIM forms in tweedie_step.hip
 
-// one element of the v-prediction solver step, shared by the scalar and the device form (so the two agree bit for bit): vv and x0 are
-// tweedie_step.hip's vpred_step_kernel operation for operation (rnd<DT> behind every binary op), so x0 is that kernel's x0; the history value p
-// is used only when c1 != 0 (a NaN left in an unused history stays out); returns the moved state, x0 through the reference
+// one element of the v-prediction solver step, shared by the scalar and the device form (so the two agree bit for bit): x0 is vpred_x0's, as in
+// tweedie_step.hip's vpred_step_kernel; the history value p is used only when c1 != 0 (a NaN left in an unused history stays out); returns the
+// moved state, x0 through the reference
 template <int DT>
 __device__ __forceinline__ float vpred_ms_element(float xv, float vu, float vc, float p, float g, float sa, float s1, float cx, float c0, float c1,
                                                   float& x0) {
-    const float vv = cfg<DT>(vu, vc, g);
-    x0 = rnd<DT>(rnd<DT>(sa * xv) - rnd<DT>(s1 * vv));
+    x0 = vpred_x0<DT>(xv, vu, vc, g, sa, s1).x0;
     float m = rnd<DT>(c0 * x0);
     if (c1 != 0.0f) m = rnd<DT>(m + rnd<DT>(c1 * p));
     return rnd<DT>(rnd<DT>(cx * xv) + m);
@@ -160,24 +121,15 @@ extern "C" int tmix_vpred_step_ms(const void* x, const void* v, void* out, float
     if (!x0_prev) TMIX_FAIL(TMIX_EINVAL, "vpred_step_ms: null x0_prev (the history buffer is read and written by every step)");
     if (dtype != TMIX_F32 && dtype != TMIX_F16 && dtype != TMIX_BF16) TMIX_FAIL(TMIX_EINVAL, "vpred_step_ms: bad dtype %d", dtype);
     if (n < 1) TMIX_FAIL(TMIX_ESHAPE, "vpred_step_ms: empty latent");
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-    case TMIX_F32:  return launch_vpred_ms<TMIX_F32>(x, v, out, x0_prev, n, g, sa, s1, cx, c0, c1, st);
-    case TMIX_F16:  return launch_vpred_ms<TMIX_F16>(x, v, out, x0_prev, n, g, sa, s1, cx, c0, c1, st);
-    default:        return launch_vpred_ms<TMIX_BF16>(x, v, out, x0_prev, n, g, sa, s1, cx, c0, c1, st);
-    }
+    return for_dtype(dtype, "vpred_step_ms", "dtype", [&](auto dt) { return launch_vpred_ms<dt()>(x, v, out, x0_prev, n, g, sa, s1, cx, c0, c1, (hipStream_t)stream); });
 }
 
 extern "C" int tmix_vpred_step_ms_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
                                       const float* params, int videos, int channels, int frames, int64_t hw, void* stream) {
     if (!x || !v_u || !v_c || !params) TMIX_FAIL(TMIX_EINVAL, "vpred_step_ms_dev: null pointer");
     if (!x0_prev) TMIX_FAIL(TMIX_EINVAL, "vpred_step_ms_dev: null x0_prev (the history buffer is read and written by every step)");
-    if (videos < 1 || channels < 1 || frames < 1 || hw < 1)
-        TMIX_FAIL(TMIX_ESHAPE, "vpred_step_ms_dev: videos=%d channels=%d frames=%d hw=%lld", videos, channels, frames, (long long)hw);
-    const int64_t clip = (int64_t)frames * channels * hw;
-    if (clip_stride_u < clip || clip_stride_c < clip)
-        TMIX_FAIL(TMIX_ESHAPE, "vpred_step_ms_dev: clip strides %lld / %lld < one clip's %lld floats", (long long)clip_stride_u, (long long)clip_stride_c, (long long)clip);
-    const int64_t n = (int64_t)videos * clip;
+    if (int rc = check_video_step("vpred_step_ms_dev", videos, channels, frames, hw, channels, false, clip_stride_u, clip_stride_c)) return rc;
+    const int64_t n = (int64_t)videos * frames * channels * hw;
     int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
     vpred_step_ms_dev_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, v_u, clip_stride_u, v_c, clip_stride_c, x0_prev, params,
                                                                                 channels, frames, hw, n);
@@ -188,41 +140,20 @@ extern "C" int tmix_vpred_step_ms_dev(float* x, const float* v_u, int64_t clip_s
 extern "C" int tmix_fused_tweedie_step_ms_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
                                               int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
                                               int64_t hw, int mode, int rows, int seeds, const float* params, void* stream) {
-    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: null pointer");
-    if (!x0_prev) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: null x0_prev (the history buffer is read and written by every step)");
-    if (mode != TMIX_STEP_FUSION && mode != TMIX_STEP_PLAIN) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: bad mode %d (FUSION or PLAIN)", mode);
-    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: FUSION needs masks and K>=1");
-    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
-    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
-    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
-    const int64_t n = (int64_t)channels * hw;
-    hipStream_t st = (hipStream_t)stream;
-    switch (eps_dtype) {
-    case TMIX_F32:  return launch_ms<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st);
-    case TMIX_F16:  return launch_ms<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st);
-    case TMIX_BF16: return launch_ms<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_dev: bad eps dtype %d", eps_dtype);
+    const char* me = "tweedie_step_ms_dev";
+    if (int rc = check_dev_step(me, false, true, x, eps, out_x, params, x0_prev, nullptr, masks, K, channels, hw, mode, rows, seeds)) return rc;
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, (int64_t)channels * hw, hw, mode, rows, seeds, params, (hipStream_t)stream);
+    });
 }
 
 extern "C" int tmix_fused_tweedie_step_ms_rs_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
                                                  int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
                                                  int64_t hw, int mode, int rows, int seeds, const float* params, const float* factors, void* stream) {
-    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: null pointer");
-    if (!x0_prev) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: null x0_prev (the history buffer is read and written by every step)");
-    if (!factors) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: null factors");
-    if (mode != TMIX_STEP_FUSION && mode != TMIX_STEP_PLAIN) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: bad mode %d (FUSION or PLAIN)", mode);
-    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: FUSION needs masks and K>=1");
-    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_rs_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
-    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
-    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_ms_rs_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
-    const int64_t n = (int64_t)channels * hw;
+    const char* me = "tweedie_step_ms_rs_dev";
+    if (int rc = check_dev_step(me, false, true, x, eps, out_x, params, x0_prev, factors ? nullptr : "null factors", masks, K, channels, hw, mode, rows, seeds)) return rc;
     const RescaleArgs rs = {factors};
-    hipStream_t st = (hipStream_t)stream;
-    switch (eps_dtype) {
-    case TMIX_F32:  return launch_ms<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st, rs);
-    case TMIX_F16:  return launch_ms<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st, rs);
-    case TMIX_BF16: return launch_ms<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, st, rs);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_ms_rs_dev: bad eps dtype %d", eps_dtype);
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, (int64_t)channels * hw, hw, mode, rows, seeds, params, (hipStream_t)stream, rs);
+    });
 }

@@ -1,0 +1,148 @@
+// step_core.h -- the ONE definition of what the sampler's step kernels share (tweedie_step.hip: the DDIM forms, solver_step.hip: the
+// DPM-Solver++(2M) forms, cfg_rescale.hip: the statistics of the guided prediction).  Device side: element types, the fp16 rounding point, CFG,
+// the blended Tweedie x0 of one element, the v-prediction element of the video sampler.  Host side: the argument checks the *_dev step entries
+// and the video entries share, and the dtype dispatch.  Every file that includes it is compiled with -ffp-contract=off: the kernels that call one
+// function here agree bit for bit because they run the same operations, not because two copies were kept alike.
+#pragma once
+#include <type_traits>
+#include "common.h"
+
+namespace {
+
+template <int DT> struct EpsT;
+template <> struct EpsT<TMIX_F32>  { typedef float  T; static __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; } };
+template <> struct EpsT<TMIX_F16>  { typedef __half T; static __device__ __forceinline__ float ld(const __half* p, int64_t i) { return __half2float(p[i]); } };
+template <> struct EpsT<TMIX_BF16> { typedef bf16_t T; static __device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); } };
+// store of an fp32 value as the element type of TMIX_F32 / TMIX_F16 / TMIX_BF16 (one rounding to nearest even)
+template <int DT> struct StT;
+template <> struct StT<TMIX_F32>  { static __device__ __forceinline__ void st(float* p, int64_t i, float v) { p[i] = v; } };
+template <> struct StT<TMIX_F16>  { static __device__ __forceinline__ void st(__half* p, int64_t i, float v) { p[i] = __float2half_rn(v); } };
+template <> struct StT<TMIX_BF16> { static __device__ __forceinline__ void st(bf16_t* p, int64_t i, float v) { p[i] = f2bf(v); } };
+
+// rounding point of the reference's autocast path (only when eps is fp16)
+template <int DT> __device__ __forceinline__ float rnd(float v) {
+    if constexpr (DT == TMIX_F16) {
+        // torch evaluates fp16 elementwise ops in fp32 and rounds the fp32 RESULT to fp16 (two roundings).
+        // The empty asm makes the fp32 value opaque so LLVM cannot fold mul+convert into the single-rounding
+        // v_fma_mixlo_f16, which differs from the reference on near-ties.
+        asm volatile("" : "+v"(v));
+        return __half2float(__float2half_rn(v));
+    } else return v;
+}
+
+template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float g) {
+    const float d = rnd<DT>(ec - eu);
+    const float gd = rnd<DT>(g * d);
+    return rnd<DT>(eu + gd);
+}
+
+// RESCALE: every guided prediction e_r a step kernel forms becomes rnd<DT>(f_r * e_r) with f_r = fac[seed][r - 1] (layout [seeds][rows - 1];
+// tmix_cfg_rescale_factors writes it: DESIGN.md 7k).  f_r = 1.0f gives e_r back bit for bit.  The flag is the presence of ONE trailing
+// RescaleArgs kernel argument: without it a kernel has the arguments it had before the rescale existed.
+struct RescaleArgs { const float* fac; };
+__device__ __forceinline__ RescaleArgs rescale_args(const RescaleArgs& r) { return r; }
+
+// The blended Tweedie estimate of element i, the x0 of EVERY fused step (fusion_sampling.py:376-385,392-403,406-412): CFG per eps row, the rescale
+// (RS), x0 per row, then the mask blend (FUSION), the one row (PLAIN) or (K-1)*x0_multi - sum_{c<K-1} x0_single_c (RESAMPLE).  eps / masks / fac are
+// the seed's own; xv = x[i], eu = the unconditional row's value at i.
+template <int DT, int MODE, bool RS>
+__device__ __forceinline__ float blended_x0(const typename EpsT<DT>::T* eps, const float* masks, const float* fac, int K, int64_t n, int64_t hw,
+                                            int64_t i, float xv, float eu, float g, float sa, float s1) {
+    float x0;
+    if constexpr (MODE == TMIX_STEP_FUSION) {
+        const int64_t p = i % hw;
+        x0 = 0.0f;
+        for (int c = 0; c < K; ++c) {
+            float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
+            if constexpr (RS) e = rnd<DT>(fac[c] * e);
+            const float t = (xv - rnd<DT>(s1 * e)) / sa;
+            x0 = x0 + masks[(int64_t)c * hw + p] * t;
+        }
+    } else if constexpr (MODE == TMIX_STEP_PLAIN) {
+        float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+        if constexpr (RS) e = rnd<DT>(fac[0] * e);
+        x0 = (xv - rnd<DT>(s1 * e)) / sa;
+    } else {
+        float em = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+        if constexpr (RS) em = rnd<DT>(fac[0] * em);
+        x0 = (float)(K - 1) * ((xv - rnd<DT>(s1 * em)) / sa);
+        for (int c = 0; c < K - 1; ++c) {
+            float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(2 + c) * n + i), g);
+            if constexpr (RS) e = rnd<DT>(fac[1 + c] * e);
+            x0 = x0 - (xv - rnd<DT>(s1 * e)) / sa;
+        }
+    }
+    return x0;
+}
+
+// ---- video sampler (I2VGen-XL loop): video_gen/pipeline_i2vgen_xl.py:699-719.  Latents and predictions share the model dtype in that loop, so in
+// fp16 mode EVERY binary op rounds (rnd<DT>).
+// one element's guided v-prediction and the x0 it gives: what the DDIM and the multistep video kernels have in common
+struct VPred { float vv, x0; };
+template <int DT> __device__ __forceinline__ VPred vpred_x0(float xv, float vu, float vc, float g, float sa, float s1) {
+    const float vv = cfg<DT>(vu, vc, g);
+    return {vv, rnd<DT>(rnd<DT>(sa * xv) - rnd<DT>(s1 * vv))};
+}
+// the DDIM move of that element: eps from (x, v), then sa_n * x0 + s1_n * eps
+template <int DT> __device__ __forceinline__ float vpred_ddim_move(float xv, const VPred& p, float sa, float s1, float sa_n, float s1_n) {
+    const float eps = rnd<DT>(rnd<DT>(sa * p.vv) + rnd<DT>(s1 * xv));
+    return rnd<DT>(rnd<DT>(sa_n * p.x0) + rnd<DT>(s1_n * eps));
+}
+// index i of the pipeline-layout state [S][C][F][hw] -> offset of (video s, frame f, channel c, pixel p) in a per-row plan buffer
+// [(clip*F + f)][row_channels][hw] whose clip s starts at s * clip_stride
+__device__ __forceinline__ int64_t video_row_offset(int64_t i, int C, int F, int64_t hw, int row_channels, int64_t clip_stride) {
+    const int64_t p = i % hw;
+    int64_t r = i / hw;
+    const int64_t f = r % F; r /= F;
+    const int64_t c = r % C;
+    const int64_t s = r / C;
+    return s * clip_stride + (f * row_channels + c) * hw + p;
+}
+
+// ------------------------------------------------------------------ host side
+
+// f(std::integral_constant<int, DT>()) for dt = TMIX_F32 / TMIX_F16 / TMIX_BF16; any other value: EINVAL, "<me>: bad <word> <dt>"
+template <typename F> int for_dtype(int dt, const char* me, const char* word, F&& f) {
+    switch (dt) {
+    case TMIX_F32:  return f(std::integral_constant<int, TMIX_F32>());
+    case TMIX_F16:  return f(std::integral_constant<int, TMIX_F16>());
+    case TMIX_BF16: return f(std::integral_constant<int, TMIX_BF16>());
+    }
+    TMIX_FAIL(TMIX_EINVAL, "%s: bad %s %d", me, word, dt);
+}
+
+// The argument checks of the five device-parameter step entries (tmix_fused_tweedie_step_dev / _keep_dev / _rs_dev / _ms_dev / _ms_rs_dev), under
+// the entry's short name `me`.  resample: RESAMPLE is one of the entry's modes (the DDIM forms; the multistep forms take FUSION or PLAIN).
+// need_prev: the entry has the history buffer x0_prev, which must not be null.  missing: the entry's complaint about a null pointer of its own
+// (factors, the keep arrays), or nullptr when it has none to make; it is reported behind the shared pointers and in front of the mode.
+inline int check_dev_step(const char* me, bool resample, bool need_prev, const void* x, const void* eps, const void* out_x, const void* params,
+                          const void* x0_prev, const char* missing, const float* masks, int K, int channels, int64_t hw, int mode, int rows, int seeds) {
+    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
+    if (need_prev && !x0_prev) TMIX_FAIL(TMIX_EINVAL, "%s: null x0_prev (the history buffer is read and written by every step)", me);
+    if (missing) TMIX_FAIL(TMIX_EINVAL, "%s: %s", me, missing);
+    if (resample) {
+        if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "%s: bad mode %d", me, mode);
+    } else if (mode != TMIX_STEP_FUSION && mode != TMIX_STEP_PLAIN) TMIX_FAIL(TMIX_EINVAL, "%s: bad mode %d (FUSION or PLAIN)", me, mode);
+    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "%s: FUSION needs masks and K>=1", me);
+    if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "%s: RESAMPLE needs K>=1", me);
+    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "%s: channels=%d hw=%lld seeds=%d", me, channels, (long long)hw, seeds);
+    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
+    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "%s: mode %d needs %d eps rows per seed, got %d", me, mode, need, rows);
+    return TMIX_OK;
+}
+
+// Shape and clip strides of a batched video entry: the plan rows of a clip hold row_channels >= channels channels (wide_rows: the entry has that
+// argument and names it; otherwise the rows hold the state's channels alone) and a clip's stride covers them.
+inline int check_video_step(const char* me, int videos, int channels, int frames, int64_t hw, int row_channels, bool wide_rows, int64_t clip_stride_u,
+                            int64_t clip_stride_c) {
+    if (videos < 1 || channels < 1 || frames < 1 || hw < 1 || row_channels < channels) {
+        if (wide_rows) TMIX_FAIL(TMIX_ESHAPE, "%s: videos=%d channels=%d frames=%d hw=%lld row_channels=%d", me, videos, channels, frames, (long long)hw, row_channels);
+        TMIX_FAIL(TMIX_ESHAPE, "%s: videos=%d channels=%d frames=%d hw=%lld", me, videos, channels, frames, (long long)hw);
+    }
+    const int64_t clip = (int64_t)frames * row_channels * hw;
+    if (clip_stride_u < clip || clip_stride_c < clip)
+        TMIX_FAIL(TMIX_ESHAPE, "%s: clip strides %lld / %lld < one clip's %lld floats", me, (long long)clip_stride_u, (long long)clip_stride_c, (long long)clip);
+    return TMIX_OK;
+}
+
+}  // namespace

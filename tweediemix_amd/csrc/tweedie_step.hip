@@ -1,32 +1,11 @@
 // tweedie_step.hip -- fused CFG + Tweedie x0 + mask blend + DDIM update (one HBM pass).
 // Follows fusion_generation/fusion_sampling.py:376-385,392-403,406-412,424-430,471-472.
 // HBM-bound: per element it reads (rows) eps values + x + K mask values and writes 1-2 floats.
-// Compiled with -ffp-contract=off so fp32 results are bit-identical to the numpy oracle.
-#include "common.h"
+// Compiled with -ffp-contract=off so fp32 results are bit-identical to the numpy oracle.  The x0 of an element, the fp16 rounding point and the
+// argument checks of the *_dev entries are step_core.h's, shared with solver_step.hip.
+#include "step_core.h"
 
 namespace {
-
-template <int DT> struct EpsT;
-template <> struct EpsT<TMIX_F32>  { typedef float  T; static __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; } };
-template <> struct EpsT<TMIX_F16>  { typedef __half T; static __device__ __forceinline__ float ld(const __half* p, int64_t i) { return __half2float(p[i]); } };
-template <> struct EpsT<TMIX_BF16> { typedef bf16_t T; static __device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); } };
-
-// rounding point of the reference's autocast path (only when eps is fp16)
-template <int DT> __device__ __forceinline__ float rnd(float v) {
-    if constexpr (DT == TMIX_F16) {
-        // torch evaluates fp16 elementwise ops in fp32 and rounds the fp32 RESULT to fp16 (two roundings).
-        // The empty asm makes the fp32 value opaque so LLVM cannot fold mul+convert into the single-rounding
-        // v_fma_mixlo_f16, which differs from the reference on near-ties.
-        asm volatile("" : "+v"(v));
-        return __half2float(__float2half_rn(v));
-    } else return v;
-}
-
-template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float g) {
-    const float d = rnd<DT>(ec - eu);
-    const float gd = rnd<DT>(g * d);
-    return rnd<DT>(eu + gd);
-}
 
 // DEV = 1: the step coefficients come from a device buffer prm = {t, sa, s1, sa_next, s1_next, is_last, g} (so ONE captured
 // launch serves every timestep of a hipGraph replay) and blockIdx.y walks co-batched seeds (x / out: [seeds][n], eps:
@@ -34,15 +13,12 @@ template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float
 // KEEP (with DEV): a region of the latent is held at a given clean latent kp.x0 re-noised with its own fixed noise kp.eps to the level
 // of the state the step writes; kp.w [hw] (broadcast over the channels) is the weight of the held part.  Seed sd reads its arrays at
 // sd * stride (0: shared by all seeds).  The mode's x0 / moved are computed exactly as without it.  The flag is the presence of ONE
-// trailing KeepArgs kernel argument (the pack KeepT is empty or {KeepArgs}): without it the kernel has the arguments, and compiles to
-// the instructions, it had before the keep region existed.
+// trailing KeepArgs kernel argument (the pack KeepT is empty or {KeepArgs}): without it the kernel has the arguments it had before the keep
+// region existed.
 struct KeepArgs { const float* x0; const float* eps; const float* w; int64_t x0_stride, eps_stride, w_stride; };
 __device__ __forceinline__ KeepArgs keep_args(const KeepArgs& k) { return k; }
-// RESCALE (with DEV; the same mechanism, the other type of the ONE trailing argument): every guided prediction e_r the mode forms becomes
-// rnd<DT>(f_r * e_r) with f_r = fac[seed][r - 1] (layout [seeds][rows - 1]; tmix_cfg_rescale_factors writes it: DESIGN.md 7k).  f_r = 1.0f gives e_r back
-// bit for bit.  The move's noise term stays the unconditional eu.
-struct RescaleArgs { const float* fac; };
-__device__ __forceinline__ RescaleArgs rescale_args(const RescaleArgs& r) { return r; }
+// RESCALE (with DEV; the same mechanism, the other type of the ONE trailing argument): step_core.h's RescaleArgs.  The move's noise term stays the
+// unconditional eu.
 template <typename A, typename... T> constexpr bool pack_is = sizeof...(T) == 1 && (__is_same(T, A) && ...);
 
 template <int DT, int MODE, int DEV = 0, typename... KeepT>
@@ -69,30 +45,7 @@ tweedie_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float xv = x[i];
         const float eu = EpsT<DT>::ld(eps, i);
-        float x0;
-        if constexpr (MODE == TMIX_STEP_FUSION) {
-            const int64_t p = i % hw;
-            x0 = 0.0f;
-            for (int c = 0; c < K; ++c) {
-                float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
-                if constexpr (RS) e = rnd<DT>(fac[c] * e);
-                const float t = (xv - rnd<DT>(s1 * e)) / sa;
-                x0 = x0 + masks[(int64_t)c * hw + p] * t;
-            }
-        } else if constexpr (MODE == TMIX_STEP_PLAIN) {
-            float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
-            if constexpr (RS) e = rnd<DT>(fac[0] * e);
-            x0 = (xv - rnd<DT>(s1 * e)) / sa;
-        } else {   // RESAMPLE: (K-1)*x0_multi - sum_{c<K-1} x0_single_c
-            float em = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
-            if constexpr (RS) em = rnd<DT>(fac[0] * em);
-            x0 = (float)(K - 1) * ((xv - rnd<DT>(s1 * em)) / sa);
-            for (int c = 0; c < K - 1; ++c) {
-                float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(2 + c) * n + i), g);
-                if constexpr (RS) e = rnd<DT>(fac[1 + c] * e);
-                x0 = x0 - (xv - rnd<DT>(s1 * e)) / sa;
-            }
-        }
+        const float x0 = blended_x0<DT, MODE, RS>(eps, masks, fac, K, n, hw, i, xv, eu, g, sa, s1);
         const float moved = sa_n * x0 + rnd<DT>(s1_n * eu);
         if constexpr (KEEP) {   // fp32, two products and one sum each (-ffp-contract=off); w in {0, 1} gives exactly kept or exactly new
             const float kx = kp.x0[i], w = kp.w[i % hw];
@@ -107,59 +60,22 @@ tweedie_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps
     }
 }
 
-template <int DT>
-int launch(const float* x, const void* eps, const float* masks, float* out_x, float* out_x0, int K, int64_t n,
-           int64_t hw, int mode, float g, float sa, float s1, float sa_n, float s1_n, int is_last, hipStream_t st) {
-    typedef typename EpsT<DT>::T T;
-    const int threads = 256;
-    int64_t blocks = (n + threads - 1) / threads;
-    if (blocks > 2048) blocks = 2048;
-    const T* e = (const T*)eps;
-    switch (mode) {
-    case TMIX_STEP_FUSION:
-        tweedie_step_kernel<DT, TMIX_STEP_FUSION><<<blocks, threads, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, g, sa, s1, sa_n, s1_n, is_last); break;
-    case TMIX_STEP_PLAIN:
-        tweedie_step_kernel<DT, TMIX_STEP_PLAIN><<<blocks, threads, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, g, sa, s1, sa_n, s1_n, is_last); break;
-    default:
-        tweedie_step_kernel<DT, TMIX_STEP_RESAMPLE><<<blocks, threads, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, g, sa, s1, sa_n, s1_n, is_last); break;
-    }
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
-}
+// the coefficients of the scalar form (DEV = 0); the device-parameter forms leave them at these values and the kernel reads prm instead
+struct HostCoef { float g = 0.f, sa = 1.f, s1 = 0.f, sa_n = 1.f, s1_n = 0.f; int is_last = 0; };
 
-template <int DT>
-int launch_dev(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, int K, int64_t n,
-               int64_t hw, int mode, int rows, int seeds, const float* prm, hipStream_t st) {
-    typedef typename EpsT<DT>::T T;
+template <int DT, int DEV, typename... ExtraT>      // ExtraT: empty, or the one trailing kernel argument (KeepArgs or RescaleArgs)
+int launch(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, int K, int64_t n, int64_t hw, int mode,
+           const HostCoef& c, int rows, int seeds, const float* prm, hipStream_t st, const ExtraT&... extra) {
     int64_t bx = (n + 255) / 256; if (bx > 2048) bx = 2048;
     const dim3 grid((unsigned)bx, (unsigned)seeds);
-    const T* e = (const T*)eps;
+    auto go = [&](auto m) {
+        tweedie_step_kernel<DT, m(), DEV, ExtraT...><<<grid, 256, 0, st>>>(x, (const typename EpsT<DT>::T*)eps, masks, out_x, out_x0, K, n, hw, c.g, c.sa, c.s1,
+                                                                           c.sa_n, c.s1_n, c.is_last, prm, rows, mss, extra...);
+    };
     switch (mode) {
-    case TMIX_STEP_FUSION:
-        tweedie_step_kernel<DT, TMIX_STEP_FUSION, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss); break;
-    case TMIX_STEP_PLAIN:
-        tweedie_step_kernel<DT, TMIX_STEP_PLAIN, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss); break;
-    default:
-        tweedie_step_kernel<DT, TMIX_STEP_RESAMPLE, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss); break;
-    }
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
-}
-
-template <int DT, typename ExtraT>      // ExtraT: KeepArgs or RescaleArgs, the one trailing kernel argument
-int launch_extra(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, int K, int64_t n,
-                int64_t hw, int mode, int rows, int seeds, const float* prm, const ExtraT& kp, hipStream_t st) {
-    typedef typename EpsT<DT>::T T;
-    int64_t bx = (n + 255) / 256; if (bx > 2048) bx = 2048;
-    const dim3 grid((unsigned)bx, (unsigned)seeds);
-    const T* e = (const T*)eps;
-    switch (mode) {
-    case TMIX_STEP_FUSION:
-        tweedie_step_kernel<DT, TMIX_STEP_FUSION, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss, kp); break;
-    case TMIX_STEP_PLAIN:
-        tweedie_step_kernel<DT, TMIX_STEP_PLAIN, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss, kp); break;
-    default:
-        tweedie_step_kernel<DT, TMIX_STEP_RESAMPLE, 1><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, K, n, hw, 0.f, 1.f, 0.f, 1.f, 0.f, 0, prm, rows, mss, kp); break;
+    case TMIX_STEP_FUSION: go(std::integral_constant<int, TMIX_STEP_FUSION>()); break;
+    case TMIX_STEP_PLAIN:  go(std::integral_constant<int, TMIX_STEP_PLAIN>()); break;
+    default:               go(std::integral_constant<int, TMIX_STEP_RESAMPLE>()); break;
     }
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
@@ -179,10 +95,9 @@ step_prologue_kernel(const float* __restrict__ x, float* __restrict__ latent, fl
     if (blockIdx.x == 0 && threadIdx.x < rows) t_dev[sd * rows + threadIdx.x] = prm[0];
 }
 
-// ------------------------------------------------------------------ video sampler (I2VGen-XL loop, config #5); StT<DT>::st: common.h
+// ------------------------------------------------------------------ video sampler (I2VGen-XL loop, config #5); StT<DT>::st: step_core.h
 
-// video_gen/pipeline_i2vgen_xl.py:699-719 in one pass: CFG on the v-prediction, eps / x0 from (x, v), DDIM move.
-// Latents and predictions share the model dtype in that loop, so in fp16 mode EVERY binary op rounds (rnd<DT>).
+// video_gen/pipeline_i2vgen_xl.py:699-719 in one pass: CFG on the v-prediction, eps / x0 from (x, v), DDIM move (step_core.h: vpred_x0, vpred_ddim_move)
 template <int DT>
 __global__ void __launch_bounds__(256)
 vpred_step_kernel(const typename EpsT<DT>::T* __restrict__ x, const typename EpsT<DT>::T* __restrict__ v,
@@ -190,10 +105,7 @@ vpred_step_kernel(const typename EpsT<DT>::T* __restrict__ x, const typename Eps
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float xv = EpsT<DT>::ld(x, i);
-        const float vv = cfg<DT>(EpsT<DT>::ld(v, i), EpsT<DT>::ld(v, n + i), g);
-        const float eps = rnd<DT>(rnd<DT>(sa * vv) + rnd<DT>(s1 * xv));
-        const float x0 = rnd<DT>(rnd<DT>(sa * xv) - rnd<DT>(s1 * vv));
-        StT<DT>::st(out, i, rnd<DT>(rnd<DT>(sa_n * x0) + rnd<DT>(s1_n * eps)));
+        StT<DT>::st(out, i, vpred_ddim_move<DT>(xv, vpred_x0<DT>(xv, EpsT<DT>::ld(v, i), EpsT<DT>::ld(v, n + i), g, sa, s1), sa, s1, sa_n, s1_n));
     }
 }
 
@@ -213,7 +125,7 @@ frame_inject_kernel(typename EpsT<DT>::T* __restrict__ x, int64_t per_frame, int
     }
 }
 
-// ------------------------------------------------------------------ batched video step (S videos, both CFG halves); video_row_offset: common.h
+// ------------------------------------------------------------------ batched video step (S videos, both CFG halves); video_row_offset: step_core.h
 
 // head of the captured video step: the state goes into channels [0, C) of the frame rows of both CFG halves' inputs (the image-latent
 // channels [C, row_channels) are not touched) and prm[0] = t into both halves' per-clip timestep inputs
@@ -234,7 +146,7 @@ video_prologue_kernel(const float* __restrict__ x, float* __restrict__ xu, int64
 }
 
 // vpred_step_kernel<TMIX_F32> for S videos with the coefficients from prm = {t, sa, s1, sa_next, s1_next, g, ...} and v_u / v_c read
-// from the plans' prediction rows [(clip*F + f)][C][hw]; the same operations in the same order, so the result is that kernel's bit for bit.
+// from the plans' prediction rows [(clip*F + f)][C][hw]; the same two element functions, so the result is that kernel's bit for bit.
 // x is updated in place (element i is read before it is written).
 __global__ void __launch_bounds__(256)
 vpred_step_dev_kernel(float* __restrict__ x, const float* __restrict__ vu, int64_t su, const float* __restrict__ vc, int64_t sc,
@@ -243,10 +155,8 @@ vpred_step_dev_kernel(float* __restrict__ x, const float* __restrict__ vu, int64
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float xv = x[i];
-        const float vv = cfg<TMIX_F32>(vu[video_row_offset(i, C, F, hw, C, su)], vc[video_row_offset(i, C, F, hw, C, sc)], g);
-        const float eps = rnd<TMIX_F32>(rnd<TMIX_F32>(sa * vv) + rnd<TMIX_F32>(s1 * xv));
-        const float x0 = rnd<TMIX_F32>(rnd<TMIX_F32>(sa * xv) - rnd<TMIX_F32>(s1 * vv));
-        x[i] = rnd<TMIX_F32>(rnd<TMIX_F32>(sa_n * x0) + rnd<TMIX_F32>(s1_n * eps));
+        const VPred p = vpred_x0<TMIX_F32>(xv, vu[video_row_offset(i, C, F, hw, C, su)], vc[video_row_offset(i, C, F, hw, C, sc)], g, sa, s1);
+        x[i] = vpred_ddim_move<TMIX_F32>(xv, p, sa, s1, sa_n, s1_n);
     }
 }
 
@@ -274,13 +184,7 @@ extern "C" int tmix_vpred_step(const void* x, const void* v, void* out, int dtyp
                                float sa, float s1, float sa_next, float s1_next, void* stream) {
     if (!x || !v || !out) TMIX_FAIL(TMIX_EINVAL, "vpred_step: null pointer");
     if (n < 1) TMIX_FAIL(TMIX_ESHAPE, "vpred_step: empty latent");
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-    case TMIX_F32:  return launch_vpred<TMIX_F32>(x, v, out, n, g, sa, s1, sa_next, s1_next, st);
-    case TMIX_F16:  return launch_vpred<TMIX_F16>(x, v, out, n, g, sa, s1, sa_next, s1_next, st);
-    case TMIX_BF16: return launch_vpred<TMIX_BF16>(x, v, out, n, g, sa, s1, sa_next, s1_next, st);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "vpred_step: bad dtype %d", dtype);
+    return for_dtype(dtype, "vpred_step", "dtype", [&](auto dt) { return launch_vpred<dt()>(x, v, out, n, g, sa, s1, sa_next, s1_next, (hipStream_t)stream); });
 }
 
 extern "C" int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,
@@ -288,13 +192,7 @@ extern "C" int tmix_frame_inject(void* x, int dtype, int clips, int frames, int6
     if (!x) TMIX_FAIL(TMIX_EINVAL, "frame_inject: null pointer");
     if (clips < 1 || frames < 2 || per_frame < 1) TMIX_FAIL(TMIX_ESHAPE, "frame_inject: clips=%d frames=%d per_frame=%lld", clips, frames, (long long)per_frame);
     const int64_t n = (int64_t)clips * (frames - 1) * per_frame;
-    hipStream_t st = (hipStream_t)stream;
-    switch (dtype) {
-    case TMIX_F32:  return launch_inject<TMIX_F32>(x, per_frame, frames, n, hard, interp, one_minus_interp, st);
-    case TMIX_F16:  return launch_inject<TMIX_F16>(x, per_frame, frames, n, hard, interp, one_minus_interp, st);
-    case TMIX_BF16: return launch_inject<TMIX_BF16>(x, per_frame, frames, n, hard, interp, one_minus_interp, st);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "frame_inject: bad dtype %d", dtype);
+    return for_dtype(dtype, "frame_inject", "dtype", [&](auto dt) { return launch_inject<dt()>(x, per_frame, frames, n, hard, interp, one_minus_interp, (hipStream_t)stream); });
 }
 
 extern "C" int tmix_fused_tweedie_step(const float* x, const void* eps, int eps_dtype, const float* masks,
@@ -307,34 +205,20 @@ extern "C" int tmix_fused_tweedie_step(const float* x, const void* eps, int eps_
     if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "tweedie_step: RESAMPLE needs K>=1");
     if (channels < 1 || hw < 1) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step: empty latent (channels=%d hw=%lld)", channels, (long long)hw);
     if (!(sa > 0.0f)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step: sqrt(alpha) must be > 0");
-    const int64_t n = (int64_t)channels * hw;
-    hipStream_t st = (hipStream_t)stream;
-    switch (eps_dtype) {
-    case TMIX_F32:  return launch<TMIX_F32>(x, eps, masks, out_x, out_x0, K, n, hw, mode, g, sa, s1, sa_next, s1_next, is_last, st);
-    case TMIX_F16:  return launch<TMIX_F16>(x, eps, masks, out_x, out_x0, K, n, hw, mode, g, sa, s1, sa_next, s1_next, is_last, st);
-    case TMIX_BF16: return launch<TMIX_BF16>(x, eps, masks, out_x, out_x0, K, n, hw, mode, g, sa, s1, sa_next, s1_next, is_last, st);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "tweedie_step: bad eps dtype %d", eps_dtype);
+    const HostCoef c = {g, sa, s1, sa_next, s1_next, is_last};
+    return for_dtype(eps_dtype, "tweedie_step", "eps dtype", [&](auto dt) {
+        return launch<dt(), 0>(x, eps, masks, 0, out_x, out_x0, K, (int64_t)channels * hw, hw, mode, c, 0, 1, nullptr, (hipStream_t)stream);
+    });
 }
 
 extern "C" int tmix_fused_tweedie_step_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
                                            int64_t mask_seed_stride, float* out_x, float* out_x0, int K, int channels,
                                            int64_t hw, int mode, int rows, int seeds, const float* params, void* stream) {
-    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_dev: null pointer");
-    if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_dev: bad mode %d", mode);
-    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_dev: FUSION needs masks and K>=1");
-    if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_dev: RESAMPLE needs K>=1");
-    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
-    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
-    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
-    const int64_t n = (int64_t)channels * hw;
-    hipStream_t st = (hipStream_t)stream;
-    switch (eps_dtype) {
-    case TMIX_F32:  return launch_dev<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, st);
-    case TMIX_F16:  return launch_dev<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, st);
-    case TMIX_BF16: return launch_dev<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, st);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_dev: bad eps dtype %d", eps_dtype);
+    const char* me = "tweedie_step_dev";
+    if (int rc = check_dev_step(me, true, false, x, eps, out_x, params, nullptr, nullptr, masks, K, channels, hw, mode, rows, seeds)) return rc;
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        return launch<dt(), 1>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, (int64_t)channels * hw, hw, mode, HostCoef(), rows, seeds, params, (hipStream_t)stream);
+    });
 }
 
 extern "C" int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
@@ -342,49 +226,29 @@ extern "C" int tmix_fused_tweedie_step_keep_dev(const float* x, const void* eps,
                                                 int64_t hw, int mode, int rows, int seeds, const float* params,
                                                 const float* keep_x0, int64_t keep_x0_seed_stride, const float* keep_eps,
                                                 int64_t keep_eps_seed_stride, const float* keep_w, int64_t keep_w_seed_stride, void* stream) {
-    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: null pointer");
-    if (!keep_x0 || !keep_eps || !keep_w) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: null keep pointer");
-    if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: bad mode %d", mode);
-    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: FUSION needs masks and K>=1");
-    if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: RESAMPLE needs K>=1");
-    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_keep_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
-    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
-    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_keep_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
+    const char* me = "tweedie_step_keep_dev";
+    const char* missing = keep_x0 && keep_eps && keep_w ? nullptr : "null keep pointer";
+    if (int rc = check_dev_step(me, true, false, x, eps, out_x, params, nullptr, missing, masks, K, channels, hw, mode, rows, seeds)) return rc;
     const int64_t n = (int64_t)channels * hw;
     if ((keep_x0_seed_stride != 0 && keep_x0_seed_stride < n) || (keep_eps_seed_stride != 0 && keep_eps_seed_stride < n) ||
         (keep_w_seed_stride != 0 && keep_w_seed_stride < hw))
         TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_keep_dev: keep seed strides %lld / %lld / %lld: 0 (shared) or >= %lld / %lld / %lld floats",
                   (long long)keep_x0_seed_stride, (long long)keep_eps_seed_stride, (long long)keep_w_seed_stride, (long long)n, (long long)n, (long long)hw);
     const KeepArgs kp = {keep_x0, keep_eps, keep_w, keep_x0_seed_stride, keep_eps_seed_stride, keep_w_seed_stride};
-    hipStream_t st = (hipStream_t)stream;
-    switch (eps_dtype) {
-    case TMIX_F32:  return launch_extra<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
-    case TMIX_F16:  return launch_extra<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
-    case TMIX_BF16: return launch_extra<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, kp, st);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_keep_dev: bad eps dtype %d", eps_dtype);
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        return launch<dt(), 1>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, HostCoef(), rows, seeds, params, (hipStream_t)stream, kp);
+    });
 }
 
 extern "C" int tmix_fused_tweedie_step_rs_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
                                               int64_t mask_seed_stride, float* out_x, float* out_x0, int K, int channels,
                                               int64_t hw, int mode, int rows, int seeds, const float* params, const float* factors, void* stream) {
-    if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: null pointer");
-    if (!factors) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: null factors");
-    if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: bad mode %d", mode);
-    if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: FUSION needs masks and K>=1");
-    if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: RESAMPLE needs K>=1");
-    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_rs_dev: channels=%d hw=%lld seeds=%d", channels, (long long)hw, seeds);
-    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
-    if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "tweedie_step_rs_dev: mode %d needs %d eps rows per seed, got %d", mode, need, rows);
-    const int64_t n = (int64_t)channels * hw;
+    const char* me = "tweedie_step_rs_dev";
+    if (int rc = check_dev_step(me, true, false, x, eps, out_x, params, nullptr, factors ? nullptr : "null factors", masks, K, channels, hw, mode, rows, seeds)) return rc;
     const RescaleArgs rs = {factors};
-    hipStream_t st = (hipStream_t)stream;
-    switch (eps_dtype) {
-    case TMIX_F32:  return launch_extra<TMIX_F32>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, rs, st);
-    case TMIX_F16:  return launch_extra<TMIX_F16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, rs, st);
-    case TMIX_BF16: return launch_extra<TMIX_BF16>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, n, hw, mode, rows, seeds, params, rs, st);
-    }
-    TMIX_FAIL(TMIX_EINVAL, "tweedie_step_rs_dev: bad eps dtype %d", eps_dtype);
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        return launch<dt(), 1>(x, eps, masks, mask_seed_stride, out_x, out_x0, K, (int64_t)channels * hw, hw, mode, HostCoef(), rows, seeds, params, (hipStream_t)stream, rs);
+    });
 }
 
 extern "C" int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,
@@ -402,11 +266,7 @@ extern "C" int tmix_video_step_prologue(const float* x, float* x_u, int64_t clip
                                         float* t_c, const float* params, int videos, int channels, int frames, int64_t hw,
                                         int row_channels, void* stream) {
     if (!x || !x_u || !t_u || !x_c || !t_c || !params) TMIX_FAIL(TMIX_EINVAL, "video_step_prologue: null pointer");
-    if (videos < 1 || channels < 1 || frames < 1 || hw < 1 || row_channels < channels)
-        TMIX_FAIL(TMIX_ESHAPE, "video_step_prologue: videos=%d channels=%d frames=%d hw=%lld row_channels=%d", videos, channels, frames, (long long)hw, row_channels);
-    const int64_t clip = (int64_t)frames * row_channels * hw;
-    if (clip_stride_u < clip || clip_stride_c < clip)
-        TMIX_FAIL(TMIX_ESHAPE, "video_step_prologue: clip strides %lld / %lld < one clip's %lld floats", (long long)clip_stride_u, (long long)clip_stride_c, (long long)clip);
+    if (int rc = check_video_step("video_step_prologue", videos, channels, frames, hw, row_channels, true, clip_stride_u, clip_stride_c)) return rc;
     const int64_t n = (int64_t)videos * channels * frames * hw;
     int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
     video_prologue_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, x_u, clip_stride_u, t_u, x_c, clip_stride_c, t_c, params,
@@ -418,11 +278,7 @@ extern "C" int tmix_video_step_prologue(const float* x, float* x_u, int64_t clip
 extern "C" int tmix_vpred_step_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
                                    const float* params, int videos, int channels, int frames, int64_t hw, void* stream) {
     if (!x || !v_u || !v_c || !params) TMIX_FAIL(TMIX_EINVAL, "vpred_step_dev: null pointer");
-    if (videos < 1 || channels < 1 || frames < 1 || hw < 1)
-        TMIX_FAIL(TMIX_ESHAPE, "vpred_step_dev: videos=%d channels=%d frames=%d hw=%lld", videos, channels, frames, (long long)hw);
-    const int64_t clip = (int64_t)frames * channels * hw;
-    if (clip_stride_u < clip || clip_stride_c < clip)
-        TMIX_FAIL(TMIX_ESHAPE, "vpred_step_dev: clip strides %lld / %lld < one clip's %lld floats", (long long)clip_stride_u, (long long)clip_stride_c, (long long)clip);
+    if (int rc = check_video_step("vpred_step_dev", videos, channels, frames, hw, channels, false, clip_stride_u, clip_stride_c)) return rc;
     const int64_t n = (int64_t)videos * channels * frames * hw;
     int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
     vpred_step_dev_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, v_u, clip_stride_u, v_c, clip_stride_c, params,

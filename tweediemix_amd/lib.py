@@ -54,6 +54,11 @@ class ConvDesc(C.Structure):
                 ("batch_bias_images", i32), ("col_stats_out", vp), ("S1", vp), ("S2", vp), ("S1_channels", i32), ("S2_channels", i32)]
 
 
+# the 14 arguments the five *_dev step entries begin with (x, eps, eps_dtype, masks, mask_seed_stride, out_x, out_x0, K, channels, hw, mode, rows,
+# seeds, params); the multistep entries take x0_prev behind out_x0
+_DEV_STEP = [vp, vp, C.c_int, vp, i64, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int, C.c_int, vp]
+_DEV_STEP_MS = _DEV_STEP[:7] + [vp] + _DEV_STEP[7:]
+
 SIGNATURES = {
     "tmix_version": (C.c_int, []),
     "tmix_last_error_string": (C.c_char_p, []),
@@ -63,18 +68,13 @@ SIGNATURES = {
     "tmix_prof_end": (C.c_int, []),
     "tmix_fused_tweedie_step": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int,
                                           f32, f32, f32, f32, f32, C.c_int, vp]),
-    "tmix_fused_tweedie_step_dev": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int,
-                                              C.c_int, vp, vp]),
-    "tmix_fused_tweedie_step_keep_dev": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int,
-                                                   C.c_int, vp, vp, i64, vp, i64, vp, i64, vp]),
-    "tmix_fused_tweedie_step_ms_dev": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int,
-                                                 C.c_int, vp, vp]),
+    "tmix_fused_tweedie_step_dev": (C.c_int, _DEV_STEP + [vp]),
+    "tmix_fused_tweedie_step_keep_dev": (C.c_int, _DEV_STEP + [vp, i64, vp, i64, vp, i64, vp]),
+    "tmix_fused_tweedie_step_ms_dev": (C.c_int, _DEV_STEP_MS + [vp]),
     "tmix_cfg_rescale_ws_doubles": (i64, [C.c_int, C.c_int]),
     "tmix_cfg_rescale_factors": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, vp]),
-    "tmix_fused_tweedie_step_rs_dev": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int,
-                                                 C.c_int, vp, vp, vp]),
-    "tmix_fused_tweedie_step_ms_rs_dev": (C.c_int, [vp, vp, C.c_int, vp, i64, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int,
-                                                    C.c_int, vp, vp, vp]),
+    "tmix_fused_tweedie_step_rs_dev": (C.c_int, _DEV_STEP + [vp, vp]),
+    "tmix_fused_tweedie_step_ms_rs_dev": (C.c_int, _DEV_STEP_MS + [vp, vp]),
     "tmix_step_prologue": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, i64, vp]),
     "tmix_window_consensus": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "tmix_mask_edt": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),

@@ -68,36 +68,12 @@ def _seed_stride(t, seeds, extent, what):
     return 0 if t.shape[0] == 1 else extent
 
 
-def fused_tweedie_step_keep_dev(x, eps, masks, mode, K, params, keep_x0, keep_eps, keep_w, out_x=None, out_x0=None):
-    """tmix_fused_tweedie_step_keep_dev: x [S,C,h,w] fp32, eps [S*rows,C,h,w] f32|f16|bf16, masks [K,1,h,w] or [S,K,1,h,w] (FUSION),
-    params the device buffer {t, sa, s1, sa_next, s1_next, is_last, g, -}; keep_x0 [1|S,C,h,w], keep_eps [1|S,C,h,w], keep_w [1|S,1,h,w]
-    (first axis 1: shared by all seeds).  out_x may be x itself (in place).  Returns out_x."""
-    _need_cuda(x, eps, masks, params, keep_x0, keep_eps, keep_w)
+def _dev_step_head(x, eps, masks, mode, K, params, out_x, out_x0, x0_prev=None):
+    """the shared preparation of the *_dev step wrappers: (S, n, hw, rows, out_x, head), head the 14 arguments every such entry begins with
+    (the multistep entries take x0_prev behind the seventh)"""
     assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and params.dtype == torch.float32 and params.numel() >= 8
-    S, Cc, h, w = x.shape
-    n, hw = Cc * h * w, h * w
-    assert eps.shape[0] % S == 0
-    rows = eps.shape[0] // S
-    mss = 0
-    if mode == L.STEP_FUSION:
-        assert masks is not None and masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() in (K * hw, S * K * hw)
-        mss = 0 if masks.numel() == K * hw else K * hw
-    if out_x is None:
-        out_x = torch.empty_like(x)
-    L.check(L.load().tmix_fused_tweedie_step_keep_dev(
-        _p(x), _p(eps), _EPS_DT[eps.dtype], _p(masks), mss, _p(out_x), _p(out_x0), K, Cc, hw, mode, rows, S, _p(params),
-        _p(keep_x0), _seed_stride(keep_x0, S, n, "keep_x0"), _p(keep_eps), _seed_stride(keep_eps, S, n, "keep_eps"),
-        _p(keep_w), _seed_stride(keep_w, S, hw, "keep_w"), _stream()), "tmix_fused_tweedie_step_keep_dev")
-    return out_x
-
-
-def fused_tweedie_step_ms_dev(x, eps, masks, mode, K, params, x0_prev, out_x=None, out_x0=None):
-    """tmix_fused_tweedie_step_ms_dev: x [S,C,h,w] fp32, eps [S*rows,C,h,w] f32|f16|bf16, masks [K,1,h,w] or [S,K,1,h,w] (FUSION), params the
-    device buffer {t, sa, s1, cx, c0, c1, is_last, g} (solver.multistep_coeffs), x0_prev [S,C,h,w] fp32 the history buffer, read and
-    rewritten with this step's x0.  out_x may be x itself (in place).  Returns out_x."""
-    _need_cuda(x, eps, masks, params, x0_prev)
-    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and params.dtype == torch.float32 and params.numel() >= 8
-    assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.shape == x.shape, tuple(x0_prev.shape)
+    if x0_prev is not None:
+        assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.shape == x.shape, tuple(x0_prev.shape)
     S, Cc, h, w = x.shape
     hw = h * w
     assert eps.shape[0] % S == 0
@@ -108,9 +84,29 @@ def fused_tweedie_step_ms_dev(x, eps, masks, mode, K, params, x0_prev, out_x=Non
         mss = 0 if masks.numel() == K * hw else K * hw
     if out_x is None:
         out_x = torch.empty_like(x)
-    L.check(L.load().tmix_fused_tweedie_step_ms_dev(
-        _p(x), _p(eps), _EPS_DT[eps.dtype], _p(masks), mss, _p(out_x), _p(out_x0), _p(x0_prev), K, Cc, hw, mode, rows, S, _p(params),
-        _stream()), "tmix_fused_tweedie_step_ms_dev")
+    head = (_p(x), _p(eps), _EPS_DT[eps.dtype], _p(masks), mss, _p(out_x), _p(out_x0), K, Cc, hw, mode, rows, S, _p(params))
+    return S, Cc * hw, hw, rows, out_x, head
+
+
+def fused_tweedie_step_keep_dev(x, eps, masks, mode, K, params, keep_x0, keep_eps, keep_w, out_x=None, out_x0=None):
+    """tmix_fused_tweedie_step_keep_dev: x [S,C,h,w] fp32, eps [S*rows,C,h,w] f32|f16|bf16, masks [K,1,h,w] or [S,K,1,h,w] (FUSION),
+    params the device buffer {t, sa, s1, sa_next, s1_next, is_last, g, -}; keep_x0 [1|S,C,h,w], keep_eps [1|S,C,h,w], keep_w [1|S,1,h,w]
+    (first axis 1: shared by all seeds).  out_x may be x itself (in place).  Returns out_x."""
+    _need_cuda(x, eps, masks, params, keep_x0, keep_eps, keep_w)
+    S, n, hw, _rows, out_x, head = _dev_step_head(x, eps, masks, mode, K, params, out_x, out_x0)
+    L.check(L.load().tmix_fused_tweedie_step_keep_dev(
+        *head, _p(keep_x0), _seed_stride(keep_x0, S, n, "keep_x0"), _p(keep_eps), _seed_stride(keep_eps, S, n, "keep_eps"),
+        _p(keep_w), _seed_stride(keep_w, S, hw, "keep_w"), _stream()), "tmix_fused_tweedie_step_keep_dev")
+    return out_x
+
+
+def fused_tweedie_step_ms_dev(x, eps, masks, mode, K, params, x0_prev, out_x=None, out_x0=None):
+    """tmix_fused_tweedie_step_ms_dev: x [S,C,h,w] fp32, eps [S*rows,C,h,w] f32|f16|bf16, masks [K,1,h,w] or [S,K,1,h,w] (FUSION), params the
+    device buffer {t, sa, s1, cx, c0, c1, is_last, g} (solver.multistep_coeffs), x0_prev [S,C,h,w] fp32 the history buffer, read and
+    rewritten with this step's x0.  out_x may be x itself (in place).  Returns out_x."""
+    _need_cuda(x, eps, masks, params, x0_prev)
+    _S, _n, _hw, _rows, out_x, head = _dev_step_head(x, eps, masks, mode, K, params, out_x, out_x0, x0_prev)
+    L.check(L.load().tmix_fused_tweedie_step_ms_dev(*head[:7], _p(x0_prev), *head[7:], _stream()), "tmix_fused_tweedie_step_ms_dev")
     return out_x
 
 
@@ -145,25 +141,12 @@ def fused_tweedie_step_rs_dev(x, eps, masks, mode, K, params, factors, out_x=Non
     """tmix_fused_tweedie_step_rs_dev, or with x0_prev (the history buffer) tmix_fused_tweedie_step_ms_rs_dev: the arguments of
     fused_tweedie_step_ms_dev plus factors [S, rows-1] fp32 (cfg_rescale_factors).  out_x may be x itself (in place).  Returns out_x."""
     _need_cuda(x, eps, masks, params, factors, x0_prev)
-    assert x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and params.dtype == torch.float32 and params.numel() >= 8
-    S, Cc, h, w = x.shape
-    hw = h * w
-    assert eps.shape[0] % S == 0
-    rows = eps.shape[0] // S
+    S, _n, _hw, rows, out_x, head = _dev_step_head(x, eps, masks, mode, K, params, out_x, out_x0, x0_prev)
     assert factors.dtype == torch.float32 and factors.is_contiguous() and factors.numel() == S * (rows - 1), tuple(factors.shape)
-    mss = 0
-    if mode == L.STEP_FUSION:
-        assert masks is not None and masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() in (K * hw, S * K * hw)
-        mss = 0 if masks.numel() == K * hw else K * hw
-    if out_x is None:
-        out_x = torch.empty_like(x)
-    head = (_p(x), _p(eps), _EPS_DT[eps.dtype], _p(masks), mss, _p(out_x), _p(out_x0))
-    tail = (K, Cc, hw, mode, rows, S, _p(params), _p(factors), _stream())
     if x0_prev is None:
-        L.check(L.load().tmix_fused_tweedie_step_rs_dev(*head, *tail), "tmix_fused_tweedie_step_rs_dev")
+        L.check(L.load().tmix_fused_tweedie_step_rs_dev(*head, _p(factors), _stream()), "tmix_fused_tweedie_step_rs_dev")
     else:
-        assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.shape == x.shape, tuple(x0_prev.shape)
-        L.check(L.load().tmix_fused_tweedie_step_ms_rs_dev(*head, _p(x0_prev), *tail), "tmix_fused_tweedie_step_ms_rs_dev")
+        L.check(L.load().tmix_fused_tweedie_step_ms_rs_dev(*head[:7], _p(x0_prev), *head[7:], _p(factors), _stream()), "tmix_fused_tweedie_step_ms_rs_dev")
     return out_x
 
 
