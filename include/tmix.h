@@ -238,6 +238,36 @@ int tmix_vpred_step_ms(const void* x, const void* v, void* out, float* x0_prev, 
                        float sa, float s1, float cx, float c0, float c1, void* stream);
 int tmix_vpred_step_ms_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
                            const float* params, int videos, int channels, int frames, int64_t hw, void* stream);
+/* GUIDANCE RESCALE of the video step (no reference counterpart; arXiv:2305.08891 section 3.4 = diffusers' rescale_noise_cfg on the v-prediction,
+ * per video).  One video has n = channels*frames*hw elements.  With v'[i] = the step kernels' cfg(v_u[i], v_c[i], g):
+ *   sd_c, sd_v = the standard deviations of v_c and of v' over the video's n elements (denominator n - 1), in fp64
+ *   f          = fp32( phi*sd_c/sd_v + (1 - phi) ), evaluated in fp64 from the fp32 phi and rounded once; 1.0f where sd_v is zero or a variance
+ *                is not finite (the rule of tmix_cfg_rescale_factors)
+ *   v''[i]     = rnd(f * v'[i])   (rnd: to fp16 for TMIX_F16, else nothing)
+ * and v'' takes the place of v' EVERYWHERE in the step: in x0 = sa x - s1 v'' and in eps = sa v'' + s1 x (both come from the one model output;
+ * unlike tmix_fused_tweedie_step_rs_dev, whose move keeps the unconditional row as its noise term).
+ * tmix_vpred_rescale_factors writes factors[videos].  Video s is the n_per_video CONTIGUOUS elements of `dtype` at v_u + s*stride_u and at
+ *   v_c + s*stride_c (strides in elements; the order inside a video does not matter to a standard deviation): the plan's two half buffers with their
+ *   clip strides, one plan buffer of 2*videos clips with v_c based at clip `videos`, or a dense [2][videos][n] array with v_c = v_u + videos*n.
+ *   g = params[g_slot] is read ON THE DEVICE (slot 5: the params of tmix_vpred_step_dev, 6: of tmix_vpred_step_ms_dev; params holds >= 8 floats).
+ *   ws: tmix_cfg_rescale_ws_doubles(2, videos) doubles, no initial contents required.  Two launches on `stream`, the method of
+ *   tmix_cfg_rescale_factors (a fixed partition of 32 workgroups per video, fp64 sums, no atomics): bit-reproducible, and the factor of a video does
+ *   not depend on how many videos share the call.  The inputs are only read.
+ *   TMIX_EINVAL: a null pointer, a bad dtype, g_slot outside 0..7, phi outside [0, 1] or not finite.  TMIX_ESHAPE: videos outside 1..65535,
+ *   n_per_video < 2, a stride shorter than n_per_video.  All before any launch.
+ * tmix_vpred_step_rs / _ms_rs: tmix_vpred_step / _ms on [videos][n_per_video] (v: [2][videos][n_per_video]) with one more argument, factors [videos]:
+ *   element i uses factors[i / n_per_video].  tmix_vpred_step_rs_dev / _ms_rs_dev: tmix_vpred_step_dev / _ms_dev with factors [videos] behind hw.
+ *   With all factors 1.0f the results are the parent entry's bit for bit.  TMIX_EINVAL on null factors; otherwise the parent's checks. */
+int tmix_vpred_rescale_factors(const void* v_u, int64_t stride_u, const void* v_c, int64_t stride_c, int dtype, float* factors, double* ws,
+                               int videos, int64_t n_per_video, const float* params, int g_slot, float phi, void* stream);
+int tmix_vpred_step_rs(const void* x, const void* v, void* out, int dtype, int videos, int64_t n_per_video, float g,
+                       float sa, float s1, float sa_next, float s1_next, const float* factors, void* stream);
+int tmix_vpred_step_rs_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
+                           const float* params, int videos, int channels, int frames, int64_t hw, const float* factors, void* stream);
+int tmix_vpred_step_ms_rs(const void* x, const void* v, void* out, float* x0_prev, int dtype, int videos, int64_t n_per_video, float g,
+                          float sa, float s1, float cx, float c0, float c1, const float* factors, void* stream);
+int tmix_vpred_step_ms_rs_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
+                              const float* params, int videos, int channels, int frames, int64_t hw, const float* factors, void* stream);
 /* First-frame feature injection of the patched ResnetBlock2D.forward (video_gen/utils_attn.py:433-455), in place on
  * x [clips][frames][per_frame]: frames 1.. <- frame 0 (hard) or interp*frame0 + one_minus_interp*frame. */
 int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,

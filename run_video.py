@@ -30,7 +30,13 @@ frames are decoded in batches (vae.decode_in_groups), so a video's GIF does not 
 Few-step sampling (no reference counterpart):
   --solver dpmpp2m          every step is a DPM-Solver++(2M) step on the x0 of the v-prediction (tmix_vpred_step_ms_dev)
   --timestep_spacing logsnr the num_inference_steps timesteps uniform in log-SNR from the leading grid's first timestep to 1
-Without them (ddim, leading) the run is the reference's loop; an n the grid or the solver cannot take is refused before the GPU is touched."""
+Without them (ddim, leading) the run is the reference's loop; an n the grid or the solver cannot take is refused before the GPU is touched.
+
+Guidance rescale (no reference counterpart; arXiv:2305.08891 section 3.4):
+  --guidance_rescale PHI    in [0, 1]; 0 (default): off, the run above launch for launch; 0.7: the paper's value.  Every step scales each video's
+                            guided v-prediction back towards the standard deviation of its text-conditional one (tmix_vpred_rescale_factors, then
+                            tmix_vpred_step_rs_dev / tmix_vpred_step_ms_rs_dev); meant for exactly this setting: zero terminal SNR, v-prediction,
+                            --guidance_scale 9.  Combines with every flag above; a value outside [0, 1] is refused before the GPU is touched."""
 import argparse
 import os
 import sys
@@ -76,6 +82,9 @@ def build_parser():
     # few-step sampling; the defaults are the reference's loop
     p.add_argument("--solver", default="ddim", choices=["ddim", "dpmpp2m"], help="dpmpp2m: every step is a DPM-Solver++(2M) step on the x0 of the v-prediction")
     p.add_argument("--timestep_spacing", default="leading", choices=["leading", "logsnr"], help="logsnr: timesteps uniform in log-SNR from the leading grid's first timestep to 1")
+    # guidance rescale; 0 is the run without it
+    p.add_argument("--guidance_rescale", type=float, default=0.0, help="phi in [0, 1]: scale each video's guided v-prediction back towards the standard "
+                   "deviation of the conditional one (arXiv:2305.08891 section 3.4; 0: off, 0.7: the paper's value)")
     return p
 
 
@@ -114,6 +123,15 @@ def check_args(opt):
         raise SystemExit(f"--conditioning_path holds the conditioning of ONE video; this run has {len(videos)} videos "
                          f"({len(images)} image(s) x {opt.num_seeds} seed(s)): drop it or run one image with one seed")
     return images, videos
+
+
+def checked_rescale(opt):
+    """--guidance_rescale through the one validator of phi, on the host before anything touches the GPU or any rank is started"""
+    from tweediemix_amd.guidance import validate_phi
+    try:
+        return validate_phi(opt.guidance_rescale, "--guidance_rescale")
+    except ValueError as e:
+        raise SystemExit(str(e))
 
 
 def _vae_config(j):
@@ -240,6 +258,7 @@ def main(argv=None):
     videos, batched decode, the gather to rank 0, which writes every file."""
     opt = build_parser().parse_args(argv)
     images, videos = check_args(opt)
+    phi = checked_rescale(opt)
     from tweediemix_amd import dist as D, i2vgen as I, launch as LA, video as V
     few_step = (opt.solver, opt.timestep_spacing) != ("ddim", "leading")
     if opt.gpus > 1 and not LA.launched():
@@ -300,7 +319,7 @@ def main(argv=None):
         smp = plan = None                                            # the previous batch's plan and graphs go before the next are built
         plan = I.I2VVideoPlan(Wt, S, Fr, h, w, fe, ctx, ilf, streams=opt.streams, interp=opt.interp_ratio)
         inj = V.FeatureInjector(sch.injection_schedule(opt.injection_timestep), opt.interp_ratio, clips=2 * S, frames=Fr)
-        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs, solver=opt.solver)
+        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs, solver=opt.solver, guidance_rescale=phi)
         lats.append(smp.sample(torch.cat([xs[i] for i in batch]).to(dev))[:n_real])
     smp = plan = None
     lat = torch.cat(lats) if lats else torch.zeros(0, 4, Fr, h, w, device=dev)

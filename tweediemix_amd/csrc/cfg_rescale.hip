@@ -5,6 +5,8 @@
 // read, and the summation order is a function of (n, RS_P, RS_THREADS) alone: the factors are the same bits run after run.
 // e_r is formed by the step kernels' own cfg<DT> (step_core.h; compiled with -ffp-contract=off like them), so the statistics are those of the
 // very values the step kernel will scale.
+// Second entry, the same method per VIDEO for the v-prediction step kernels (tmix_vpred_rescale_factors): one accumulation function
+// (rescale_partial_sums) and one finalise kernel serve both.
 #include "step_core.h"
 
 namespace {
@@ -18,24 +20,19 @@ __device__ __forceinline__ double wave_sum(double v) {      // wave64 butterfly:
     return v;
 }
 
-// grid (RS_P, rows - 1, seeds).  Workgroup (p, r - 1, s) reads elements p * RS_THREADS + tid + k * RS_P * RS_THREADS of eu and ec_r once and writes
-// {S_c, Q_c, S_e, Q_e} to slot ws[s][r - 1][p]: sum and sum of squares of ec_r and of e_r, in fp64, of the values MINUS the row's element 0 (the
-// difference of two fp32 values in fp64; the variance does not see the shift).  The shift keeps a constant row at S = Q = 0 exactly and takes the
-// mean^2 / variance term out of the one-pass formula's error.  Rows the mode does not read (r > used) are left alone: finalise does not read them.
+// The sums of ONE workgroup's share of one row of n elements (eu: the unconditional values, ec: the conditional ones), shared by the image kernel
+// (a row of eps) and the video kernel (a video's clip): workgroup p of RS_P reads elements p * RS_THREADS + tid + k * RS_P * RS_THREADS of eu and ec
+// once and writes {S_c, Q_c, S_e, Q_e} to slot[0..4): sum and sum of squares of ec and of e = cfg(eu, ec, g), in fp64, of the values MINUS the row's
+// element 0 (the difference of two fp32 values in fp64; the variance does not see the shift).  The shift keeps a constant row at S = Q = 0 exactly
+// and takes the mean^2 / variance term out of the one-pass formula's error.  Every loop is bounded by n; the order of the additions is a function
+// of (n, RS_P, RS_THREADS) alone.
 template <int DT>
-__global__ void __launch_bounds__(RS_THREADS)
-rescale_partials_kernel(const typename EpsT<DT>::T* __restrict__ eps, double* __restrict__ ws, int64_t n, int rows, int used,
-                        const float* __restrict__ prm, int g_slot) {
-    const int r = blockIdx.y + 1;
-    if (r > used) return;
-    const int64_t sd = blockIdx.z;
-    const float g = prm[g_slot];
-    const typename EpsT<DT>::T* eu = eps + sd * rows * n;
-    const typename EpsT<DT>::T* ec = eu + (int64_t)r * n;
+__device__ __forceinline__ void rescale_partial_sums(const typename EpsT<DT>::T* __restrict__ eu, const typename EpsT<DT>::T* __restrict__ ec, int64_t n,
+                                                     float g, int p, double* __restrict__ slot) {
     const float c0 = EpsT<DT>::ld(ec, 0);
     const float e0 = cfg<DT>(EpsT<DT>::ld(eu, 0), c0, g);
     double sc = 0.0, qc = 0.0, se = 0.0, qe = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x; i < n; i += (int64_t)RS_P * RS_THREADS) {
+    for (int64_t i = (int64_t)p * RS_THREADS + threadIdx.x; i < n; i += (int64_t)RS_P * RS_THREADS) {
         const float c = EpsT<DT>::ld(ec, i);
         const float e = cfg<DT>(EpsT<DT>::ld(eu, i), c, g);
         const double dc = (double)c - (double)c0, de = (double)e - (double)e0;
@@ -50,8 +47,32 @@ rescale_partials_kernel(const typename EpsT<DT>::T* __restrict__ eps, double* __
     if (threadIdx.x < 4) {
         double a = part[0][threadIdx.x];
         for (int w = 1; w < RS_WAVES; ++w) a = a + part[w][threadIdx.x];
-        ws[((sd * (rows - 1) + (r - 1)) * RS_P + blockIdx.x) * 4 + threadIdx.x] = a;
+        slot[threadIdx.x] = a;
     }
+}
+
+// grid (RS_P, rows - 1, seeds).  Workgroup (p, r - 1, s) writes the sums of its share of eps row r of seed s (rescale_partial_sums) to slot
+// ws[s][r - 1][p].  Rows the mode does not read (r > used) are left alone: finalise does not read them.
+template <int DT>
+__global__ void __launch_bounds__(RS_THREADS)
+rescale_partials_kernel(const typename EpsT<DT>::T* __restrict__ eps, double* __restrict__ ws, int64_t n, int rows, int used,
+                        const float* __restrict__ prm, int g_slot) {
+    const int r = blockIdx.y + 1;
+    if (r > used) return;
+    const int64_t sd = blockIdx.z;
+    const typename EpsT<DT>::T* eu = eps + sd * rows * n;
+    rescale_partial_sums<DT>(eu, eu + (int64_t)r * n, n, prm[g_slot], blockIdx.x, ws + ((sd * (rows - 1) + (r - 1)) * RS_P + blockIdx.x) * 4);
+}
+
+// VIDEO: grid (RS_P, videos).  Video s is the n contiguous elements at vu + s * su and vc + s * sc (strides in elements; a standard
+// deviation does not care about the order inside a clip, so plan rows and the pipeline layout are served alike); slot ws[s][p].  The partition of
+// a video does not depend on `videos`: co-batched videos get the bits of their single runs.
+template <int DT>
+__global__ void __launch_bounds__(RS_THREADS)
+vpred_rescale_partials_kernel(const typename EpsT<DT>::T* __restrict__ vu, int64_t su, const typename EpsT<DT>::T* __restrict__ vc, int64_t sc,
+                              double* __restrict__ ws, int64_t n, const float* __restrict__ prm, int g_slot) {
+    const int64_t s = blockIdx.y;
+    rescale_partial_sums<DT>(vu + s * su, vc + s * sc, n, prm[g_slot], blockIdx.x, ws + (s * RS_P + blockIdx.x) * 4);
 }
 
 // one lane per (seed, row): the RS_P partials in index order, the variances (Q - S*S/n) / (n - 1), the factor in fp64 rounded once to fp32.
@@ -87,6 +108,18 @@ int launch_rescale(const void* eps, float* factors, double* ws, int64_t n, int r
     return TMIX_OK;
 }
 
+// the video pair: the partials per video, then rescale_finalise_kernel with every video as a "seed" of two rows (rows = 2, used = 1)
+template <int DT>
+int launch_vpred_rescale(const void* vu, int64_t su, const void* vc, int64_t sc, float* factors, double* ws, int videos, int64_t n, const float* prm,
+                         int g_slot, float phi, hipStream_t st) {
+    typedef typename EpsT<DT>::T T;
+    vpred_rescale_partials_kernel<DT><<<dim3(RS_P, (unsigned)videos), RS_THREADS, 0, st>>>((const T*)vu, su, (const T*)vc, sc, ws, n, prm, g_slot);
+    TMIX_LAUNCH_CHECK();
+    rescale_finalise_kernel<<<(unsigned)((videos + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(ws, factors, n, 2, 1, videos, phi);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t tmix_cfg_rescale_ws_doubles(int rows, int seeds) {
@@ -109,5 +142,21 @@ extern "C" int tmix_cfg_rescale_factors(const void* eps, int eps_dtype, float* f
     if (rows < used + 1 || rows > 256) TMIX_FAIL(TMIX_ESHAPE, "cfg_rescale_factors: mode %d needs %d..256 eps rows per seed, got %d", mode, used + 1, rows);
     return for_dtype(eps_dtype, "cfg_rescale_factors", "eps dtype", [&](auto dt) {
         return launch_rescale<dt()>(eps, factors, ws, n, rows, used, seeds, params, g_slot, phi, (hipStream_t)stream);
+    });
+}
+
+extern "C" int tmix_vpred_rescale_factors(const void* v_u, int64_t stride_u, const void* v_c, int64_t stride_c, int dtype, float* factors, double* ws,
+                                          int videos, int64_t n_per_video, const float* params, int g_slot, float phi, void* stream) {
+    const char* me = "vpred_rescale_factors";
+    if (!v_u || !v_c || !factors || !ws || !params) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
+    if (dtype != TMIX_F32 && dtype != TMIX_F16 && dtype != TMIX_BF16) TMIX_FAIL(TMIX_EINVAL, "%s: bad dtype %d", me, dtype);
+    if (g_slot < 0 || g_slot > 7) TMIX_FAIL(TMIX_EINVAL, "%s: g_slot %d outside 0..7", me, g_slot);
+    if (!(phi >= 0.0f && phi <= 1.0f)) TMIX_FAIL(TMIX_EINVAL, "%s: phi %g outside [0, 1]", me, (double)phi);
+    if (videos < 1 || videos > 65535) TMIX_FAIL(TMIX_ESHAPE, "%s: videos=%d (1..65535)", me, videos);
+    if (n_per_video < 2) TMIX_FAIL(TMIX_ESHAPE, "%s: a standard deviation needs n >= 2 elements per video, got %lld", me, (long long)n_per_video);
+    if (stride_u < n_per_video || stride_c < n_per_video)
+        TMIX_FAIL(TMIX_ESHAPE, "%s: strides %lld / %lld < one video's %lld elements", me, (long long)stride_u, (long long)stride_c, (long long)n_per_video);
+    return for_dtype(dtype, me, "dtype", [&](auto dt) {
+        return launch_vpred_rescale<dt()>(v_u, stride_u, v_c, stride_c, factors, ws, videos, n_per_video, params, g_slot, phi, (hipStream_t)stream);
     });
 }

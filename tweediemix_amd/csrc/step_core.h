@@ -39,7 +39,9 @@ template <int DT> __device__ __forceinline__ float cfg(float eu, float ec, float
 // RESCALE: every guided prediction e_r a step kernel forms becomes rnd<DT>(f_r * e_r) with f_r = fac[seed][r - 1] (layout [seeds][rows - 1];
 // tmix_cfg_rescale_factors writes it: DESIGN.md 7k).  f_r = 1.0f gives e_r back bit for bit.  The flag is the presence of ONE trailing
 // RescaleArgs kernel argument: without it a kernel has the arguments it had before the rescale existed.
-struct RescaleArgs { const float* fac; };
+// The video step kernels read fac[i / per]: one factor per video of `per` elements (tmix_vpred_rescale_factors); the image kernels
+// leave per at 0 and never read it.
+struct RescaleArgs { const float* fac; int64_t per = 0; };
 __device__ __forceinline__ RescaleArgs rescale_args(const RescaleArgs& r) { return r; }
 
 // The blended Tweedie estimate of element i, the x0 of EVERY fused step (fusion_sampling.py:376-385,392-403,406-412): CFG per eps row, the rescale
@@ -77,10 +79,13 @@ __device__ __forceinline__ float blended_x0(const typename EpsT<DT>::T* eps, con
 
 // ---- video sampler (I2VGen-XL loop): video_gen/pipeline_i2vgen_xl.py:699-719.  Latents and predictions share the model dtype in that loop, so in
 // fp16 mode EVERY binary op rounds (rnd<DT>).
-// one element's guided v-prediction and the x0 it gives: what the DDIM and the multistep video kernels have in common
+// one element's guided v-prediction and the x0 it gives: what the DDIM and the multistep video kernels have in common.  RS: the guided prediction
+// is rescaled, v'' = rnd<DT>(f * v'), before ANYTHING uses it -- x0 here and, through VPred::vv, the eps of vpred_ddim_move (in the video loop both
+// come from the one model output; the image kernels' move keeps the unconditional row instead).  Without RS f is not read.
 struct VPred { float vv, x0; };
-template <int DT> __device__ __forceinline__ VPred vpred_x0(float xv, float vu, float vc, float g, float sa, float s1) {
-    const float vv = cfg<DT>(vu, vc, g);
+template <int DT, bool RS = false> __device__ __forceinline__ VPred vpred_x0(float xv, float vu, float vc, float g, float sa, float s1, float f = 1.0f) {
+    float vv = cfg<DT>(vu, vc, g);
+    if constexpr (RS) vv = rnd<DT>(f * vv);
     return {vv, rnd<DT>(rnd<DT>(sa * xv) - rnd<DT>(s1 * vv))};
 }
 // the DDIM move of that element: eps from (x, v), then sa_n * x0 + s1_n * eps

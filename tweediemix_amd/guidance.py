@@ -10,6 +10,9 @@ with the standard deviations taken over the row's n = C h w elements; phi = 0 sw
 phi = 0.7 is the paper's value.  Where sd(e_r) is zero or a variance is not finite f_r = 1: OUR choice (diffusers divides and produces inf / nan).
 
 Everything here is host code and loads no library: the kernels (csrc/cfg_rescale.hip; the *_rs_dev step entries) are compared with it.
+
+The video sampler's form (the second half of this file) takes the statistics per video of the guided v-prediction and puts the
+rescaled prediction into x0 AND into the move's eps term.
 """
 from __future__ import annotations
 
@@ -109,3 +112,68 @@ def rescaled_multistep_reference(mode, x, eps, masks, x0_prev, factors, g, sa, s
     K = 1 if mode == STEP_PLAIN else np.asarray(masks).shape[0]
     ep = rescaled_rows(eps[:K + 1], np.asarray(factors, F32)[:K], g, lowp)
     return SV.multistep_step_reference(mode, x, _as_guided(ep), masks, x0_prev, 1.0, sa, s1, cx, c0, c1, is_last, lowp)
+
+
+# ------------------------------------------------------------------------------------------------ video sampler (v-prediction)
+# diffusers' rescale_noise_cfg on the guided v-prediction, per VIDEO: v' = cfg(v_u, v_c, g), f = phi sd(v_c) / sd(v') + (1 - phi) over the video's
+# n = C F h w elements, v'' = rnd(f v').  v'' replaces v' in x0 = sa x - s1 v'' AND in eps = sa v'' + s1 x: the video loop hands the scheduler one
+# model output and both come from it (the image path above keeps the unconditional row as the move's noise term).
+# lowp as in solver.vpred_multistep_reference: None, np.float16 (every operation rounds) or "bf16" (fp32 arithmetic, one rounding at the store).
+def _lp(lowp):
+    return None if isinstance(lowp, str) and lowp == "bf16" else lowp
+
+
+def vpred_guided(v_u, v_c, g, lowp=None):
+    """v' = cfg(v_u, v_c, g) elementwise, fp32 with the kernel's rounding points"""
+    return SV._cfg(np.asarray(v_u, F32), np.asarray(v_c, F32), g, _lp(lowp))
+
+
+def vpred_rescale_factors_reference(v_u, v_c, g, phi, lowp=None):
+    """factors [B] fp32 of v_u, v_c [B, ...] (fp32 copies of values of the model dtype): what tmix_vpred_rescale_factors writes, up to the order
+    of the fp64 sums.  Per video: v' elementwise as the kernel forms it; mean and variance two-pass in fp64 (denominator n - 1); the factor in fp64
+    from the fp32 value of phi, rounded once; 1 where sd(v') is zero or a variance is not finite."""
+    v_u, v_c = np.asarray(v_u, F32), np.asarray(v_c, F32)
+    ph = float(F32(validate_phi(phi, "phi")))
+    vv = vpred_guided(v_u, v_c, g, lowp)
+    out = np.ones(v_c.shape[0], F32)
+    for b in range(v_c.shape[0]):
+        c64, e64 = v_c[b].astype(np.float64).reshape(-1), vv[b].astype(np.float64).reshape(-1)
+        n = c64.size
+        with np.errstate(all="ignore"):
+            vc = float(((c64 - c64.mean()) ** 2).sum() / (n - 1))
+            ve = float(((e64 - e64.mean()) ** 2).sum() / (n - 1))
+            if math.isfinite(vc) and math.isfinite(ve) and ve > 0.0:
+                out[b] = F32(ph * math.sqrt(vc) / math.sqrt(ve) + (1.0 - ph))
+    return out
+
+
+def vpred_rescaled(v, factors, g, lowp=None):
+    """v'' = rnd(f_b v'_b) of v [2B, ...] (uncond rows first) -> [B, ...] fp32"""
+    v = np.asarray(v, F32)
+    B = v.shape[0] // 2
+    vv = vpred_guided(v[:B], v[B:], g, lowp)
+    f = np.asarray(factors, F32).reshape((B,) + (1,) * (vv.ndim - 1))
+    return SV._h((f * vv).astype(F32), _lp(lowp))
+
+
+def vpred_rescaled_step_reference(x, v, factors, g, sa, s1, sa_next, s1_next, lowp=None):
+    """numpy restatement of tmix_vpred_step_rs (and, with lowp None, of tmix_vpred_step_rs_dev per video) -> (out, x0): the DDIM move of the video
+    loop on v'' -- eps = sa v'' + s1 x, x0 = sa x - s1 v'', out = sa' x0 + s1' eps, every product and sum its own fp32 operation
+    (oracle.tweedie_oracle.video_vpred_step's operations; tests/test_video_rescale_cpu.py pins the two at factor 1).  Compared by equality."""
+    x = np.asarray(x, F32)
+    lp = _lp(lowp)
+    h = lambda a: SV._h(a, lp)
+    vv = vpred_rescaled(v, factors, g, lowp)
+    eps = h(h(F32(sa) * vv) + h(F32(s1) * x))
+    x0 = h(h(F32(sa) * x) - h(F32(s1) * vv)).astype(F32)
+    out = h(h(F32(sa_next) * x0) + h(F32(s1_next) * eps)).astype(F32)
+    if lp is not lowp:
+        out = SV._bf16_round(out)
+    return out, x0
+
+
+def vpred_rescaled_multistep_reference(x, v, x0_prev, factors, g, sa, s1, cx, c0, c1, lowp=None):
+    """numpy restatement of tmix_vpred_step_ms_rs (and, with lowp None, of tmix_vpred_step_ms_rs_dev per video) -> (out, x0):
+    solver.vpred_multistep_reference on [0; v''] with g = 1 (cfg(0, e, 1) gives e back exactly).  Compared by equality."""
+    vv = vpred_rescaled(v, factors, g, lowp)
+    return SV.vpred_multistep_reference(x, np.concatenate([np.zeros_like(vv), vv]), x0_prev, 1.0, sa, s1, cx, c0, c1, lowp)      # _as_guided for B videos

@@ -937,6 +937,98 @@ def video_step_params_ms(t, g, at, coeffs, out=None):
     return out
 
 
+def vpred_rescale_ws(videos, device):
+    """the fp64 workspace tmix_vpred_rescale_factors needs for `videos` videos (contents irrelevant: written before read)"""
+    return cfg_rescale_ws(2, videos, device)
+
+
+def _vpred_rescale(v_u, su, v_c, sc, videos, n, params, g_slot, phi, out, ws):
+    from .guidance import validate_phi
+    _need_cuda(v_u, v_c, params, out, ws)
+    assert v_u.dtype == v_c.dtype and v_u.is_contiguous() and v_c.is_contiguous() and params.dtype == torch.float32 and params.numel() >= 8
+    for buf, st in ((v_u, su), (v_c, sc)):
+        assert buf.numel() >= (videos - 1) * st + n, (tuple(buf.shape), videos, st, n)
+    if out is None:
+        out = torch.empty(videos, device=v_u.device, dtype=torch.float32)
+    if ws is None:
+        ws = vpred_rescale_ws(videos, v_u.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == videos, tuple(out.shape)
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= L.load().tmix_cfg_rescale_ws_doubles(2, videos)
+    L.check(L.load().tmix_vpred_rescale_factors(_p(v_u), su, _p(v_c), sc, _EPS_DT[v_u.dtype], _p(out), _p(ws), videos, n, _p(params), int(g_slot),
+                                                validate_phi(phi, "phi"), _stream()), "tmix_vpred_rescale_factors")
+    return out
+
+
+def vpred_rescale_factors(v, params, g_slot, phi, out=None, ws=None):
+    """tmix_vpred_rescale_factors on the host loop's layout: v [2B,...] f32|f16|bf16 (uncond rows first), params a device buffer (>= 8 floats) with g
+    in slot g_slot, phi in [0, 1] -> factors [B] fp32 (guidance.vpred_rescale_factors_reference), one per video."""
+    assert v.shape[0] % 2 == 0
+    B = v.shape[0] // 2
+    n = v.numel() // (2 * B)
+    return _vpred_rescale(v[:B], n, v[B:], n, B, n, params, g_slot, phi, out, ws)
+
+
+def vpred_rescale_factors_dev(v_u, v_c, videos, n_per_video, params, g_slot, phi, out=None, ws=None, clip_stride_u=None, clip_stride_c=None):
+    """tmix_vpred_rescale_factors on the plans' prediction rows v_u / v_c [(S*F), C, h, w] fp32 (clip s at s * clip_stride floats, as vpred_step_dev
+    reads them), g from params[g_slot] (5: video_step_params, 6: video_step_params_ms) -> factors [S] fp32."""
+    return _vpred_rescale(v_u, clip_stride_u or n_per_video, v_c, clip_stride_c or n_per_video, int(videos), int(n_per_video), params, g_slot, phi,
+                          out, ws)
+
+
+def _video_factors(factors, videos):
+    assert factors.is_cuda and factors.dtype == torch.float32 and factors.is_contiguous() and factors.numel() == videos, (tuple(factors.shape), videos)
+    return _p(factors)
+
+
+def vpred_step_rs(x, v, g, at, at_next, factors, out=None):
+    """vpred_step with the guided prediction of video b scaled by factors[b] (tmix_vpred_step_rs): x [B,...], v [2B,...]."""
+    _need_cuda(x, v)
+    assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
+    out = torch.empty_like(x) if out is None else out
+    B = x.shape[0]
+    f = np.float32
+    sa, s1 = np.sqrt(f(at)), np.sqrt(f(1) - f(at))
+    san, s1n = np.sqrt(f(at_next)), np.sqrt(f(1) - f(at_next))
+    L.check(L.load().tmix_vpred_step_rs(_p(x), _p(v), _p(out), _EPS_DT[x.dtype], B, x.numel() // B, float(g), float(sa), float(s1),
+                                        float(san), float(s1n), _video_factors(factors, B), _stream()), "tmix_vpred_step_rs")
+    return out
+
+
+def vpred_step_ms_rs(x, v, g, at, coeffs, x0_prev, factors, out=None):
+    """vpred_step_ms with the guided prediction of video b scaled by factors[b] (tmix_vpred_step_ms_rs)."""
+    _need_cuda(x, v, x0_prev)
+    sa, s1 = np.sqrt(np.float32(at)), np.sqrt(np.float32(1) - np.float32(at))
+    cx, c0, c1 = coeffs
+    assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
+    assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
+    out = torch.empty_like(x) if out is None else out
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    B = x.shape[0]
+    L.check(L.load().tmix_vpred_step_ms_rs(_p(x), _p(v), _p(out), _p(x0_prev), _EPS_DT[x.dtype], B, x.numel() // B, float(g), float(sa), float(s1),
+                                           float(cx), float(c0), float(c1), _video_factors(factors, B), _stream()), "tmix_vpred_step_ms_rs")
+    return out
+
+
+def vpred_step_rs_dev(x, v_u, v_c, params, factors, x0_prev=None, clip_stride_u=None, clip_stride_c=None):
+    """tmix_vpred_step_rs_dev, or with x0_prev (the history buffer) tmix_vpred_step_ms_rs_dev: the arguments of vpred_step_dev / vpred_step_ms_dev
+    plus factors [S] fp32 (vpred_rescale_factors_dev).  In place on x [S,C,F,h,w] fp32; returns x."""
+    _need_cuda(x, v_u, v_c, params, x0_prev)
+    assert x.dtype == v_u.dtype == v_c.dtype == torch.float32 and x.is_contiguous() and params.numel() >= 8
+    S, Cc, Fr, h, w = x.shape
+    su = clip_stride_u or Fr * Cc * h * w
+    sc = clip_stride_c or Fr * Cc * h * w
+    for buf, st in ((v_u, su), (v_c, sc)):
+        assert buf.is_contiguous() and buf.numel() >= (S - 1) * st + Fr * Cc * h * w
+    fp = _video_factors(factors, S)
+    if x0_prev is None:
+        L.check(L.load().tmix_vpred_step_rs_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(params), S, Cc, Fr, h * w, fp, _stream()), "tmix_vpred_step_rs_dev")
+    else:
+        assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
+        L.check(L.load().tmix_vpred_step_ms_rs_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(x0_prev), _p(params), S, Cc, Fr, h * w, fp, _stream()),
+                "tmix_vpred_step_ms_rs_dev")
+    return x
+
+
 def frame_inject(x, clips, frames, interp=None):
     """first-frame feature injection (video_gen/utils_attn.py:433-455), in place on x [(clips*frames), ...] contiguous."""
     _need_cuda(x)

@@ -178,20 +178,34 @@ def _check_solver(solver):
 
 @torch.no_grad()
 def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None,
-                solver: str = "ddim"):
+                solver: str = "ddim", guidance_rescale: float = 0.0):
     """pipeline_i2vgen_xl.py:680-719.  unet(latent_model_input [2B,C,F,H,W], t) -> v-prediction of the same shape (the
     caller closes over prompt/image conditioning; an i2vgen plan behind it needs its `inject` flag set for t, from
     injection_active); latents [B,C,F,H,W] on the GPU in the model dtype.  solver="dpmpp2m": every step is tmix_vpred_step_ms on the
-    model dtype with an fp32 history of x0."""
+    model dtype with an fp32 history of x0.  guidance_rescale = phi > 0: every step is tmix_vpred_rescale_factors on
+    v (one factor per video, g read from a small device tensor) and then the _rs form of the step entry; 0 is the loop without it, launch for launch."""
+    from .guidance import validate_phi
     ms = _check_solver(solver)
+    phi = validate_phi(guidance_rescale)
     x = latents.contiguous()
     if ms:
         phase, hist = SolverPhase(schedule), torch.zeros_like(x, dtype=torch.float32)
+    if phi > 0.0:
+        B = x.shape[0]
+        g_dev = torch.zeros(8, device=x.device, dtype=torch.float32)
+        g_dev[0] = float(guidance_scale)
+        fac, ws = torch.empty(B, device=x.device, dtype=torch.float32), ops.vpred_rescale_ws(B, x.device)
     for t in schedule.timesteps:
         if injector is not None:
             injector.register_time(t)
         v = unet(torch.cat([x, x]), int(t)).contiguous()
-        if ms:
+        if phi > 0.0:
+            ops.vpred_rescale_factors(v, g_dev, 0, phi, out=fac, ws=ws)
+            if ms:
+                x = ops.vpred_step_ms_rs(x, v, guidance_scale, schedule.alpha(int(t)), phase.coeffs(int(t)), hist, fac)
+            else:
+                x = ops.vpred_step_rs(x, v, guidance_scale, schedule.alpha(int(t)), schedule.next_alpha(int(t)), fac)
+        elif ms:
             x = ops.vpred_step_ms(x, v, guidance_scale, schedule.alpha(int(t)), phase.coeffs(int(t)), hist)
         else:
             x = ops.vpred_step(x, v, guidance_scale, schedule.alpha(int(t)), schedule.next_alpha(int(t)))
@@ -209,12 +223,20 @@ class VideoSampler:
 
     solver="dpmpp2m" (DESIGN.md 7j): the step ends in tmix_vpred_step_ms_dev instead, on one fp32 history buffer `x0_prev` of the state's
     shape; params is then {t, sa, s1, cx, c0, c1, g, 0} and the graphs are keyed (inject, "ms").  The order of a step sits in the uploaded
-    coefficients (SolverPhase), so one graph serves both orders and a step stays one 32-byte upload and one replay."""
+    coefficients (SolverPhase), so one graph serves both orders and a step stays one 32-byte upload and one replay.
+
+    guidance_rescale = phi > 0: behind the plan's chains come tmix_vpred_rescale_factors (two small launches: one factor per video
+    into `rs_factors` [S], g read on the device from params) and the _rs_dev form of whichever step entry runs; the graphs are keyed (inject, "rs")
+    and (inject, "ms", "rs"); phi is a launch argument fixed at capture, so a step stays one 32-byte upload and one replay.  The statistics'
+    partition per video does not depend on S: video s of a batch is still bit for bit its single run.  phi = 0 is the sampler without it: no new
+    launch, buffer or graph key."""
 
     def __init__(self, plan, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None, use_graphs: bool = True,
-                 solver: str = "ddim"):
+                 solver: str = "ddim", guidance_rescale: float = 0.0):
+        from .guidance import validate_phi
         self.plan, self.schedule, self.g, self.injector, self.use_graphs = plan, schedule, float(guidance_scale), injector, use_graphs
         self.solver, self.ms = solver, _check_solver(solver)
+        self.guidance_rescale = validate_phi(guidance_rescale)
         cfg = plan.cfg
         dev = plan.plans[0].dev
         self.state = torch.zeros(plan.videos, cfg.in_channels, plan.frames, plan.h, plan.w, device=dev, dtype=torch.float32)
@@ -227,12 +249,20 @@ class VideoSampler:
         self.graphs = {}
         self.x0_prev = torch.zeros_like(self.state) if self.ms else None
         self.phase = SolverPhase(schedule) if self.ms else None
+        self.rs_factors = self._rs_ws = None
+        if self.guidance_rescale > 0.0:                   # allocated once; the workspace needs no initial contents
+            self.rs_factors = torch.ones(plan.videos, device=dev, dtype=torch.float32)
+            self._rs_ws = ops.vpred_rescale_ws(plan.videos, dev)
 
     def _enqueue(self):
         (xu, tu, eu), (xc, tc, ec) = self.plan.halves
         ops.video_step_prologue(self.state, xu, tu, xc, tc, self.params)
         self.plan.run()
-        if self.ms:
+        if self.guidance_rescale > 0.0:
+            ops.vpred_rescale_factors_dev(eu, ec, self.state.shape[0], self.state[0].numel(), self.params, 6 if self.ms else 5,
+                                          self.guidance_rescale, out=self.rs_factors, ws=self._rs_ws)
+            ops.vpred_step_rs_dev(self.state, eu, ec, self.params, self.rs_factors, x0_prev=self.x0_prev)
+        elif self.ms:
             ops.vpred_step_ms_dev(self.state, eu, ec, self.x0_prev, self.params)
         else:
             ops.vpred_step_dev(self.state, eu, ec, self.params)
@@ -264,6 +294,8 @@ class VideoSampler:
             self._enqueue()
             return
         key = (inject, "ms") if self.ms else inject
+        if self.guidance_rescale > 0.0:
+            key = (key if self.ms else (inject,)) + ("rs",)
         g = self.graphs.get(key)
         if g is None:
             self._enqueue()                               # warm-up outside capture; it has already performed this step
