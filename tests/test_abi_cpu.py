@@ -103,6 +103,92 @@ def test_dev_step_entries_validate_alike():
             assert call(head(mode=3), **dict.fromkeys(extras)) == lib.EINVAL and err().startswith(own + words[extras[0]]), (name, err())
 
 
+def test_video_step_entries_validate_alike():
+    """the eight tmix_vpred_step* entries: every single bad argument's code and message under the entry's own short name, and the order in which a call
+    with two bad arguments is answered.  The wording and the order differ between the entries on purpose (they are the ABI): tmix_vpred_step checks n in
+    front of the dtype, tmix_vpred_step_ms the dtype in front of n, the _rs forms the shape (videos=...) in front of the dtype.  Nothing launches."""
+    import ctypes as C
+    from tweediemix_amd import lib
+    l = lib.load()
+    f = C.c_void_p(0x1000)                      # never dereferenced: validation fails first
+    err = l.tmix_last_error_string
+    PREV, FAC = b"null x0_prev (the history buffer is read and written by every step)", b"null factors"
+    coef = (9.0, 0.5, 0.5)                      # g, sa, s1
+
+    def dense(ms, rs):
+        def call(x=f, v=f, out=f, prev=f, fac=f, dt=lib.F32, n=16, videos=2, per=8):
+            shape = (videos, per) if rs else (n,)
+            tail = (0.8, 0.4, -0.1) if ms else (0.6, 0.4)
+            args = (x, v, out) + ((prev,) if ms else ()) + (dt,) + shape + coef + tail + ((fac,) if rs else ()) + (None,)
+            return getattr(l, "tmix_vpred_step" + ("_ms" if ms else "") + ("_rs" if rs else ""))(*args)
+        return call
+
+    def rows(ms, rs):
+        def call(x=f, vu=f, vc=f, prm=f, prev=f, fac=f, S=2, Cc=4, F=3, hw=5, su=60, sc=60):
+            args = (x, vu, su, vc, sc) + ((prev,) if ms else ()) + (prm, S, Cc, F, hw) + ((fac,) if rs else ()) + (None,)
+            return getattr(l, "tmix_vpred_step" + ("_ms" if ms else "") + ("_rs" if rs else "") + "_dev")(*args)
+        return call
+
+    def answered(name, call, kw, code, text):
+        rc = call(**kw)
+        assert rc == code and err().startswith(name.encode() + b": " + text), (name, kw, rc, err())
+
+    for ms in (False, True):
+        for rs in (False, True):
+            # ---- the dense forms
+            name = "vpred_step" + ("_ms" if ms else "") + ("_rs" if rs else "")
+            call = dense(ms, rs)
+            for ptr in ("x", "v", "out"):
+                answered(name, call, {ptr: None}, lib.EINVAL, b"null pointer")
+            for dt in (7, -1):
+                answered(name, call, dict(dt=dt), lib.EINVAL, b"bad dtype %d" % dt)
+            if rs:
+                answered(name, call, dict(videos=0), lib.ESHAPE, b"videos=0 channels=1 frames=1 hw=8")
+                answered(name, call, dict(per=0), lib.ESHAPE, b"videos=2 channels=1 frames=1 hw=0")
+                answered(name, call, dict(fac=None), lib.EINVAL, FAC)
+                answered(name, call, dict(x=None, fac=None), lib.EINVAL, b"null pointer")
+                answered(name, call, dict(fac=None, videos=0), lib.EINVAL, FAC)                  # factors in front of the shape
+                answered(name, call, dict(fac=None, dt=7), lib.EINVAL, FAC)
+                answered(name, call, dict(dt=7, videos=0), lib.ESHAPE, b"videos=0 channels=1 frames=1 hw=8")     # the shape in front of the dtype
+                answered(name, call, dict(dt=7, per=0), lib.ESHAPE, b"videos=2 channels=1 frames=1 hw=0")
+            else:
+                answered(name, call, dict(n=0), lib.ESHAPE, b"empty latent")
+                if ms:
+                    answered(name, call, dict(dt=7, n=0), lib.EINVAL, b"bad dtype 7")             # the dtype in front of n
+                else:
+                    answered(name, call, dict(dt=7, n=0), lib.ESHAPE, b"empty latent")            # n in front of the dtype
+            if ms:
+                answered(name, call, dict(prev=None), lib.EINVAL, PREV)
+                answered(name, call, dict(v=None, prev=None), lib.EINVAL, b"null pointer")      # the shared pointers in front of x0_prev
+                answered(name, call, dict(prev=None, dt=7), lib.EINVAL, PREV)
+                answered(name, call, dict(prev=None, **(dict(videos=0) if rs else dict(n=0))), lib.EINVAL, PREV)
+            if ms and rs:
+                answered(name, call, dict(prev=None, fac=None), lib.EINVAL, PREV)                # x0_prev in front of factors
+            # ---- the device-parameter forms on plan rows
+            name += "_dev"
+            call = rows(ms, rs)
+            for ptr in ("x", "vu", "vc", "prm"):
+                answered(name, call, {ptr: None}, lib.EINVAL, b"null pointer")
+            for kw, text in ((dict(S=0), b"videos=0 channels=4 frames=3 hw=5"), (dict(Cc=0), b"videos=2 channels=0 frames=3 hw=5"),
+                             (dict(F=0), b"videos=2 channels=4 frames=0 hw=5"), (dict(hw=0), b"videos=2 channels=4 frames=3 hw=0")):
+                answered(name, call, kw, lib.ESHAPE, text)
+                assert b"row_channels" not in err(), (name, err())
+            answered(name, call, dict(su=59), lib.ESHAPE, b"clip strides 59 / 60 < one clip's 60 floats")
+            answered(name, call, dict(sc=59), lib.ESHAPE, b"clip strides 60 / 59 < one clip's 60 floats")
+            answered(name, call, dict(S=0, su=59), lib.ESHAPE, b"videos=0 channels=4 frames=3 hw=5")    # the shape in front of the strides
+            if ms:
+                answered(name, call, dict(prev=None), lib.EINVAL, PREV)
+                answered(name, call, dict(prm=None, prev=None), lib.EINVAL, b"null pointer")
+                answered(name, call, dict(prev=None, F=0), lib.EINVAL, PREV)
+            if rs:
+                answered(name, call, dict(fac=None), lib.EINVAL, FAC)
+                answered(name, call, dict(vc=None, fac=None), lib.EINVAL, b"null pointer")
+                answered(name, call, dict(fac=None, hw=0), lib.EINVAL, FAC)                      # factors in front of the shape
+                answered(name, call, dict(fac=None, sc=59), lib.EINVAL, FAC)
+            if ms and rs:
+                answered(name, call, dict(prev=None, fac=None), lib.EINVAL, PREV)
+
+
 def test_argument_errors_are_reported_before_any_launch():
     """every entry point validates its arguments first and returns a TMIX_E* code with a message (no GPU needed to see that)."""
     import ctypes as C

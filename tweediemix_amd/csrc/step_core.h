@@ -1,8 +1,8 @@
-// step_core.h -- the ONE definition of what the sampler's step kernels share (tweedie_step.hip: the DDIM forms, solver_step.hip: the
-// DPM-Solver++(2M) forms, cfg_rescale.hip: the statistics of the guided prediction).  Device side: element types, the fp16 rounding point, CFG,
-// the blended Tweedie x0 of one element, the v-prediction element of the video sampler.  Host side: the argument checks the *_dev step entries
-// and the video entries share, and the dtype dispatch.  Every file that includes it is compiled with -ffp-contract=off: the kernels that call one
-// function here agree bit for bit because they run the same operations, not because two copies were kept alike.
+// step_core.h -- the ONE definition of what the sampler's step kernels share (tweedie_step.hip: the image sampler's DDIM forms, solver_step.hip: its
+// DPM-Solver++(2M) forms, video_step.hip: the video sampler's step, cfg_rescale.hip: the statistics of the guided prediction).  Device side: element
+// types, the fp16 rounding point, CFG, the blended Tweedie x0 of one element, the v-prediction element of the video sampler and its two moves.  Host
+// side: the argument checks of the *_dev image entries and of the video entries, and the dtype dispatch.  Every file that includes it is compiled with
+// -ffp-contract=off: the kernels that call one function here agree bit for bit because they run the same operations, not because two copies were kept alike.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -93,6 +93,13 @@ template <int DT> __device__ __forceinline__ float vpred_ddim_move(float xv, con
     const float eps = rnd<DT>(rnd<DT>(sa * p.vv) + rnd<DT>(s1 * xv));
     return rnd<DT>(rnd<DT>(sa_n * p.x0) + rnd<DT>(s1_n * eps));
 }
+// the DPM-Solver++(2M) move of that element, x_next = cx x + c0 x0 + c1 x0_prev (no eps term): the history value p is used only when
+// c1 != 0, so a NaN left in an unused history stays out of a first-order step
+template <int DT> __device__ __forceinline__ float vpred_ms_move(float xv, float x0, float p, float cx, float c0, float c1) {
+    float m = rnd<DT>(c0 * x0);
+    if (c1 != 0.0f) m = rnd<DT>(m + rnd<DT>(c1 * p));
+    return rnd<DT>(rnd<DT>(cx * xv) + m);
+}
 // index i of the pipeline-layout state [S][C][F][hw] -> offset of (video s, frame f, channel c, pixel p) in a per-row plan buffer
 // [(clip*F + f)][row_channels][hw] whose clip s starts at s * clip_stride
 __device__ __forceinline__ int64_t video_row_offset(int64_t i, int C, int F, int64_t hw, int row_channels, int64_t clip_stride) {
@@ -147,6 +154,26 @@ inline int check_video_step(const char* me, int videos, int channels, int frames
     const int64_t clip = (int64_t)frames * row_channels * hw;
     if (clip_stride_u < clip || clip_stride_c < clip)
         TMIX_FAIL(TMIX_ESHAPE, "%s: clip strides %lld / %lld < one clip's %lld floats", me, (long long)clip_stride_u, (long long)clip_stride_c, (long long)clip);
+    return TMIX_OK;
+}
+
+// The argument checks of the eight video step entries (tmix_vpred_step[_ms][_rs][_dev]) under the entry's short name `me`.  The codes, the wording
+// and the ORDER of the answers are the entries' ABI and differ between them, so the differences are arguments and stay as they are:
+// required: none of the entry's own pointers (x, v / v_u, v_c, out / params) is null.  need_prev / need_fac: the entry has x0_prev / factors.
+// dtype: the dense forms' element type (the forms on plan rows pass TMIX_F32).  dtype_first: a bad dtype is answered in front of a bad shape
+// (tmix_vpred_step_ms alone).  plain_n: the shape is one count n, passed as hw, and its complaint is "empty latent" (the dense forms without the
+// rescale); otherwise the shape and the clip strides are check_video_step's (the dense _rs forms pass videos x n_per_video as videos x 1 x 1 x hw).
+inline int check_vpred_step(const char* me, bool required, bool need_prev, const void* x0_prev, bool need_fac, const void* factors, int dtype,
+                            bool dtype_first, bool plain_n, int videos, int channels, int frames, int64_t hw, int64_t clip_stride_u, int64_t clip_stride_c) {
+    if (!required) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
+    if (need_prev && !x0_prev) TMIX_FAIL(TMIX_EINVAL, "%s: null x0_prev (the history buffer is read and written by every step)", me);
+    if (need_fac && !factors) TMIX_FAIL(TMIX_EINVAL, "%s: null factors", me);
+    const bool bad_dtype = dtype != TMIX_F32 && dtype != TMIX_F16 && dtype != TMIX_BF16;
+    if (dtype_first && bad_dtype) TMIX_FAIL(TMIX_EINVAL, "%s: bad dtype %d", me, dtype);
+    if (plain_n) {
+        if (hw < 1) TMIX_FAIL(TMIX_ESHAPE, "%s: empty latent", me);
+    } else if (int rc = check_video_step(me, videos, channels, frames, hw, channels, false, clip_stride_u, clip_stride_c)) return rc;
+    if (bad_dtype) TMIX_FAIL(TMIX_EINVAL, "%s: bad dtype %d", me, dtype);
     return TMIX_OK;
 }
 

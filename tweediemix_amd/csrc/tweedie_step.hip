@@ -2,7 +2,8 @@
 // Follows fusion_generation/fusion_sampling.py:376-385,392-403,406-412,424-430,471-472.
 // HBM-bound: per element it reads (rows) eps values + x + K mask values and writes 1-2 floats.
 // Compiled with -ffp-contract=off so fp32 results are bit-identical to the numpy oracle.  The x0 of an element, the fp16 rounding point and the
-// argument checks of the *_dev entries are step_core.h's, shared with solver_step.hip.
+// argument checks of the *_dev entries are step_core.h's, shared with solver_step.hip.  The image sampler's kernels and entries only: the video
+// sampler's step is video_step.hip.
 #include "step_core.h"
 
 namespace {
@@ -95,129 +96,7 @@ step_prologue_kernel(const float* __restrict__ x, float* __restrict__ latent, fl
     if (blockIdx.x == 0 && threadIdx.x < rows) t_dev[sd * rows + threadIdx.x] = prm[0];
 }
 
-// ------------------------------------------------------------------ video sampler (I2VGen-XL loop, config #5); StT<DT>::st: step_core.h
-
-// video_gen/pipeline_i2vgen_xl.py:699-719 in one pass: CFG on the v-prediction, eps / x0 from (x, v), DDIM move (step_core.h: vpred_x0, vpred_ddim_move)
-// RESCALE: the presence of ONE trailing RescaleArgs kernel argument (the pack RsT is empty or {RescaleArgs}, the mechanism of
-// tweedie_step_kernel); element i then uses the factor of its video, fac[i / per], for x0 AND for the move's eps.  Without it the kernel has the
-// arguments it had before.
-template <int DT, typename... RsT>
-__global__ void __launch_bounds__(256)
-vpred_step_kernel(const typename EpsT<DT>::T* __restrict__ x, const typename EpsT<DT>::T* __restrict__ v,
-                  typename EpsT<DT>::T* __restrict__ out, int64_t n, float g, float sa, float s1, float sa_n, float s1_n, RsT... rs) {
-    constexpr bool RS = sizeof...(RsT) != 0;
-    RescaleArgs ra = {};
-    if constexpr (RS) ra = rescale_args(rs...);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float xv = EpsT<DT>::ld(x, i);
-        float f = 1.0f;
-        if constexpr (RS) f = ra.fac[i / ra.per];
-        StT<DT>::st(out, i, vpred_ddim_move<DT>(xv, vpred_x0<DT, RS>(xv, EpsT<DT>::ld(v, i), EpsT<DT>::ld(v, n + i), g, sa, s1, f), sa, s1, sa_n, s1_n));
-    }
-}
-
-// video_gen/utils_attn.py:433-455: frames 1.. of every clip <- first frame (hard) or interp*first + (1-interp)*frame
-template <int DT>
-__global__ void __launch_bounds__(256)
-frame_inject_kernel(typename EpsT<DT>::T* __restrict__ x, int64_t per_frame, int frames, int64_t n, int hard, float a, float b) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t per_clip = (int64_t)(frames - 1) * per_frame;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const int64_t clip = i / per_clip, r = i - clip * per_clip;
-        const int64_t e = r % per_frame, base = clip * frames * per_frame;
-        const float first = EpsT<DT>::ld(x, base + e);
-        const int64_t dst = base + per_frame + r;
-        const float o = hard ? first : rnd<DT>(rnd<DT>(a * first) + rnd<DT>(b * EpsT<DT>::ld(x, dst)));
-        StT<DT>::st(x, dst, o);
-    }
-}
-
-// ------------------------------------------------------------------ batched video step (S videos, both CFG halves); video_row_offset: step_core.h
-
-// head of the captured video step: the state goes into channels [0, C) of the frame rows of both CFG halves' inputs (the image-latent
-// channels [C, row_channels) are not touched) and prm[0] = t into both halves' per-clip timestep inputs
-__global__ void __launch_bounds__(256)
-video_prologue_kernel(const float* __restrict__ x, float* __restrict__ xu, int64_t su, float* __restrict__ tu,
-                      float* __restrict__ xc, int64_t sc, float* __restrict__ tc, const float* __restrict__ prm,
-                      int videos, int C, int F, int64_t hw, int row_channels, int64_t n) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float v = x[i];
-        xu[video_row_offset(i, C, F, hw, row_channels, su)] = v;
-        xc[video_row_offset(i, C, F, hw, row_channels, sc)] = v;
-    }
-    if (blockIdx.x == 0) {
-        const float t = prm[0];
-        for (int k = threadIdx.x; k < videos; k += blockDim.x) { tu[k] = t; tc[k] = t; }
-    }
-}
-
-// vpred_step_kernel<TMIX_F32> for S videos with the coefficients from prm = {t, sa, s1, sa_next, s1_next, g, ...} and v_u / v_c read
-// from the plans' prediction rows [(clip*F + f)][C][hw]; the same two element functions, so the result is that kernel's bit for bit.
-// x is updated in place (element i is read before it is written).  RsT: as in vpred_step_kernel; the video is the outermost index of i.
-template <typename... RsT>
-__global__ void __launch_bounds__(256)
-vpred_step_dev_kernel(float* __restrict__ x, const float* __restrict__ vu, int64_t su, const float* __restrict__ vc, int64_t sc,
-                      const float* __restrict__ prm, int C, int F, int64_t hw, int64_t n, RsT... rs) {
-    constexpr bool RS = sizeof...(RsT) != 0;
-    RescaleArgs ra = {};
-    if constexpr (RS) ra = rescale_args(rs...);
-    const float sa = prm[1], s1 = prm[2], sa_n = prm[3], s1_n = prm[4], g = prm[5];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float xv = x[i];
-        float f = 1.0f;
-        if constexpr (RS) f = ra.fac[i / ra.per];
-        const VPred p = vpred_x0<TMIX_F32, RS>(xv, vu[video_row_offset(i, C, F, hw, C, su)], vc[video_row_offset(i, C, F, hw, C, sc)], g, sa, s1, f);
-        x[i] = vpred_ddim_move<TMIX_F32>(xv, p, sa, s1, sa_n, s1_n);
-    }
-}
-
-template <int DT, typename... RsT>      // RsT: empty, or {RescaleArgs}
-int launch_vpred(const void* x, const void* v, void* out, int64_t n, float g, float sa, float s1, float sa_n, float s1_n, hipStream_t st, RsT... rs) {
-    typedef typename EpsT<DT>::T T;
-    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
-    vpred_step_kernel<DT, RsT...><<<blocks, 256, 0, st>>>((const T*)x, (const T*)v, (T*)out, n, g, sa, s1, sa_n, s1_n, rs...);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
-}
-
-template <typename... RsT>              // the device-parameter form
-int launch_vpred_dev(float* x, const float* vu, int64_t su, const float* vc, int64_t sc, const float* prm, int videos, int C, int F, int64_t hw,
-                     hipStream_t st, RsT... rs) {
-    const int64_t n = (int64_t)videos * C * F * hw;
-    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
-    vpred_step_dev_kernel<RsT...><<<(unsigned)blocks, 256, 0, st>>>(x, vu, su, vc, sc, prm, C, F, hw, n, rs...);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
-}
-
-template <int DT>
-int launch_inject(void* x, int64_t per_frame, int frames, int64_t n, int hard, float a, float b, hipStream_t st) {
-    typedef typename EpsT<DT>::T T;
-    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
-    frame_inject_kernel<DT><<<blocks, 256, 0, st>>>((T*)x, per_frame, frames, n, hard, a, b);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
-}
-
 }  // namespace
-
-extern "C" int tmix_vpred_step(const void* x, const void* v, void* out, int dtype, int64_t n, float g,
-                               float sa, float s1, float sa_next, float s1_next, void* stream) {
-    if (!x || !v || !out) TMIX_FAIL(TMIX_EINVAL, "vpred_step: null pointer");
-    if (n < 1) TMIX_FAIL(TMIX_ESHAPE, "vpred_step: empty latent");
-    return for_dtype(dtype, "vpred_step", "dtype", [&](auto dt) { return launch_vpred<dt()>(x, v, out, n, g, sa, s1, sa_next, s1_next, (hipStream_t)stream); });
-}
-
-extern "C" int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,
-                                 float one_minus_interp, void* stream) {
-    if (!x) TMIX_FAIL(TMIX_EINVAL, "frame_inject: null pointer");
-    if (clips < 1 || frames < 2 || per_frame < 1) TMIX_FAIL(TMIX_ESHAPE, "frame_inject: clips=%d frames=%d per_frame=%lld", clips, frames, (long long)per_frame);
-    const int64_t n = (int64_t)clips * (frames - 1) * per_frame;
-    return for_dtype(dtype, "frame_inject", "dtype", [&](auto dt) { return launch_inject<dt()>(x, per_frame, frames, n, hard, interp, one_minus_interp, (hipStream_t)stream); });
-}
 
 extern "C" int tmix_fused_tweedie_step(const float* x, const void* eps, int eps_dtype, const float* masks,
                                        float* out_x, float* out_x0, int K, int channels, int64_t hw, int mode,
@@ -284,47 +163,4 @@ extern "C" int tmix_step_prologue(const float* x, float* latent, float* t_dev, c
     step_prologue_kernel<<<dim3((unsigned)bx, (unsigned)seeds), 256, 0, (hipStream_t)stream>>>(x, latent, t_dev, params, rows, n);
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
-}
-
-extern "C" int tmix_video_step_prologue(const float* x, float* x_u, int64_t clip_stride_u, float* t_u, float* x_c, int64_t clip_stride_c,
-                                        float* t_c, const float* params, int videos, int channels, int frames, int64_t hw,
-                                        int row_channels, void* stream) {
-    if (!x || !x_u || !t_u || !x_c || !t_c || !params) TMIX_FAIL(TMIX_EINVAL, "video_step_prologue: null pointer");
-    if (int rc = check_video_step("video_step_prologue", videos, channels, frames, hw, row_channels, true, clip_stride_u, clip_stride_c)) return rc;
-    const int64_t n = (int64_t)videos * channels * frames * hw;
-    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
-    video_prologue_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, x_u, clip_stride_u, t_u, x_c, clip_stride_c, t_c, params,
-                                                                             videos, channels, frames, hw, row_channels, n);
-    TMIX_LAUNCH_CHECK();
-    return TMIX_OK;
-}
-
-extern "C" int tmix_vpred_step_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
-                                   const float* params, int videos, int channels, int frames, int64_t hw, void* stream) {
-    if (!x || !v_u || !v_c || !params) TMIX_FAIL(TMIX_EINVAL, "vpred_step_dev: null pointer");
-    if (int rc = check_video_step("vpred_step_dev", videos, channels, frames, hw, channels, false, clip_stride_u, clip_stride_c)) return rc;
-    return launch_vpred_dev(x, v_u, clip_stride_u, v_c, clip_stride_c, params, videos, channels, frames, hw, (hipStream_t)stream);
-}
-
-// tmix_vpred_step / tmix_vpred_step_dev with the guided prediction rescaled per video: factors [videos] from tmix_vpred_rescale_factors
-extern "C" int tmix_vpred_step_rs(const void* x, const void* v, void* out, int dtype, int videos, int64_t n_per_video, float g,
-                                  float sa, float s1, float sa_next, float s1_next, const float* factors, void* stream) {
-    const char* me = "vpred_step_rs";
-    if (!x || !v || !out) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
-    if (!factors) TMIX_FAIL(TMIX_EINVAL, "%s: null factors", me);
-    if (int rc = check_video_step(me, videos, 1, 1, n_per_video, 1, false, n_per_video, n_per_video)) return rc;
-    const RescaleArgs rs = {factors, n_per_video};
-    return for_dtype(dtype, me, "dtype", [&](auto dt) {
-        return launch_vpred<dt()>(x, v, out, (int64_t)videos * n_per_video, g, sa, s1, sa_next, s1_next, (hipStream_t)stream, rs);
-    });
-}
-
-extern "C" int tmix_vpred_step_rs_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
-                                      const float* params, int videos, int channels, int frames, int64_t hw, const float* factors, void* stream) {
-    const char* me = "vpred_step_rs_dev";
-    if (!x || !v_u || !v_c || !params) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
-    if (!factors) TMIX_FAIL(TMIX_EINVAL, "%s: null factors", me);
-    if (int rc = check_video_step(me, videos, channels, frames, hw, channels, false, clip_stride_u, clip_stride_c)) return rc;
-    const RescaleArgs rs = {factors, (int64_t)channels * frames * hw};
-    return launch_vpred_dev(x, v_u, clip_stride_u, v_c, clip_stride_c, params, videos, channels, frames, hw, (hipStream_t)stream, rs);
 }

@@ -1,0 +1,196 @@
+// video_step.hip -- everything the video sampler's step owns (I2VGen-XL loop, video_gen/pipeline_i2vgen_xl.py:699-719): the head of
+// the captured step, the first-frame injection, and ONE element kernel behind the eight tmix_vpred_step[_ms][_rs][_dev] entries -- CFG on the
+// v-prediction, the optional per-video rescale, x0, then the DDIM move or the DPM-Solver++(2M) move, in one HBM pass.
+// The element's operations are step_core.h's (vpred_x0, vpred_ddim_move, vpred_ms_move), so the forms agree bit for bit -- device form with dense form,
+// factors of 1.0 with no rescale, the multistep x0 with the DDIM x0 -- because they are one loop.  Compiled with -ffp-contract=off so fp32 results are
+// bit-identical to the numpy restatements (guidance.vpred_rescaled_step_reference / vpred_rescaled_multistep_reference).
+#include "step_core.h"
+
+namespace {
+
+// the coefficients of one step: g, sa, s1 and the move's -- {sa_next, s1_next} (DDIM; c unused) or {cx, c0, c1} (multistep)
+struct StepCoef { float g, sa, s1, a, b, c; };
+
+// WHERE the operands of element i live: two views with the same four accessors.
+// Dense: x, v [2][n] (uncond rows first, so v_c at n + i) and out of the model dtype, the coefficients by value.  out may alias x in the multistep form
+// (element i of every array is read before it is written), so the view both moves share promises nothing about its pointers.
+template <int D> struct DenseView {
+    static constexpr int DT = D;
+    typedef typename EpsT<D>::T T;
+    const T* x; const T* v; T* out; int64_t n; StepCoef k;
+    template <bool MS> __device__ __forceinline__ StepCoef coef() const { return k; }
+    __device__ __forceinline__ float xv(int64_t i) const { return EpsT<D>::ld(x, i); }
+    __device__ __forceinline__ float vu(int64_t i) const { return EpsT<D>::ld(v, i); }
+    __device__ __forceinline__ float vc(int64_t i) const { return EpsT<D>::ld(v, n + i); }
+    __device__ __forceinline__ void st(int64_t i, float o) const { StT<D>::st(out, i, o); }
+};
+// Plan rows: the fp32 state x [S][C][F][hw] updated in place (element i is read before it is written), v_u / v_c read from the plans' prediction rows
+// [(clip*F + f)][C][hw] with their clip strides, the coefficients from device memory (one captured launch serves every timestep and both orders):
+// prm = {t, sa, s1, sa_next, s1_next, g, 0, 0} for the DDIM move and {t, sa, s1, cx, c0, c1, g, 0} for the multistep move.
+struct RowsView {
+    static constexpr int DT = TMIX_F32;
+    float* x; const float* v_u; int64_t su; const float* v_c; int64_t sc; const float* prm; int C, F; int64_t hw;
+    template <bool MS> __device__ __forceinline__ StepCoef coef() const { return {prm[MS ? 6 : 5], prm[1], prm[2], prm[3], prm[4], MS ? prm[5] : 0.0f}; }
+    __device__ __forceinline__ float xv(int64_t i) const { return x[i]; }
+    __device__ __forceinline__ float vu(int64_t i) const { return v_u[video_row_offset(i, C, F, hw, C, su)]; }
+    __device__ __forceinline__ float vc(int64_t i) const { return v_c[video_row_offset(i, C, F, hw, C, sc)]; }
+    __device__ __forceinline__ void st(int64_t i, float o) const { x[i] = o; }
+};
+
+// MS: the multistep move; x0_prev [n] fp32 is then read and rewritten with this step's x0 (no other argument aliases it), and is not touched otherwise.
+// RS: element i uses the factor of its video, rs.fac[i / rs.per] (the video is the outermost index of i), for x0 AND for the DDIM move's eps; without
+// RS no factor is read and no product is formed, which is what keeps those instantiations' bits the ones they had before the rescale existed.
+template <typename View, bool MS, bool RS>
+__global__ void __launch_bounds__(256)
+video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const RescaleArgs rs) {
+    constexpr int DT = View::DT;
+    const StepCoef k = vw.template coef<MS>();
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float xv = vw.xv(i);
+        float p = 0.0f, f = 1.0f;
+        if constexpr (MS) p = x0_prev[i];
+        if constexpr (RS) f = rs.fac[i / rs.per];
+        const VPred e = vpred_x0<DT, RS>(xv, vw.vu(i), vw.vc(i), k.g, k.sa, k.s1, f);
+        if constexpr (MS) {
+            vw.st(i, vpred_ms_move<DT>(xv, e.x0, p, k.a, k.b, k.c));
+            x0_prev[i] = e.x0;
+        } else vw.st(i, vpred_ddim_move<DT>(xv, e, k.sa, k.s1, k.a, k.b));
+    }
+}
+
+template <bool MS, bool RS, typename View>
+int launch_video_step(const View& vw, float* x0_prev, int64_t n, const RescaleArgs& rs, hipStream_t st) {
+    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    video_step_kernel<View, MS, RS><<<(unsigned)blocks, 256, 0, st>>>(vw, x0_prev, n, rs);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+// the four dense entries: videos x per elements (the forms without the rescale: 1 x n, answered as "empty latent")
+template <bool MS, bool RS>
+int dense_step(const char* me, bool dtype_first, const void* x, const void* v, void* out, float* x0_prev, int dtype, int videos, int64_t per,
+               const StepCoef& k, const float* factors, void* stream) {
+    if (int rc = check_vpred_step(me, x && v && out, MS, x0_prev, RS, factors, dtype, dtype_first, !RS, videos, 1, 1, per, per, per)) return rc;
+    const int64_t n = (int64_t)videos * per;
+    return for_dtype(dtype, me, "dtype", [&](auto dt) {
+        typedef typename EpsT<dt()>::T T;
+        return launch_video_step<MS, RS>(DenseView<dt()>{(const T*)x, (const T*)v, (T*)out, n, k}, x0_prev, n, RescaleArgs{factors, per}, (hipStream_t)stream);
+    });
+}
+
+// the four entries on plan rows
+template <bool MS, bool RS>
+int rows_step(const char* me, float* x, const float* v_u, int64_t su, const float* v_c, int64_t sc, float* x0_prev, const float* prm, int videos, int C,
+              int F, int64_t hw, const float* factors, void* stream) {
+    if (int rc = check_vpred_step(me, x && v_u && v_c && prm, MS, x0_prev, RS, factors, TMIX_F32, false, false, videos, C, F, hw, su, sc)) return rc;
+    const int64_t per = (int64_t)C * F * hw;
+    return launch_video_step<MS, RS>(RowsView{x, v_u, su, v_c, sc, prm, C, F, hw}, x0_prev, videos * per, RescaleArgs{factors, per}, (hipStream_t)stream);
+}
+
+// head of the captured video step: the state goes into channels [0, C) of the frame rows of both CFG halves' inputs (the image-latent
+// channels [C, row_channels) are not touched) and prm[0] = t into both halves' per-clip timestep inputs
+__global__ void __launch_bounds__(256)
+video_prologue_kernel(const float* __restrict__ x, float* __restrict__ xu, int64_t su, float* __restrict__ tu,
+                      float* __restrict__ xc, int64_t sc, float* __restrict__ tc, const float* __restrict__ prm,
+                      int videos, int C, int F, int64_t hw, int row_channels, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float v = x[i];
+        xu[video_row_offset(i, C, F, hw, row_channels, su)] = v;
+        xc[video_row_offset(i, C, F, hw, row_channels, sc)] = v;
+    }
+    if (blockIdx.x == 0) {
+        const float t = prm[0];
+        for (int k = threadIdx.x; k < videos; k += blockDim.x) { tu[k] = t; tc[k] = t; }
+    }
+}
+
+// video_gen/utils_attn.py:433-455: frames 1.. of every clip <- first frame (hard) or interp*first + (1-interp)*frame
+template <int DT>
+__global__ void __launch_bounds__(256)
+frame_inject_kernel(typename EpsT<DT>::T* __restrict__ x, int64_t per_frame, int frames, int64_t n, int hard, float a, float b) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t per_clip = (int64_t)(frames - 1) * per_frame;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t clip = i / per_clip, r = i - clip * per_clip;
+        const int64_t e = r % per_frame, base = clip * frames * per_frame;
+        const float first = EpsT<DT>::ld(x, base + e);
+        const int64_t dst = base + per_frame + r;
+        const float o = hard ? first : rnd<DT>(rnd<DT>(a * first) + rnd<DT>(b * EpsT<DT>::ld(x, dst)));
+        StT<DT>::st(x, dst, o);
+    }
+}
+
+template <int DT>
+int launch_inject(void* x, int64_t per_frame, int frames, int64_t n, int hard, float a, float b, hipStream_t st) {
+    typedef typename EpsT<DT>::T T;
+    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    frame_inject_kernel<DT><<<blocks, 256, 0, st>>>((T*)x, per_frame, frames, n, hard, a, b);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+}  // namespace
+
+extern "C" int tmix_video_step_prologue(const float* x, float* x_u, int64_t clip_stride_u, float* t_u, float* x_c, int64_t clip_stride_c,
+                                        float* t_c, const float* params, int videos, int channels, int frames, int64_t hw,
+                                        int row_channels, void* stream) {
+    if (!x || !x_u || !t_u || !x_c || !t_c || !params) TMIX_FAIL(TMIX_EINVAL, "video_step_prologue: null pointer");
+    if (int rc = check_video_step("video_step_prologue", videos, channels, frames, hw, row_channels, true, clip_stride_u, clip_stride_c)) return rc;
+    const int64_t n = (int64_t)videos * channels * frames * hw;
+    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    video_prologue_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, x_u, clip_stride_u, t_u, x_c, clip_stride_c, t_c, params,
+                                                                             videos, channels, frames, hw, row_channels, n);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+extern "C" int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,
+                                 float one_minus_interp, void* stream) {
+    if (!x) TMIX_FAIL(TMIX_EINVAL, "frame_inject: null pointer");
+    if (clips < 1 || frames < 2 || per_frame < 1) TMIX_FAIL(TMIX_ESHAPE, "frame_inject: clips=%d frames=%d per_frame=%lld", clips, frames, (long long)per_frame);
+    const int64_t n = (int64_t)clips * (frames - 1) * per_frame;
+    return for_dtype(dtype, "frame_inject", "dtype", [&](auto dt) { return launch_inject<dt()>(x, per_frame, frames, n, hard, interp, one_minus_interp, (hipStream_t)stream); });
+}
+
+// ---- the eight step entries: [_ms] the multistep move with the history buffer, [_rs] factors [videos] from tmix_vpred_rescale_factors, [_dev] on plan rows
+extern "C" int tmix_vpred_step(const void* x, const void* v, void* out, int dtype, int64_t n, float g,
+                               float sa, float s1, float sa_next, float s1_next, void* stream) {
+    return dense_step<false, false>("vpred_step", false, x, v, out, nullptr, dtype, 1, n, {g, sa, s1, sa_next, s1_next, 0.0f}, nullptr, stream);
+}
+
+extern "C" int tmix_vpred_step_ms(const void* x, const void* v, void* out, float* x0_prev, int dtype, int64_t n, float g,
+                                  float sa, float s1, float cx, float c0, float c1, void* stream) {
+    return dense_step<true, false>("vpred_step_ms", true, x, v, out, x0_prev, dtype, 1, n, {g, sa, s1, cx, c0, c1}, nullptr, stream);
+}
+
+extern "C" int tmix_vpred_step_rs(const void* x, const void* v, void* out, int dtype, int videos, int64_t n_per_video, float g,
+                                  float sa, float s1, float sa_next, float s1_next, const float* factors, void* stream) {
+    return dense_step<false, true>("vpred_step_rs", false, x, v, out, nullptr, dtype, videos, n_per_video, {g, sa, s1, sa_next, s1_next, 0.0f}, factors, stream);
+}
+
+extern "C" int tmix_vpred_step_ms_rs(const void* x, const void* v, void* out, float* x0_prev, int dtype, int videos, int64_t n_per_video, float g,
+                                     float sa, float s1, float cx, float c0, float c1, const float* factors, void* stream) {
+    return dense_step<true, true>("vpred_step_ms_rs", false, x, v, out, x0_prev, dtype, videos, n_per_video, {g, sa, s1, cx, c0, c1}, factors, stream);
+}
+
+extern "C" int tmix_vpred_step_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
+                                   const float* params, int videos, int channels, int frames, int64_t hw, void* stream) {
+    return rows_step<false, false>("vpred_step_dev", x, v_u, clip_stride_u, v_c, clip_stride_c, nullptr, params, videos, channels, frames, hw, nullptr, stream);
+}
+
+extern "C" int tmix_vpred_step_ms_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
+                                      const float* params, int videos, int channels, int frames, int64_t hw, void* stream) {
+    return rows_step<true, false>("vpred_step_ms_dev", x, v_u, clip_stride_u, v_c, clip_stride_c, x0_prev, params, videos, channels, frames, hw, nullptr, stream);
+}
+
+extern "C" int tmix_vpred_step_rs_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
+                                      const float* params, int videos, int channels, int frames, int64_t hw, const float* factors, void* stream) {
+    return rows_step<false, true>("vpred_step_rs_dev", x, v_u, clip_stride_u, v_c, clip_stride_c, nullptr, params, videos, channels, frames, hw, factors, stream);
+}
+
+extern "C" int tmix_vpred_step_ms_rs_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
+                                         const float* params, int videos, int channels, int frames, int64_t hw, const float* factors, void* stream) {
+    return rows_step<true, true>("vpred_step_ms_rs_dev", x, v_u, clip_stride_u, v_c, clip_stride_c, x0_prev, params, videos, channels, frames, hw, factors, stream);
+}

@@ -839,15 +839,57 @@ def softmax_rows_causal(scores, probs, seq, scale):
 def vpred_step(x, v, g, at, at_next, out=None):
     """I2VGen-XL loop update (video_gen/pipeline_i2vgen_xl.py:699-719): x [B,...], v [2B,...] (uncond rows first) of one
     dtype; at / at_next from the un-shifted alpha table.  Returns the next latents (same dtype)."""
-    _need_cuda(x, v)
+    return _vpred_dense(x, v, g, at, step_coeffs(at, at_next)[2:], None, None, out)
+
+
+def _history(x0_prev, x):
+    assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
+    return _p(x0_prev)
+
+
+def _video_factors(factors, videos):
+    assert factors.is_cuda and factors.dtype == torch.float32 and factors.is_contiguous() and factors.numel() == videos, (tuple(factors.shape), videos)
+    return _p(factors)
+
+
+def _vpred_dense(x, v, g, at, move, x0_prev, factors, out):
+    """the four dense video step entries: x0_prev None -> the DDIM move, move = (sa_next, s1_next), else the multistep move, move = (cx, c0, c1) and
+    tmix_vpred_step_ms*; factors [B] -> the _rs form.  (sa, s1) are formed from `at` in fp32 as step_coeffs forms them."""
+    _need_cuda(x, v, x0_prev)
     assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
     out = torch.empty_like(x) if out is None else out
-    f = np.float32
-    sa, s1 = np.sqrt(f(at)), np.sqrt(f(1) - f(at))
-    san, s1n = np.sqrt(f(at_next)), np.sqrt(f(1) - f(at_next))
-    L.check(L.load().tmix_vpred_step(_p(x), _p(v), _p(out), _EPS_DT[x.dtype], x.numel(), float(g), float(sa), float(s1),
-                                     float(san), float(s1n), _stream()), "tmix_vpred_step")
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    sa, s1 = step_coeffs(at, at)[:2]
+    B = x.shape[0]
+    name = "tmix_vpred_step" + ("" if x0_prev is None else "_ms") + ("" if factors is None else "_rs")
+    prev = () if x0_prev is None else (_history(x0_prev, x),)
+    shape, fac = ((x.numel(),), ()) if factors is None else ((B, x.numel() // B), (_video_factors(factors, B),))
+    L.check(getattr(L.load(), name)(_p(x), _p(v), _p(out), *prev, _EPS_DT[x.dtype], *shape, float(g), sa, s1, *(float(c) for c in move), *fac, _stream()), name)
     return out
+
+
+def _plan_rows(x, u, c, R, clip_stride_u, clip_stride_c):
+    """head of the entries on plan rows: x [S,C,F,h,w] fp32 contiguous, u / c the CFG halves' frame rows [(S*F), R, h, w] fp32 with clip s at
+    s * clip_stride floats (default: one contiguous clip) -> (S, C, F, h * w, stride_u, stride_c)"""
+    assert x.dtype == u.dtype == c.dtype == torch.float32 and x.is_contiguous()
+    S, Cc, Fr, h, w = x.shape
+    clip = Fr * R * h * w
+    su, sc = clip_stride_u or clip, clip_stride_c or clip
+    for buf, st in ((u, su), (c, sc)):                          # the kernels reach clip S-1's last frame row
+        assert buf.is_contiguous() and buf.numel() >= (S - 1) * st + clip
+    return S, Cc, Fr, h * w, su, sc
+
+
+def _vpred_rows(x, v_u, v_c, params, x0_prev, factors, clip_stride_u, clip_stride_c):
+    """the four video step entries on plan rows, in place on x: x0_prev -> tmix_vpred_step_ms*_dev, factors [S] -> the _rs form"""
+    _need_cuda(x, v_u, v_c, params, x0_prev)
+    S, Cc, Fr, hw, su, sc = _plan_rows(x, v_u, v_c, x.shape[1], clip_stride_u, clip_stride_c)
+    assert params.numel() >= (6 if x0_prev is None and factors is None else 8)
+    name = "tmix_vpred_step" + ("" if x0_prev is None else "_ms") + ("" if factors is None else "_rs") + "_dev"
+    prev = () if x0_prev is None else (_history(x0_prev, x),)
+    fac = () if factors is None else (_video_factors(factors, S),)
+    L.check(getattr(L.load(), name)(_p(x), _p(v_u), su, _p(v_c), sc, *prev, _p(params), S, Cc, Fr, hw, *fac, _stream()), name)
+    return x
 
 
 def video_step_prologue(x, x_u, t_u, x_c, t_c, params, clip_stride_u=None, clip_stride_c=None):
@@ -855,86 +897,51 @@ def video_step_prologue(x, x_u, t_u, x_c, t_c, params, clip_stride_u=None, clip_
     x_u / x_c (frame rows [(S*F), R, h, w], R >= C, clip s at s * clip_stride floats: default one contiguous clip), and
     params[0] -> t_u / t_c [S].  Channels [C, R) are not written."""
     _need_cuda(x, x_u, t_u, x_c, t_c, params)
-    assert x.dtype == torch.float32 and x.is_contiguous() and x_u.dtype == x_c.dtype == torch.float32
-    S, Cc, Fr, h, w = x.shape
     R = x_u.shape[1]
-    su = clip_stride_u or Fr * R * h * w
-    sc = clip_stride_c or Fr * R * h * w
-    for buf, st, tt in ((x_u, su, t_u), (x_c, sc, t_c)):        # the kernel writes up to clip S-1's last frame row and S timesteps
-        assert buf.is_contiguous() and buf.shape[1] == R and buf.numel() >= (S - 1) * st + Fr * R * h * w and tt.numel() >= S
-    L.check(L.load().tmix_video_step_prologue(_p(x), _p(x_u), su, _p(t_u), _p(x_c), sc, _p(t_c), _p(params), S, Cc, Fr, h * w, R,
+    S, Cc, Fr, hw, su, sc = _plan_rows(x, x_u, x_c, R, clip_stride_u, clip_stride_c)
+    assert x_u.shape[1] == x_c.shape[1] == R and t_u.numel() >= S and t_c.numel() >= S        # the kernel writes S timesteps into each half's input
+    L.check(L.load().tmix_video_step_prologue(_p(x), _p(x_u), su, _p(t_u), _p(x_c), sc, _p(t_c), _p(params), S, Cc, Fr, hw, R,
                                               _stream()), "tmix_video_step_prologue")
 
 
 def vpred_step_dev(x, v_u, v_c, params, clip_stride_u=None, clip_stride_c=None):
     """vpred_step for S videos in place on x [S,C,F,h,w] fp32, the CFG halves' predictions read from the plans' frame rows
     v_u / v_c [(S*F), C, h, w] (clip s at s * clip_stride floats) and the coefficients from params {t, sa, s1, sa', s1', g}."""
-    _need_cuda(x, v_u, v_c, params)
-    assert x.dtype == v_u.dtype == v_c.dtype == torch.float32 and x.is_contiguous()
-    S, Cc, Fr, h, w = x.shape
-    su = clip_stride_u or Fr * Cc * h * w
-    sc = clip_stride_c or Fr * Cc * h * w
-    for buf, st in ((v_u, su), (v_c, sc)):
-        assert buf.is_contiguous() and buf.numel() >= (S - 1) * st + Fr * Cc * h * w
-    L.check(L.load().tmix_vpred_step_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(params), S, Cc, Fr, h * w, _stream()),
-            "tmix_vpred_step_dev")
-    return x
+    return _vpred_rows(x, v_u, v_c, params, None, None, clip_stride_u, clip_stride_c)
 
 
-def video_step_params(t, g, at, at_next, out=None):
-    """the 8 floats {t, sa, s1, sa_next, s1_next, g, 0, 0} the batched video step reads (coefficients as vpred_step computes them)."""
-    f = np.float32
-    vals = [float(t), float(np.sqrt(f(at))), float(np.sqrt(f(1) - f(at))), float(np.sqrt(f(at_next))), float(np.sqrt(f(1) - f(at_next))),
-            float(g), 0.0, 0.0]
+def _fill_params(vals, out):
     if out is None:
         return torch.tensor(vals, dtype=torch.float32)
     for i, v in enumerate(vals):
         out[i] = v
     return out
+
+
+def video_step_params(t, g, at, at_next, out=None):
+    """the 8 floats {t, sa, s1, sa_next, s1_next, g, 0, 0} the batched video step reads (coefficients as vpred_step computes them)."""
+    return _fill_params([float(t), *step_coeffs(at, at_next), float(g), 0.0, 0.0], out)
 
 
 def vpred_step_ms(x, v, g, at, coeffs, x0_prev, out=None):
     """DPM-Solver++(2M) form of vpred_step (tmix_vpred_step_ms): x [B,...], v [2B,...] of one dtype, x0_prev fp32 of x's shape
     (read and rewritten with this step's x0); at from the un-shifted alpha table (sa, s1 formed as vpred_step forms them), coeffs = (cx, c0, c1)
     from solver.video_multistep_coeffs.  out may be x.  Returns the next latents (same dtype)."""
-    _need_cuda(x, v, x0_prev)
-    sa, s1 = np.sqrt(np.float32(at)), np.sqrt(np.float32(1) - np.float32(at))
-    cx, c0, c1 = coeffs
-    assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
-    assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
-    out = torch.empty_like(x) if out is None else out
-    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
-    L.check(L.load().tmix_vpred_step_ms(_p(x), _p(v), _p(out), _p(x0_prev), _EPS_DT[x.dtype], x.numel(), float(g), float(sa), float(s1),
-                                        float(cx), float(c0), float(c1), _stream()), "tmix_vpred_step_ms")
-    return out
+    assert x0_prev is not None
+    return _vpred_dense(x, v, g, at, coeffs, x0_prev, None, out)
 
 
 def vpred_step_ms_dev(x, v_u, v_c, x0_prev, params, clip_stride_u=None, clip_stride_c=None):
     """vpred_step_ms for S videos in place on x [S,C,F,h,w] fp32 (x0_prev: the same shape), the CFG halves' predictions read from the plans'
     frame rows as in vpred_step_dev and the coefficients from params {t, sa, s1, cx, c0, c1, g, 0} (video_step_params_ms)."""
-    _need_cuda(x, v_u, v_c, x0_prev, params)
-    assert x.dtype == v_u.dtype == v_c.dtype == x0_prev.dtype == torch.float32 and x.is_contiguous()
-    assert x0_prev.is_contiguous() and x0_prev.numel() == x.numel() and params.numel() >= 8
-    S, Cc, Fr, h, w = x.shape
-    su = clip_stride_u or Fr * Cc * h * w
-    sc = clip_stride_c or Fr * Cc * h * w
-    for buf, st in ((v_u, su), (v_c, sc)):
-        assert buf.is_contiguous() and buf.numel() >= (S - 1) * st + Fr * Cc * h * w
-    L.check(L.load().tmix_vpred_step_ms_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(x0_prev), _p(params), S, Cc, Fr, h * w, _stream()),
-            "tmix_vpred_step_ms_dev")
-    return x
+    assert x0_prev is not None
+    return _vpred_rows(x, v_u, v_c, params, x0_prev, None, clip_stride_u, clip_stride_c)
 
 
 def video_step_params_ms(t, g, at, coeffs, out=None):
     """the 8 floats {t, sa, s1, cx, c0, c1, g, 0} the batched solver step reads: sa, s1 as vpred_step computes them, coeffs = (cx, c0, c1)."""
-    f = np.float32
     cx, c0, c1 = coeffs
-    vals = [float(t), float(np.sqrt(f(at))), float(np.sqrt(f(1) - f(at))), float(f(cx)), float(f(c0)), float(f(c1)), float(g), 0.0]
-    if out is None:
-        return torch.tensor(vals, dtype=torch.float32)
-    for i, v in enumerate(vals):
-        out[i] = v
-    return out
+    return _fill_params([float(t), *step_coeffs(at, at)[:2], *(float(np.float32(c)) for c in (cx, c0, c1)), float(g), 0.0], out)
 
 
 def vpred_rescale_ws(videos, device):
@@ -975,58 +982,23 @@ def vpred_rescale_factors_dev(v_u, v_c, videos, n_per_video, params, g_slot, phi
                           out, ws)
 
 
-def _video_factors(factors, videos):
-    assert factors.is_cuda and factors.dtype == torch.float32 and factors.is_contiguous() and factors.numel() == videos, (tuple(factors.shape), videos)
-    return _p(factors)
-
-
 def vpred_step_rs(x, v, g, at, at_next, factors, out=None):
     """vpred_step with the guided prediction of video b scaled by factors[b] (tmix_vpred_step_rs): x [B,...], v [2B,...]."""
-    _need_cuda(x, v)
-    assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
-    out = torch.empty_like(x) if out is None else out
-    B = x.shape[0]
-    f = np.float32
-    sa, s1 = np.sqrt(f(at)), np.sqrt(f(1) - f(at))
-    san, s1n = np.sqrt(f(at_next)), np.sqrt(f(1) - f(at_next))
-    L.check(L.load().tmix_vpred_step_rs(_p(x), _p(v), _p(out), _EPS_DT[x.dtype], B, x.numel() // B, float(g), float(sa), float(s1),
-                                        float(san), float(s1n), _video_factors(factors, B), _stream()), "tmix_vpred_step_rs")
-    return out
+    assert factors is not None
+    return _vpred_dense(x, v, g, at, step_coeffs(at, at_next)[2:], None, factors, out)
 
 
 def vpred_step_ms_rs(x, v, g, at, coeffs, x0_prev, factors, out=None):
     """vpred_step_ms with the guided prediction of video b scaled by factors[b] (tmix_vpred_step_ms_rs)."""
-    _need_cuda(x, v, x0_prev)
-    sa, s1 = np.sqrt(np.float32(at)), np.sqrt(np.float32(1) - np.float32(at))
-    cx, c0, c1 = coeffs
-    assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
-    assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
-    out = torch.empty_like(x) if out is None else out
-    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
-    B = x.shape[0]
-    L.check(L.load().tmix_vpred_step_ms_rs(_p(x), _p(v), _p(out), _p(x0_prev), _EPS_DT[x.dtype], B, x.numel() // B, float(g), float(sa), float(s1),
-                                           float(cx), float(c0), float(c1), _video_factors(factors, B), _stream()), "tmix_vpred_step_ms_rs")
-    return out
+    assert x0_prev is not None and factors is not None
+    return _vpred_dense(x, v, g, at, coeffs, x0_prev, factors, out)
 
 
 def vpred_step_rs_dev(x, v_u, v_c, params, factors, x0_prev=None, clip_stride_u=None, clip_stride_c=None):
     """tmix_vpred_step_rs_dev, or with x0_prev (the history buffer) tmix_vpred_step_ms_rs_dev: the arguments of vpred_step_dev / vpred_step_ms_dev
     plus factors [S] fp32 (vpred_rescale_factors_dev).  In place on x [S,C,F,h,w] fp32; returns x."""
-    _need_cuda(x, v_u, v_c, params, x0_prev)
-    assert x.dtype == v_u.dtype == v_c.dtype == torch.float32 and x.is_contiguous() and params.numel() >= 8
-    S, Cc, Fr, h, w = x.shape
-    su = clip_stride_u or Fr * Cc * h * w
-    sc = clip_stride_c or Fr * Cc * h * w
-    for buf, st in ((v_u, su), (v_c, sc)):
-        assert buf.is_contiguous() and buf.numel() >= (S - 1) * st + Fr * Cc * h * w
-    fp = _video_factors(factors, S)
-    if x0_prev is None:
-        L.check(L.load().tmix_vpred_step_rs_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(params), S, Cc, Fr, h * w, fp, _stream()), "tmix_vpred_step_rs_dev")
-    else:
-        assert x0_prev.dtype == torch.float32 and x0_prev.is_contiguous() and x0_prev.numel() == x.numel()
-        L.check(L.load().tmix_vpred_step_ms_rs_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(x0_prev), _p(params), S, Cc, Fr, h * w, fp, _stream()),
-                "tmix_vpred_step_ms_rs_dev")
-    return x
+    assert factors is not None
+    return _vpred_rows(x, v_u, v_c, params, x0_prev, factors, clip_stride_u, clip_stride_c)
 
 
 def frame_inject(x, clips, frames, interp=None):

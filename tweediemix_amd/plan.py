@@ -37,6 +37,27 @@ def hint_bytes(nbytes, cap, over):
     return min(nbytes, cap) if cap and nbytes > over else nbytes
 
 
+class ParamRing:
+    """Pinned staging ring for a step's eight parameter floats (image and video sampler).  The host runs ahead of the device by whole steps: next()
+    hands out a slot once the copy that last read it has completed, upload(dst) copies it asynchronously and records.  cuda=False: pageable, no events."""
+
+    def __init__(self, cuda=True, slots=64):
+        z = torch.zeros(slots, 8, dtype=torch.float32)
+        self.slots, self.events, self.i, self.cuda = (z.pin_memory() if cuda else z), [None] * slots, -1, cuda
+
+    def next(self):
+        self.i = (self.i + 1) % len(self.events)
+        if self.events[self.i] is not None:
+            self.events[self.i].synchronize()
+        return self.slots[self.i]
+
+    def upload(self, dst):
+        dst.copy_(self.slots[self.i], non_blocking=True)
+        if self.cuda:
+            self.events[self.i] = torch.cuda.Event()
+            self.events[self.i].record()
+
+
 class Arena:
     """Size-keyed free list: the plan is a static, stream-ordered launch sequence, so a buffer released
     at plan position i can be handed to any op planned after i."""

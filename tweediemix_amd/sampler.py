@@ -35,6 +35,7 @@ from . import lib as L
 from . import ops
 from .schedule import Schedule
 from .guidance import validate_phi
+from .plan import ParamRing
 from .solver import SOLVERS, multistep_coeffs
 from .unet import KVCache, PlanGroup, TokenMapSpec, TokenPropSpec, UNetPlan, UNetWeights
 
@@ -224,13 +225,7 @@ class Tweediemix:
             self._rs_factors = torch.ones(S * (self._rs_rows - 1), device=self.device, dtype=F32)
             self._rs_ws = ops.cfg_rescale_ws(self._rs_rows, S, self.device)
         self._keep = self._keep_bufs = None    # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
-        # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it
-        # has completed (the host runs ahead of the device by whole steps)
-        self._hp = torch.zeros(64, 8, dtype=F32)
-        if self.device.type == "cuda":
-            self._hp = self._hp.pin_memory()
-        self._hp_ev = [None] * self._hp.shape[0]
-        self._hp_i = 0
+        self._ring = ParamRing(cuda=self.device.type == "cuda")     # staging for the asynchronous upload of step_params
         self._mask_buf = None            # fixed-address copy of self.masks that the captured fusion step reads
 
     # ------------------------------------------------------------------ wide canvas
@@ -465,21 +460,9 @@ class Tweediemix:
         if "_unet" not in vars(self):
             self.unet_calls.append((kind, self.plan(kind).B // self.n_seeds, int(t)))
         sa, s1, san, s1n = ops.step_coeffs(at, at_next)
-        i = self._hp_i
-        self._hp_i = (i + 1) % self._hp.shape[0]
-        if self._hp_ev[i] is not None:
-            self._hp_ev[i].synchronize()
-        hp = self._hp[i]
-        if ms is None:
-            hp[0], hp[1], hp[2], hp[3], hp[4] = float(t), sa, s1, san, s1n
-            hp[5], hp[6] = (1.0 if is_last else 0.0), float(self.config.guidance_scale)
-        else:
-            hp[0], hp[1], hp[2], hp[3], hp[4], hp[5] = float(t), sa, s1, ms[0], ms[1], ms[2]
-            hp[6], hp[7] = (1.0 if is_last else 0.0), float(self.config.guidance_scale)
-        self.step_params.copy_(hp, non_blocking=True)
-        if self.device.type == "cuda":
-            self._hp_ev[i] = torch.cuda.Event()
-            self._hp_ev[i].record()
+        move =(san, s1n) if ms is None else (ms[0], ms[1], ms[2])        # 7 floats, or 8 for a multistep step: the layouts the step kernels read
+        ops._fill_params([float(t), sa, s1, *move, 1.0 if is_last else 0.0, float(self.config.guidance_scale)], self._ring.next())
+        self._ring.upload(self.step_params)
         if mode == L.STEP_FUSION:
             assert self._mask_buf is not None, "fusion step before the masks were acquired"
         if "_unet" in vars(self):

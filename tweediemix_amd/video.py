@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .plan import ParamRing
 
 
 SPACINGS = ("leading", "logsnr")
@@ -241,11 +242,7 @@ class VideoSampler:
         dev = plan.plans[0].dev
         self.state = torch.zeros(plan.videos, cfg.in_channels, plan.frames, plan.h, plan.w, device=dev, dtype=torch.float32)
         self.params = torch.zeros(8, device=dev, dtype=torch.float32)           # {t, sa, s1, sa_next, s1_next, g, -, -}; solver: {t, sa, s1, cx, c0, c1, g, -}
-        # pinned staging ring for the asynchronous parameter upload: a slot is rewritten only after the copy that read it has
-        # completed (as the image sampler's step_params)
-        self._hp = torch.zeros(64, 8, dtype=torch.float32).pin_memory()
-        self._hp_ev = [None] * self._hp.shape[0]
-        self._hp_i = 0
+        self._ring = ParamRing()                          # staging for the asynchronous parameter upload (as the image sampler's step_params)
         self.graphs = {}
         self.x0_prev = torch.zeros_like(self.state) if self.ms else None
         self.phase = SolverPhase(schedule) if self.ms else None
@@ -270,18 +267,12 @@ class VideoSampler:
     def _upload(self, t):
         sch = self.schedule
         coeffs = self.phase.coeffs(t) if self.ms else None          # first: a refused step rewrites no staging slot
-        i = self._hp_i
-        self._hp_i = (i + 1) % self._hp.shape[0]
-        if self._hp_ev[i] is not None:
-            self._hp_ev[i].synchronize()
-        hp = self._hp[i]
+        hp = self._ring.next()
         if self.ms:
             ops.video_step_params_ms(t, self.g, sch.alpha(int(t)), coeffs, out=hp)
         else:
             ops.video_step_params(t, self.g, sch.alpha(int(t)), sch.next_alpha(int(t)), out=hp)
-        self.params.copy_(hp, non_blocking=True)
-        self._hp_ev[i] = torch.cuda.Event()
-        self._hp_ev[i].record()
+        self._ring.upload(self.params)
 
     def step(self, t):
         inject = False
