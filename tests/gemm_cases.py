@@ -257,15 +257,26 @@ def exact_conv(B, H, W, Cin, Cout, mode, seed, bias=True, temb=True, residual=Tr
     return c
 
 
-def exact_conv_in(B, Cin, H, W, Cout, seed):
-    """conv_in: x fp32 NCHW, w fp32 OHWI, bias fp32, bf16 NHWC output.  fp32 operands: the same integers, a bias in the hundreds carries the sums across 256"""
-    what = f"exact_conv_in {(B, Cin, H, W, Cout)}"
+def exact_conv_in(B, Cin, H, W, Cout, seed, pre=False):
+    """conv_in: x fp32 NCHW, w fp32 OHWI, bias fp32, bf16 NHWC output.  fp32 operands: the same integers, a bias in the hundreds carries the sums across 256.
+    pre (tmix_conv_in_pre, Cin = 4): an integer 4 x 4 map pre_w in [-2, 2] and a non-zero integer pre_b in +-[1, 3] applied to every pixel of x BEFORE the zero
+    padding -- a bias that leaks into the border changes integers --; S then sums |pre_b| + |pre_w| |x| through |w|, which bounds every partial sum of the map's
+    own chain too"""
+    what = f"exact_conv_in {(B, Cin, H, W, Cout)}{' pre' if pre else ''}"
     x = ints((B, H, W, Cin), seed, 0.8)
     w = ints((Cout, 3, 3, Cin), seed + 1, 0.8) * signs(Cout, seed + 2).view(Cout, 1, 1, 1)
     b = int_rows((Cout,), seed + 5, 600)
-    ref, S = conv_product(x, w, S1) + b, conv_product(x.abs(), w.abs(), S1) + b.abs()
+    c, u, ua = {}, x, x.abs()
+    if pre:
+        assert Cin == 4
+        pw = int_rows((4, 4), seed + 6, 2)
+        pb = int_rows((4,), seed + 7, 3)
+        pb = torch.where(pb == 0, signs(4, seed + 8), pb)                      # (no channel without a bias)
+        u, ua = x @ pw.T + pb, x.abs() @ pw.abs().T + pb.abs()
+        c = dict(pre_w=pw.float(), pre_b=pb.float())
+    ref, S = conv_product(u, w, S1) + b, conv_product(ua, w.abs(), S1) + b.abs()
     e, _ = expected(ref, S, torch.ones_like(ref), what)
-    return dict(x=x.permute(0, 3, 1, 2).contiguous().float(), w=w.float(), bias=b.float(), ref=ref, exp_bf16=e)
+    return dict(c, x=x.permute(0, 3, 1, 2).contiguous().float(), w=w.float(), bias=b.float(), ref=ref, exp_bf16=e)
 
 
 def exact_conv_out(B, H, W, Cin, Cout, seed):

@@ -552,8 +552,9 @@ def conv3x3(x, w, bias=None, batch_bias=None, residual=None, mode=L.CONV_S1, out
     return out
 
 
-def conv_in(x_nchw, w_ohwi, bias, out=None):
-    """fp32 NCHW [B,Cin,H,W] -> bf16 NHWC [B,H,W,Cout]; w fp32 [Cout,3,3,Cin]."""
+def conv_in(x_nchw, w_ohwi, bias, out=None, pre_w=None, pre_b=None):
+    """fp32 NCHW [B,Cin,H,W] -> bf16 NHWC [B,H,W,Cout]; w fp32 [Cout,3,3,Cin].  pre_w [4,4] (and pre_b [4]), HOST values: tmix_conv_in_pre, the
+    per-pixel linear map of a 4-channel latent in front of the convolution (the padding stays zero)."""
     _need_cuda(x_nchw, w_ohwi)
     lib = L.load()
     B, Cin, H, W = x_nchw.shape
@@ -561,7 +562,14 @@ def conv_in(x_nchw, w_ohwi, bias, out=None):
     assert x_nchw.dtype == torch.float32 and w_ohwi.dtype == torch.float32 and x_nchw.is_contiguous() and w_ohwi.is_contiguous()
     if out is None:
         out = torch.empty(B, H, W, Cout, device=x_nchw.device, dtype=BF16)
-    L.check(lib.tmix_conv_in(_p(x_nchw), _p(w_ohwi), _p(bias), _p(out), B, Cin, H, W, Cout, _stream()), "tmix_conv_in")
+    if pre_w is None:
+        assert pre_b is None, "pre_b without pre_w"
+        L.check(lib.tmix_conv_in(_p(x_nchw), _p(w_ohwi), _p(bias), _p(out), B, Cin, H, W, Cout, _stream()), "tmix_conv_in")
+        return out
+    pw = torch.as_tensor(pre_w, dtype=torch.float32, device="cpu").contiguous()          # the entry reads the map on the host
+    pb = None if pre_b is None else torch.as_tensor(pre_b, dtype=torch.float32, device="cpu").contiguous()
+    assert pw.numel() == 16 and (pb is None or pb.numel() == 4)
+    L.check(lib.tmix_conv_in_pre(_p(x_nchw), _p(w_ohwi), _p(bias), _p(out), B, Cin, H, W, Cout, _p(pw), _p(pb), _stream()), "tmix_conv_in_pre")
     return out
 
 
