@@ -65,6 +65,12 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          prediction is scaled by PHI * sd(conditional) / sd(guided) + (1 - PHI), per UNet row (on a canvas: per window), against
                          the over-exposed look of a high --guidance_scale.  0 (default): off, today's run bit for bit; 0.7 is the paper's
                          value.  Two small launches per step, no UNet call.  Does not combine with --keep_latents / --keep_image
+  --eta E                stochastic sampling, E in [0, 1]: every step that advances the trajectory adds noise, a pure function of (the
+                         trajectory's seed, the schedule step, the canvas coordinate) computed inside the fused step kernel -- the same bits
+                         alone, co-batched, on another GPU, eagerly or from a graph, and identical where canvas windows overlap.  --solver ddim:
+                         the DDIM paper's eta; --solver dpmpp2m: SDE-DPM-Solver++(2M) in k-diffusion's eta form; the two definitions coincide at
+                         0 and 1 and differ in between.  0 (default): today's run bit for bit.  Does not combine with
+                         --keep_latents / --keep_image
   --num_seeds N          N trajectories, seeds seed..seed+N-1 (trajectory i is exactly what `--seed seed+i` alone produces: its
                          x_T comes from its own generator), co-batched --seeds_per_batch at a time
   --gpus G               shard those seeds round-robin over G GPUs of this node: the script starts one process per GPU itself
@@ -156,6 +162,10 @@ def build_parser():
     p.add_argument('--guidance_rescale', type=float, default=0.0,
                    help='PHI in [0, 1]: scale every guided prediction back towards the standard deviation of its conditional one '
                         '(0: off; 0.7 is the value of arXiv:2305.08891)')
+    p.add_argument('--eta', type=float, default=0.0,
+                   help='E in [0, 1]: noise added by every trajectory step, generated inside the step kernel from (seed, step, canvas coordinate). '
+                        '--solver ddim: the DDIM paper\'s eta; --solver dpmpp2m: k-diffusion\'s SDE-DPM-Solver++(2M) eta; the two coincide at 0 and 1 '
+                        'and differ in between (0: off)')
     p.add_argument('--timestep_spacing', type=str, default='leading', choices=['leading', 'logsnr'],
                    help="logsnr: n_timesteps uniform in log-SNR from the 'leading' grid's first timestep down to t = 1")
     p.add_argument('--num_seeds', type=int, default=1, help='trajectories to sample: seeds seed..seed+n-1')
@@ -336,7 +346,15 @@ def save_soft_weights(opt, tw, side_dir):
 
 
 def check_solver_args(opt):
-    """--solver / --timestep_spacing / --guidance_rescale: refuses what the sampler would refuse, before anything touches the GPU"""
+    """--solver / --timestep_spacing / --guidance_rescale / --eta: refuses what the sampler would refuse, before anything touches the GPU"""
+    from tweediemix_amd.solver import validate_eta
+    try:
+        eta = validate_eta(opt.eta, '--eta')
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if eta > 0.0 and (opt.keep_latents or opt.keep_image):
+        flag = '--keep_latents' if opt.keep_latents else '--keep_image'
+        raise SystemExit(f'--eta {eta} does not combine with {flag}: the keep region exists on the deterministic step only')
     if opt.solver != 'ddim' and (opt.keep_latents or opt.keep_image):
         flag = '--keep_latents' if opt.keep_latents else '--keep_image'
         raise SystemExit(f'--solver {opt.solver} does not combine with {flag}: the keep region exists on the --solver ddim step only')
@@ -613,6 +631,7 @@ def main(argv=None):
                       strict_reference=strict, use_graphs=not opt.no_graphs, n_seeds=per, n_streams=opt.streams, vae=vae,
                       fp8=(opt.dtype == 'fp8'), attention_masks=attn, mask_soften=soften,
                       solver=opt.solver, timestep_spacing=opt.timestep_spacing, guidance_rescale=opt.guidance_rescale,
+                      eta=opt.eta, noise_seeds=([opt.seed] * per if opt.eta > 0.0 else None),
                       **(dict(canvas={k: canvas[k] for k in ('height', 'width', 'overlap')}) if canvas else {}))
     if vae_scaling:                                       # fusion_sampling.py:518 divides by vae.config.scaling_factor
         tw.vae_scaling_factor = float(vae_scaling)
@@ -633,6 +652,8 @@ def main(argv=None):
         current["ids"], current["turn"] = ids, 0
         if keep is not None:
             tw.set_keep(keep_x0, keep_w, torch.cat([keep_noise_for_seed(sd_, h, w) for sd_ in ids]))
+        if opt.eta > 0.0:                                 # a trajectory's step noise is a function of its own seed, as its x_T is
+            tw.set_noise_seeds(ids)
         lat_b = tw.run_fusion(torch.cat([noise_for_seed(sd_, h, w) for sd_ in ids]))
         lats.append(lat_b[:len(batch)])
         if attn is not None:

@@ -142,6 +142,36 @@ int tmix_fused_tweedie_step_rs_dev(const float* x, const void* eps, int eps_dtyp
 int tmix_fused_tweedie_step_ms_rs_dev(const float* x, const void* eps, int eps_dtype, const float* masks,
                                       int64_t mask_seed_stride, float* out_x, float* out_x0, float* x0_prev, int K, int channels,
                                       int64_t hw, int mode, int rows, int seeds, const float* params, const float* factors, void* stream);
+/* STOCHASTIC STEPS (no reference counterpart in the hot path: the reference's pipelines carry `eta` to their schedulers).  The
+ * noise of an element is a pure function of (trajectory key, canvas index, schedule step, stream id): one Philox4x32-10 call (Salmon et al.,
+ * SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) with key = {key_lo, key_hi} and counter = {index low
+ * word, index high word, step, stream_id}, then Box-Muller on output words 0 and 1:
+ *   u1 = ((w0 >> 9) + 0.5) * 2^-23        angle = 2 pi ((w1 >> 9) + 0.5) * 2^-23        z = sqrt(-2 ln u1) cos(angle),   |z| < 5.8
+ * with ln, sin and cos written out in integer operations and single-rounded fp32 add, sub, mul, div and sqrt (csrc/noise.h), so that
+ * noise.normal (numpy) gives the same bits.  stream_id 0 is the image sampler's step; other values are reserved.
+ * tmix_noise_normal: the generator on its own: z[i] = the normal of index first_index + i, i < n.  TMIX_EINVAL: null z.  TMIX_ESHAPE: n < 1,
+ * first_index < 0.
+ * tmix_fused_tweedie_step_noise_dev: ONE entry for the stochastic form of tmix_fused_tweedie_step_dev / _rs_dev / _ms_dev / _ms_rs_dev.  The
+ * arguments of tmix_fused_tweedie_step_dev, then
+ *   x0_prev  NULL: the DDIM params layout and move (parent tmix_fused_tweedie_step_dev); else the history buffer: the multistep layout and move
+ *   factors  NULL: no guidance rescale; else [seeds][rows-1] with the meaning it has in the parent's _rs_dev form
+ *   keys     device array uint32 [seeds / n_win][2]: {low word, high word} of every trajectory's 64-bit seed value
+ *   w        the row width of the latent; hw % w == 0
+ *   n_win, win_yx, canvas_h, canvas_w   tmix_window_consensus's window table (HOST array, passed by value): the `seeds` rows are window-major
+ *            inside a trajectory, row r is window r % n_win of trajectory r / n_win, and element (c, y, x) of that window has the index
+ *            c*canvas_h*canvas_w + (oy + y)*canvas_w + (ox + x).  win_yx NULL with n_win 1: no canvas, the index is the element's own
+ *            c*hw + y*w + x and canvas_h / canvas_w are not read.
+ *   params   12 floats: the parent layout's 8, then {cz, step_index, 0, 0}; step_index an integer below 2^24 (exact in fp32)
+ * Per element, with x0 and moved (the parent's out_x value before its is_last selection) formed by the parent's operations in its order:
+ *   out_x = is_last ? x0 : (cz != 0 ? moved + cz*z : moved)        one product and one sum, not contracted
+ * out_x0 and the history write are the parent's.  With cz == 0 all outputs are the parent entry's bit for bit.  Two windows that cover one
+ * canvas pixel add the same value there.  TMIX_EINVAL: RESAMPLE mode, null keys, n_win outside 1..TMIX_MAX_WINDOWS (or not 1 without win_yx).
+ * TMIX_ESHAPE: hw % w != 0, seeds % n_win != 0, a window that leaves the canvas.  Otherwise the parents' checks; all before any launch. */
+int tmix_noise_normal(float* z, int64_t n, int64_t first_index, uint32_t key_lo, uint32_t key_hi, uint32_t step, uint32_t stream_id, void* stream);
+int tmix_fused_tweedie_step_noise_dev(const float* x, const void* eps, int eps_dtype, const float* masks, int64_t mask_seed_stride,
+                                      float* out_x, float* out_x0, int K, int channels, int64_t hw, int mode, int rows, int seeds,
+                                      const float* params, float* x0_prev, const float* factors, const uint32_t* keys, int w,
+                                      int n_win, const int* win_yx, int canvas_h, int canvas_w, void* stream);
 /* Head of the captured step (fusion_sampling.py:324-327, `latent_model_input = torch.cat([x] * rows)`, and the timestep
  * argument of the UNet call :340): latent[(s*rows + r)][n] = x[s][n] for every row r, t_dev[s*rows + r] = params[0]. */
 int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,

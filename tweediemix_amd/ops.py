@@ -150,6 +150,47 @@ def fused_tweedie_step_rs_dev(x, eps, masks, mode, K, params, factors, out_x=Non
     return out_x
 
 
+def noise_normal(n, first_index, key, step, stream_id=0, out=None, device="cuda"):
+    """tmix_noise_normal: z [n] fp32, z[i] the normal of index first_index + i under key = (low word, high word) at schedule step `step`
+    (noise.normal gives the same bits).  out: a contiguous fp32 device tensor of n elements to write instead of a new one."""
+    if out is None:
+        out = torch.empty(int(n), device=device, dtype=torch.float32)
+    _need_cuda(out)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == int(n), (tuple(out.shape), n)
+    L.check(L.load().tmix_noise_normal(_p(out), int(n), int(first_index), int(key[0]), int(key[1]), int(step), int(stream_id), _stream()),
+            "tmix_noise_normal")
+    return out
+
+
+def noise_keys(seeds, device):
+    """the `keys` array of fused_tweedie_step_noise_dev: int32 [len(seeds), 2] holding the {low, high} words of every trajectory's seed value"""
+    from .noise import seed_key
+    words = np.array([seed_key(s) for s in seeds], dtype=np.uint32).reshape(-1, 2)
+    return torch.from_numpy(words.view(np.int32).copy()).to(device)
+
+
+def fused_tweedie_step_noise_dev(x, eps, masks, mode, K, params, keys, x0_prev=None, factors=None, windows=None, canvas_hw=None, out_x=None,
+                                 out_x0=None):
+    """tmix_fused_tweedie_step_noise_dev: the stochastic form of fused_tweedie_step_dev's entry (x0_prev None), of fused_tweedie_step_ms_dev
+    (x0_prev the history buffer) and, with factors [S, rows-1], of their rescale forms.  params holds 12 floats: the parent's 8, then
+    {cz, step_index, 0, 0}.  keys int32 [S / n_win, 2] (noise_keys).  windows [(oy, ox), ...] with canvas_hw = (canvas_h, canvas_w): the S rows
+    are window-major inside a trajectory (window_consensus's layout); None: no canvas.  out_x may be x itself.  Returns out_x."""
+    _need_cuda(x, eps, masks, params, keys, x0_prev, factors)
+    S, _n, _hw, rows, out_x, head = _dev_step_head(x, eps, masks, mode, K, params, out_x, out_x0, x0_prev)
+    n_win = 1 if windows is None else len(windows)
+    assert params.numel() >= 12, params.numel()
+    assert keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() == 2 * (S // n_win) and S % n_win == 0, (tuple(keys.shape), S, n_win)
+    if factors is not None:
+        assert factors.dtype == torch.float32 and factors.is_contiguous() and factors.numel() == S * (rows - 1), tuple(factors.shape)
+    yx, ch, cw = None, 0, 0
+    if windows is not None:
+        yx = (C.c_int32 * (2 * n_win))(*[int(v) for o in windows for v in o])
+        ch, cw = int(canvas_hw[0]), int(canvas_hw[1])
+    L.check(L.load().tmix_fused_tweedie_step_noise_dev(*head, _p(x0_prev), _p(factors), _p(keys), x.shape[-1], n_win, yx, ch, cw, _stream()),
+            "tmix_fused_tweedie_step_noise_dev")
+    return out_x
+
+
 def window_consensus(x, groups, offsets, canvas_hw, weight=None):
     """tmix_window_consensus, in place on x [groups * n_win, C, h, w] fp32 (group-major: b = group * n_win + window): every canvas pixel
     that several windows cover becomes their weighted mean in all of them.  offsets [(oy, ox), ...] the windows' corners on the canvas

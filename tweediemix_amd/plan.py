@@ -38,11 +38,12 @@ def hint_bytes(nbytes, cap, over):
 
 
 class ParamRing:
-    """Pinned staging ring for a step's eight parameter floats (image and video sampler).  The host runs ahead of the device by whole steps: next()
-    hands out a slot once the copy that last read it has completed, upload(dst) copies it asynchronously and records.  cuda=False: pageable, no events."""
+    """Pinned staging ring for a step's eight parameter floats (image and video sampler; width=12 for the image sampler's stochastic steps).  The host
+    runs ahead of the device by whole steps: next() hands out a slot once the copy that last read it has completed, upload(dst) copies it
+    asynchronously and records (n: only the slot's first n floats into dst's first n).  cuda=False: pageable, no events."""
 
-    def __init__(self, cuda=True, slots=64):
-        z = torch.zeros(slots, 8, dtype=torch.float32)
+    def __init__(self, cuda=True, slots=64, width=8):
+        z = torch.zeros(slots, width, dtype=torch.float32)
         self.slots, self.events, self.i, self.cuda = (z.pin_memory() if cuda else z), [None] * slots, -1, cuda
 
     def next(self):
@@ -51,8 +52,11 @@ class ParamRing:
             self.events[self.i].synchronize()
         return self.slots[self.i]
 
-    def upload(self, dst):
-        dst.copy_(self.slots[self.i], non_blocking=True)
+    def upload(self, dst, n=None):
+        if n is None:
+            dst.copy_(self.slots[self.i], non_blocking=True)
+        else:
+            dst[:n].copy_(self.slots[self.i][:n], non_blocking=True)
         if self.cuda:
             self.events[self.i] = torch.cuda.Event()
             self.events[self.i].record()

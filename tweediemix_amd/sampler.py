@@ -16,6 +16,8 @@ Same method names, argument meaning and step semantics as fusion_generation/fusi
   (tmix_fused_tweedie_step_ms_dev), on an optional log-SNR timestep grid (timestep_spacing="logsnr"),
 * optionally (guidance_rescale=phi > 0) the guided prediction of every concept row scaled back towards the standard deviation of its
   conditional prediction (tmix_cfg_rescale_factors in front of the *_rs_dev form of whichever step entry runs), in every step of every phase,
+* optionally (eta > 0) noise added by every step that advances the trajectory, generated inside the step kernel from (seed, schedule index,
+  canvas coordinate) (tmix_fused_tweedie_step_noise_dev: one entry for the stochastic form of the DDIM, solver and rescale steps),
 * ONE hipGraph per (call kind, step mode) holding the whole step -- latent broadcast + timestep
   (tmix_step_prologue), the UNet launch chains, the fused step for all co-batched seeds: a timestep is one 32-byte
   parameter upload and one graph replay.
@@ -27,6 +29,7 @@ towers), `vae.py` (final / preview decode) and `masks.py` (side-car contract) pr
 """
 from __future__ import annotations
 
+import ctypes as C
 from types import SimpleNamespace
 
 import torch
@@ -36,7 +39,7 @@ from . import ops
 from .schedule import Schedule
 from .guidance import validate_phi
 from .plan import ParamRing
-from .solver import SOLVERS, multistep_coeffs
+from .solver import SOLVERS, ddim_eta_coeffs, multistep_coeffs, multistep_eta_coeffs, validate_eta
 from .unet import KVCache, PlanGroup, TokenMapSpec, TokenPropSpec, UNetPlan, UNetWeights
 
 F32 = torch.float32
@@ -116,14 +119,29 @@ class Tweediemix:
                       (two small launches on the eps rows the plan has just written) and then tmix_fused_tweedie_step_rs_dev / _ms_rs_dev in place
                       of the step, in the same captured graph (keys get "rs" appended).  Statistics are per UNet row: on a canvas per window.
                       Not with set_keep.  DESIGN.md 7k.
+    eta               in [0, 1], default 0.0 = the deterministic sampler (today's entries, launches, graph keys and bits).  eta > 0: the one move
+                      per schedule entry that advances the trajectory -- the fusion step, the plain step, the last PLAIN step of the start
+                      timestep, every solver step -- adds cz * z through tmix_fused_tweedie_step_noise_dev, z a pure function of (the
+                      trajectory's noise seed, the entry's index in scheduler.timesteps, the element's canvas coordinate) computed inside the
+                      step kernel (graph keys get "eta" appended; 48 bytes uploaded).  solver="ddim": the DDIM paper's eta
+                      (solver.ddim_eta_coeffs); solver="dpmpp2m": SDE-DPM-Solver++(2M) in k-diffusion's eta form (solver.multistep_eta_coeffs;
+                      the first timestep stays a DDIM step); the two definitions coincide at eta = 0 and 1.  Resampling round trips, the
+                      look-ahead, the probe and the propagate rounds stay on today's entries.  Needs noise_seeds.  Not with set_keep.
+                      DESIGN.md 7n.
+    noise_seeds       one integer (a 64-bit seed value) per trajectory the caller sees; set_noise_seeds replaces them between runs.  A
+                      trajectory's noise depends on its own seed alone: not on what it is co-batched with, the GPU, graphs or windows.
     """
 
     def __init__(self, config, weights: UNetWeights, text_embeds, text_embeds_single, mask_provider,
                  concept_num: int, lora: bool = False, strict_reference: bool = True, use_graphs: bool = False,
                  n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None,
-                 mask_soften=None, solver: str = "ddim", timestep_spacing: str = "leading", guidance_rescale: float = 0.0):
+                 mask_soften=None, solver: str = "ddim", timestep_spacing: str = "leading", guidance_rescale: float = 0.0,
+                 eta: float = 0.0, noise_seeds=None):
         self.config = config
         self.guidance_rescale = validate_phi(guidance_rescale)
+        self.eta = validate_eta(eta)
+        if self.eta > 0.0 and noise_seeds is None:
+            raise ValueError(f"eta={self.eta}: noise_seeds (one integer per trajectory) are what the step's noise is a function of")
         if solver not in SOLVERS:
             raise ValueError(f"solver={solver!r}: one of {SOLVERS}")
         self.solver = solver
@@ -212,7 +230,12 @@ class Tweediemix:
         self._x_backup = torch.zeros_like(self.x_state)
         # attention_masks with propagate >= 1: the state the last look-ahead call read, which the propagate rounds replay
         self._x_look = torch.zeros_like(self.x_state) if (self.attention_masks or {}).get("propagate") else None
-        self.step_params = torch.zeros(8, device=self.device, dtype=F32)      # {t, sa, s1, sa_next, s1_next, is_last, g, -}
+        # {t, sa, s1, sa_next, s1_next, is_last, g, -}; eta > 0: four more floats {cz, step index, 0, 0}, which the noise entry alone reads
+        self._n_params = 12 if self.eta > 0.0 else 8
+        self.step_params = torch.zeros(self._n_params, device=self.device, dtype=F32)
+        self._noise_keys = None          # eta > 0: int32 [n_canvas, 2], every trajectory's key words at an address the captured steps keep
+        if noise_seeds is not None:
+            self.set_noise_seeds(noise_seeds)
         # solver="dpmpp2m": the blended estimate of the solver step before (tmix_fused_tweedie_step_ms_dev reads and rewrites it; its steps
         # upload {t, sa, s1, cx, c0, c1, is_last, g} into step_params instead) and which step wrote it: (schedule index, step mode) or None
         self._x0_prev = torch.zeros_like(self.x_state) if solver != "ddim" else None
@@ -225,7 +248,7 @@ class Tweediemix:
             self._rs_factors = torch.ones(S * (self._rs_rows - 1), device=self.device, dtype=F32)
             self._rs_ws = ops.cfg_rescale_ws(self._rs_rows, S, self.device)
         self._keep = self._keep_bufs = None    # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
-        self._ring = ParamRing(cuda=self.device.type == "cuda")     # staging for the asynchronous upload of step_params
+        self._ring = ParamRing(cuda=self.device.type == "cuda", width=self._n_params)     # staging for the asynchronous upload of step_params
         self._mask_buf = None            # fixed-address copy of self.masks that the captured fusion step reads
 
     # ------------------------------------------------------------------ wide canvas
@@ -273,6 +296,18 @@ class Tweediemix:
         from . import canvas as CV
         return CV.assemble(x, self.windows, self.canvas_h, self.canvas_w)
 
+    # ------------------------------------------------------------------ noise seeds
+    def set_noise_seeds(self, seeds):
+        """the 64-bit seed value of every trajectory's step noise (eta > 0), copied into a buffer of fixed address: captured steps read it"""
+        seeds = [int(v) for v in seeds]
+        if len(seeds) != self.n_canvas:
+            raise ValueError(f"noise_seeds: {len(seeds)} values for {self.n_canvas} trajectories")
+        keys = ops.noise_keys(seeds, self.device)
+        if self._noise_keys is None:
+            self._noise_keys = keys
+        else:
+            self._noise_keys.copy_(keys)
+
     # ------------------------------------------------------------------ keep region
     def set_keep(self, x0, weight, eps):
         """Hold part of the latent while the loop samples the rest (re-roll one concept of a finished image, or sample into a template image).
@@ -280,6 +315,8 @@ class Tweediemix:
         the fixed noise of every seed's kept part.  From the next run_fusion / sample_loop on every step writes
         weight * (sa' x0 + s1' eps) + (1 - weight) * (its own result), with sa' / s1' of the state it writes (tmix_fused_tweedie_step_keep_dev),
         x_T is composited the same way once, and the final latent holds x0 itself.  The tensors are copied: captured steps read these buffers."""
+        if self.eta > 0.0:               # the kept part is re-noised with ONE fixed eps at every level: fresh noise has no place in it (DESIGN.md 7n)
+            raise ValueError(f"set_keep: not with eta={self.eta} (the keep region exists on the deterministic step only)")
         if self.guidance_rescale > 0.0:  # a keep entry that takes factors does not exist (yet)
             raise ValueError(f"set_keep: not with guidance_rescale={self.guidance_rescale} (the keep region exists on the unscaled step only)")
         if self.solver != "ddim":        # the keep term needs sa_next / s1_next, which the multistep entry's eight floats do not carry
@@ -408,8 +445,9 @@ class Tweediemix:
         else:
             self._set_masks(m)
 
-    def _enqueue_step(self, kind, mode, ms=False):
-        """the launches of one denoising step on the current stream: prologue, UNet chains, fused step (in place; ms: the multistep entry)."""
+    def _enqueue_step(self, kind, mode, ms=False, nz=False):
+        """the launches of one denoising step on the current stream: prologue, UNet chains, fused step (in place; ms: the multistep entry;
+        nz: the noise entry in its DDIM or multistep form)."""
         p = self.plan(kind)
         S = self.n_seeds
         rows = p.B // S
@@ -419,13 +457,13 @@ class Tweediemix:
         L.check(lib.tmix_step_prologue(self.x_state.data_ptr(), p.latent.data_ptr(), p.t_dev.data_ptr(),
                                        self.step_params.data_ptr(), S, rows, n, st), "tmix_step_prologue")
         p.run()
-        self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st, ms)
+        self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st, ms, **(dict(nz=True) if nz else {}))
         if self.windows is not None:
             self._consensus(self.x_state)
 
-    def _fused_step(self, eps_ptr, eps_dt, rows, mode, st, ms=False):
+    def _fused_step(self, eps_ptr, eps_dt, rows, mode, st, ms=False, nz=False):
         """the fused step for every seed, in place on x_state; with a keep region set (set_keep) through the entry that holds it; ms: the
-        multistep entry, which also reads and rewrites the history buffer"""
+        multistep entry, which also reads and rewrites the history buffer; nz: the noise entry (eta > 0), which is all four forms"""
         lib = L.load()
         m = self._mask_buf if mode == L.STEP_FUSION else None
         mss = 0 if (m is None or m.dim() == 4) else self.concept_num * self.h * self.w
@@ -438,6 +476,16 @@ class Tweediemix:
             L.check(lib.tmix_cfg_rescale_factors(eps_ptr, eps_dt, self._rs_factors.data_ptr(), self._rs_ws.data_ptr(), self.concept_num, 4, hw, mode,
                                                  rows, self.n_seeds, self.step_params.data_ptr(), 7 if ms else 6, self.guidance_rescale, st),
                     "tmix_cfg_rescale_factors")
+        if nz:                           # x0_prev / factors present or NULL select the parent whose move and rescale the entry takes
+            yx = None
+            if self.windows is not None:
+                yx = (C.c_int32 * (2 * len(self.windows)))(*[int(v) for o in self.windows for v in o])
+            L.check(lib.tmix_fused_tweedie_step_noise_dev(*head, self._x0_prev.data_ptr() if ms else None,
+                                                          self._rs_factors.data_ptr() if self.guidance_rescale > 0.0 else None,
+                                                          self._noise_keys.data_ptr(), self.w, 1 if yx is None else len(self.windows), yx,
+                                                          self.canvas_h, self.canvas_w, st), "tmix_fused_tweedie_step_noise_dev")
+            return
+        if self.guidance_rescale > 0.0:
             if ms:
                 L.check(lib.tmix_fused_tweedie_step_ms_rs_dev(*head[:7], self._x0_prev.data_ptr(), *head[7:], self._rs_factors.data_ptr(), st),
                         "tmix_fused_tweedie_step_ms_rs_dev")
@@ -454,15 +502,28 @@ class Tweediemix:
         L.check(lib.tmix_fused_tweedie_step_keep_dev(*head, kx.data_ptr(), 0 if kx.shape[0] == 1 else 4 * hw, ke.data_ptr(), 4 * hw,
                                                      kw.data_ptr(), 0 if kw.shape[0] == 1 else hw, st), "tmix_fused_tweedie_step_keep_dev")
 
-    def _run_step(self, kind, mode, t, at, at_next, is_last=False, ms=None):
+    def _run_step(self, kind, mode, t, at, at_next, is_last=False, ms=None, step_index=None):
         """x_state <- step(x_state) for every seed; x0_state <- the Tweedie estimate.  Host work per step: eight floats.
-        ms = (cx, c0, c1): a multistep solver step (at_next is then not read: the move is in the coefficients)."""
+        ms = (cx, c0, c1): a multistep solver step (at_next is then not read: the move is in the coefficients).
+        step_index (eta > 0 only): the step advances the trajectory from schedule entry step_index and adds that entry's noise; ms is then
+        (cx, c0, c1, cz), and a DDIM step's s1_next slot and cz are solver.ddim_eta_coeffs': twelve floats."""
         if "_unet" not in vars(self):
             self.unet_calls.append((kind, self.plan(kind).B // self.n_seeds, int(t)))
+        nz = step_index is not None
+        nzk = dict(nz=True) if nz else {}                 # a deterministic step calls _enqueue_step / _fused_step with today's arguments
         sa, s1, san, s1n = ops.step_coeffs(at, at_next)
+        cz = 0.0
+        if nz:
+            if ms is None:
+                sa, s1, san, s1n, cz = ddim_eta_coeffs(at, at_next, self.eta)
+            else:
+                cz = ms[3]
         move =(san, s1n) if ms is None else (ms[0], ms[1], ms[2])        # 7 floats, or 8 for a multistep step: the layouts the step kernels read
-        ops._fill_params([float(t), sa, s1, *move, 1.0 if is_last else 0.0, float(self.config.guidance_scale)], self._ring.next())
-        self._ring.upload(self.step_params)
+        vals = [float(t), sa, s1, *move, 1.0 if is_last else 0.0, float(self.config.guidance_scale)]
+        if nz:
+            vals = (vals + [0.0])[:8] + [0.0 if is_last else cz, float(step_index), 0.0, 0.0]
+        ops._fill_params(vals, self._ring.next())
+        self._ring.upload(self.step_params, None if self._n_params == 8 else 12 if nz else 8)      # 32 bytes, or 48 for a step with noise
         if mode == L.STEP_FUSION:
             assert self._mask_buf is not None, "fusion step before the masks were acquired"
         if "_unet" in vars(self):
@@ -470,26 +531,28 @@ class Tweediemix:
             # module in): the same fused step, eagerly, on whatever eps dtype the stand-in returns
             eps = self._unet(kind, self.x_state, t).contiguous()
             self._fused_step(eps.data_ptr(), ops._EPS_DT[eps.dtype], eps.shape[0] // self.n_seeds, mode,
-                             torch.cuda.current_stream().cuda_stream, ms is not None)
+                             torch.cuda.current_stream().cuda_stream, ms is not None, **nzk)
             if self.windows is not None:
                 self._consensus(self.x_state)
             return
         if not self.use_graphs:
-            self._enqueue_step(kind, mode, ms is not None)
+            self._enqueue_step(kind, mode, ms is not None, **nzk)
             return
         # a step captured with a keep region is another graph (another kernel, three more pointers): the ones captured without it stay valid
         # and so is a multistep step (another kernel, one more pointer): one graph serves both orders, the order is in the uploaded coefficients
         gkey = (kind, mode, "ms") if ms is not None else (kind, mode) if self._keep is None else (kind, mode, "keep")
         if self.guidance_rescale > 0.0:                   # two more launches and another step kernel: graphs of their own
             gkey = gkey + ("rs",)
+        if nz:                                            # another entry, two more pointers and the window table: graphs of their own
+            gkey = gkey + ("eta",)
         g = self.graphs.get(gkey)
         if g is None:
-            self._enqueue_step(kind, mode, ms is not None)    # warm-up outside capture (kernel attributes, lazy module load);
+            self._enqueue_step(kind, mode, ms is not None, **nzk)    # warm-up outside capture (kernel attributes, lazy module load);
             torch.cuda.synchronize()                      # it has already performed this step, so no replay now
             g = torch.cuda.CUDAGraph()
             keep = self.x_state.clone()
             with torch.cuda.graph(g):
-                self._enqueue_step(kind, mode, ms is not None)
+                self._enqueue_step(kind, mode, ms is not None, **nzk)
             self.x_state.copy_(keep)                      # capture does not execute, but keep the state explicit
             self.graphs[gkey] = g
             return
@@ -572,18 +635,25 @@ class Tweediemix:
         solver_step = self.solver != "ddim" and t != self.start_t
         if not solver_step:
             self._ms_last = None                        # a timestep on the DDIM entry leaves no history for a second-order step to use
+        # eta > 0: the ONE move of this schedule entry that advances the trajectory takes the entry's noise (the resampling round trips and
+        # the look-ahead below stay deterministic: they return to where they started); eta == 0 passes nothing, today's calls
+        adv = {}
+        if self.eta > 0.0:
+            if t not in self.scheduler.timesteps:
+                raise ValueError(f"eta={self.eta}: t = {t} is not one of the schedule's timesteps (the noise is indexed by the schedule entry)")
+            adv = dict(step_index=self.scheduler.timesteps.index(t))
         if solver_step:
             self._solver_step(t, at, at_next, last)
         elif self._in_fusion(t):
             kind = "fusion" if (t in self._window) else "fusion_base"
-            self._run_step(kind, L.STEP_FUSION, t, at, at_next, last)
+            self._run_step(kind, L.STEP_FUSION, t, at, at_next, last, **adv)
         elif t == self.start_t:
             for _ in range(cfg.resampling_steps):
                 self._run_step("start", L.STEP_RESAMPLE, t, at, at_next)
                 self._run_step("plain", L.STEP_PLAIN, next_t, at_next, at)        # Tweedie at next_t, re-noise to t
-            self._run_step("start", L.STEP_PLAIN, t, at, at_next, last)
+            self._run_step("start", L.STEP_PLAIN, t, at, at_next, last, **adv)
         else:
-            self._run_step("plain", L.STEP_PLAIN, t, at, at_next, last)
+            self._run_step("plain", L.STEP_PLAIN, t, at, at_next, last, **adv)
 
         if t == self.t_cond_prev:                       # fusion_sampling.py:431-469
             self._x_backup.copy_(self.x_state)          # the look-ahead does not move the trajectory
@@ -636,8 +706,12 @@ class Tweediemix:
             kind, mode = "plain", L.STEP_PLAIN
         second = self._ms_last == (i - 1, mode)
         # the last step writes x0 itself: its move (to alpha = 1, or on the 'leading' grid to the alpha it stands on) has no finite h
-        ms = (0.0, 1.0, 0.0) if last else multistep_coeffs(self.alpha(ts[i - 1]), at, at_next, second)
-        self._run_step(kind, mode, t, at, at_next, last, ms=ms)
+        if self.eta > 0.0:
+            ms = (0.0, 1.0, 0.0, 0.0) if last else multistep_eta_coeffs(self.alpha(ts[i - 1]), at, at_next, second, self.eta)
+            self._run_step(kind, mode, t, at, at_next, last, ms=ms, step_index=i)
+        else:
+            ms = (0.0, 1.0, 0.0) if last else multistep_coeffs(self.alpha(ts[i - 1]), at, at_next, second)
+            self._run_step(kind, mode, t, at, at_next, last, ms=ms)
         self._ms_last = (i, mode)
 
     def _propagate_rounds(self, t):

@@ -53,6 +53,65 @@ def multistep_coeffs(a_prev, a, a_next, second_order):
     return tuple(float(F32(v)) for v in multistep_coeffs64(a_prev, a, a_next, second_order))
 
 
+# ------------------------------------------------------------------------------------------------ stochastic steps (eta)
+def validate_eta(eta, name="eta"):
+    """eta as a float in [0, 1], or ValueError"""
+    try:
+        e = float(eta)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}={eta!r}: a number in [0, 1]") from None
+    if not 0.0 <= e <= 1.0:          # NaN fails both comparisons
+        raise ValueError(f"{name}={eta!r}: a number in [0, 1] (0: the deterministic sampler, 1: DDPM-like / SDE-DPM-Solver++)")
+    return e
+
+
+def ddim_eta_coeffs64(a, a_next, eta):
+    """(sa, s1, sa_next, s1_dir, cz) of the DDIM step with the paper's eta (Song et al. 2020, eq. 12 and 16) in fp64 from the fp32 alphas:
+    sigma = eta sqrt((1 - a') / (1 - a)) sqrt(1 - a / a'), s1_dir = sqrt(1 - a' - sigma^2) takes the s1_next slot, cz = sigma"""
+    a, an = float(F32(a)), float(F32(a_next))
+    if not 0.0 < a <= an <= 1.0:
+        raise ValueError(f"ddim_eta_coeffs: alpha {a} -> {an} does not move towards the data")
+    sigma = eta * math.sqrt((1.0 - an) / (1.0 - a)) * math.sqrt(1.0 - a / an)
+    return math.sqrt(a), math.sqrt(1.0 - a), math.sqrt(an), math.sqrt(max(1.0 - an - sigma * sigma, 0.0)), sigma
+
+
+def ddim_eta_coeffs(a, a_next, eta):
+    """(sa, s1, sa_next, s1_next slot, cz) the sampler uploads for a solver='ddim' step.  sa, s1, sa_next are ops.step_coeffs' fp32 square roots
+    (the x0 of a stochastic step is formed with today's coefficients); the s1_next slot and cz are ddim_eta_coeffs64's, rounded ONCE to fp32.
+    eta == 0 is today's step: ops.step_coeffs' four values bit for bit (alphas that do not move towards the data included) and cz == 0.0"""
+    at, an, one = F32(a), F32(a_next), F32(1)
+    sa, s1, san, s1n = float(np.sqrt(at)), float(np.sqrt(one - at)), float(np.sqrt(an)), float(np.sqrt(one - an))
+    if eta == 0.0:
+        return sa, s1, san, s1n, 0.0
+    _, _, _, s1d, cz = ddim_eta_coeffs64(a, a_next, eta)
+    return sa, s1, san, float(F32(s1d)), float(F32(cz))
+
+
+def multistep_eta_coeffs64(a_prev, a, a_next, second_order, eta):
+    """(cx, c0, c1, cz) of SDE-DPM-Solver++(2M) in k-diffusion's eta form (sample_dpmpp_2m_sde, midpoint), in fp64: with he = eta h
+    cx = (s1'/s1) e^-he,  B = sa' (1 - e^(-h - he)),  c0 = B (1 + 1/(2r)),  c1 = -B / (2r)  (first order: c0 = B, c1 = 0),
+    cz = s1' sqrt(1 - e^(-2 he)).  eta == 0 is multistep_coeffs64.  This eta and DDIM's coincide at 0 and 1 and differ in between."""
+    cx, c0, c1 = multistep_coeffs64(a_prev, a, a_next, second_order)
+    if eta == 0.0:
+        return cx, c0, c1, 0.0
+    sa, s1, lam = _sa_s1_lam(a)
+    san, s1n, lam_n = _sa_s1_lam(a_next)
+    h = lam_n - lam
+    he = eta * h
+    B = -san * math.expm1(-h - he)
+    if second_order:
+        r = (lam - _sa_s1_lam(a_prev)[2]) / h
+        c0, c1 = B * (1.0 + 1.0 / (2.0 * r)), -B / (2.0 * r)
+    else:
+        c0, c1 = B, 0.0
+    return (s1n / s1) * math.exp(-he), c0, c1, s1n * math.sqrt(-math.expm1(-2.0 * he))
+
+
+def multistep_eta_coeffs(a_prev, a, a_next, second_order, eta):
+    """multistep_eta_coeffs64 rounded ONCE to fp32; at eta == 0 multistep_coeffs' values and cz == 0.0"""
+    return tuple(float(F32(v)) for v in multistep_eta_coeffs64(a_prev, a, a_next, second_order, eta))
+
+
 def _h(a, lowp):
     return a.astype(lowp).astype(F32) if lowp is not None else a
 
