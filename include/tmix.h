@@ -148,7 +148,7 @@ int tmix_fused_tweedie_step_ms_rs_dev(const float* x, const void* eps, int eps_d
  * word, index high word, step, stream_id}, then Box-Muller on output words 0 and 1:
  *   u1 = ((w0 >> 9) + 0.5) * 2^-23        angle = 2 pi ((w1 >> 9) + 0.5) * 2^-23        z = sqrt(-2 ln u1) cos(angle),   |z| < 5.8
  * with ln, sin and cos written out in integer operations and single-rounded fp32 add, sub, mul, div and sqrt (csrc/noise.h), so that
- * noise.normal (numpy) gives the same bits.  stream_id 0 is the image sampler's step; other values are reserved.
+ * noise.normal (numpy) gives the same bits.  stream_id 0 is the image sampler's step, 1 the video sampler's; other values are reserved.
  * tmix_noise_normal: the generator on its own: z[i] = the normal of index first_index + i, i < n.  TMIX_EINVAL: null z.  TMIX_ESHAPE: n < 1,
  * first_index < 0.
  * tmix_fused_tweedie_step_noise_dev: ONE entry for the stochastic form of tmix_fused_tweedie_step_dev / _rs_dev / _ms_dev / _ms_rs_dev.  The
@@ -298,6 +298,34 @@ int tmix_vpred_step_ms_rs(const void* x, const void* v, void* out, float* x0_pre
                           float sa, float s1, float cx, float c0, float c1, const float* factors, void* stream);
 int tmix_vpred_step_ms_rs_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
                               const float* params, int videos, int channels, int frames, int64_t hw, const float* factors, void* stream);
+/* STOCHASTIC VIDEO STEPS (no reference counterpart): the noise of tmix_fused_tweedie_step_noise_dev (above) in the video step, ONE
+ * entry per layout for the stochastic form of all four parents.  Element i of video s = i / n_per_video draws
+ *   z = the normal of (index i % n_per_video, key {keys[s][0], keys[s][1]}, step, stream_id 1)
+ * -- its own linear index in its video's [channels][frames][hw] layout under its video's key, stream id 1 (0 is the image sampler's step, so the
+ * same seed draws unrelated noise there) -- one Philox call per element: z does not depend on `videos`, on the video's place in the batch or on
+ * the launch.  With x0, the history write and moved (the parent's stored value before the store's rounding) formed by the parent's operations:
+ *   out[i] = cz != 0 ? rnd(moved + rnd(cz * z)) : moved        one product and one sum, not contracted; rnd: to fp16 for TMIX_F16, else nothing
+ * (TMIX_BF16 rounds once, at the store).  With cz == 0 no generator call runs and every output is the parent entry's bit for bit.
+ * tmix_vpred_step_noise: the dense form on [videos][n_per_video] (v: [2][videos][n_per_video]) of `dtype`.
+ *   x0_prev  NULL: the DDIM move, (a, b) = (sa_next, s1_dir) with s1_dir = sqrt(1 - alpha' - sigma^2) and c not read (parents tmix_vpred_step /
+ *            _rs); else the fp32 history buffer and the multistep move (a, b, c) = (cx, c0, c1) (parents tmix_vpred_step_ms / _ms_rs); out may
+ *            alias x in both
+ *   factors  NULL: no guidance rescale; else [videos] as in tmix_vpred_step_rs
+ *   keys     device array uint32 [videos][2]: {low word, high word} of every video's 64-bit seed value
+ *   step     the schedule index of the step
+ * tmix_vpred_step_noise_dev: the form on plan rows: the arguments of tmix_vpred_step_dev, then x0_prev, factors, keys with the same meanings.
+ *   params   12 floats: the parent layout's 8 ({t, sa, s1, sa_next, s1_dir, g, 0, 0} without x0_prev, {t, sa, s1, cx, c0, c1, g, 0} with it), then
+ *            {cz, step_index, 0, 0}; step_index an integer below 2^24 (exact in fp32).  tmix_video_step_prologue and tmix_vpred_rescale_factors
+ *            read the first 8 only.
+ * Both: TMIX_EINVAL on a null x, v / v_u, v_c, out / params, on null keys and on a bad dtype; TMIX_ESHAPE on videos, n_per_video / channels, frames
+ * or hw below 1 or a clip stride shorter than one clip (null pointers are answered first, the dtype last); all before any launch; one launch
+ * on `stream`, capturable; no workspace. */
+int tmix_vpred_step_noise(const void* x, const void* v, void* out, float* x0_prev, int dtype, int videos, int64_t n_per_video, float g,
+                          float sa, float s1, float a, float b, float c, float cz, const float* factors, const uint32_t* keys, uint32_t step,
+                          void* stream);
+int tmix_vpred_step_noise_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, const float* params,
+                              int videos, int channels, int frames, int64_t hw, float* x0_prev, const float* factors, const uint32_t* keys,
+                              void* stream);
 /* First-frame feature injection of the patched ResnetBlock2D.forward (video_gen/utils_attn.py:433-455), in place on
  * x [clips][frames][per_frame]: frames 1.. <- frame 0 (hard) or interp*frame0 + one_minus_interp*frame. */
 int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,

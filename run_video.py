@@ -36,7 +36,15 @@ Guidance rescale (no reference counterpart; arXiv:2305.08891 section 3.4, DESIGN
   --guidance_rescale PHI    in [0, 1]; 0 (default): off, the run above launch for launch; 0.7: the paper's value.  Every step scales each video's
                             guided v-prediction back towards the standard deviation of its text-conditional one (tmix_vpred_rescale_factors, then
                             tmix_vpred_step_rs_dev / tmix_vpred_step_ms_rs_dev); meant for exactly this setting: zero terminal SNR, v-prediction,
-                            --guidance_scale 9.  Combines with every flag above; a value outside [0, 1] is refused before the GPU is touched."""
+                            --guidance_scale 9.  Combines with every flag above; a value outside [0, 1] is refused before the GPU is touched.
+
+Stochastic sampling (no reference counterpart: the reference hands `eta` to its scheduler):
+  --eta E                   in [0, 1]; 0 (default): off, the run above launch for launch.  Every step adds noise generated inside the step kernel
+                            (tmix_vpred_step_noise_dev), a pure function of (the video's seed -- the one its x_T is drawn from --, the schedule
+                            step, the element's index in the video): the same bits alone, co-batched, on another GPU, eagerly or from a graph.
+                            --solver ddim: the DDIM paper's eta; --solver dpmpp2m: SDE-DPM-Solver++(2M) in k-diffusion's eta form, the variant
+                            meant for few steps (`--solver dpmpp2m --timestep_spacing logsnr --eta 1`); the two coincide at 0 and 1.  Combines
+                            with every flag above; a value outside [0, 1] is refused before the GPU is touched and before any rank starts."""
 import argparse
 import os
 import sys
@@ -85,6 +93,9 @@ def build_parser():
     # guidance rescale; 0 is the run without it
     p.add_argument("--guidance_rescale", type=float, default=0.0, help="phi in [0, 1]: scale each video's guided v-prediction back towards the standard "
                    "deviation of the conditional one (arXiv:2305.08891 section 3.4; 0: off, 0.7: the paper's value)")
+    # stochastic sampling; 0 is the run without it
+    p.add_argument("--eta", type=float, default=0.0, help="in [0, 1]: every step adds noise computed inside the step kernel from (the video's seed, the "
+                   "schedule step, the element's index); ddim: the DDIM paper's eta, dpmpp2m: SDE-DPM-Solver++(2M)'s; 0: off")
     return p
 
 
@@ -132,6 +143,21 @@ def checked_rescale(opt):
         return validate_phi(opt.guidance_rescale, "--guidance_rescale")
     except ValueError as e:
         raise SystemExit(str(e))
+
+
+def checked_eta(opt):
+    """--eta through the one validator of eta, on the host before anything touches the GPU or any rank is started"""
+    from tweediemix_amd.solver import validate_eta
+    try:
+        return validate_eta(opt.eta, "--eta")
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
+def batch_noise_seeds(seeds, n_real):
+    """the noise seeds of one co-batched launch: a video's key is the seed its x_T is drawn from; the videos padded into a ragged last batch
+    (their results are dropped) take the key of the batch's last real video"""
+    return list(seeds[:n_real]) + [seeds[n_real - 1]] * (len(seeds) - n_real)
 
 
 def _vae_config(j):
@@ -259,6 +285,7 @@ def main(argv=None):
     opt = build_parser().parse_args(argv)
     images, videos = check_args(opt)
     phi = checked_rescale(opt)
+    eta = checked_eta(opt)
     from tweediemix_amd import dist as D, i2vgen as I, launch as LA, video as V
     few_step = (opt.solver, opt.timestep_spacing) != ("ddim", "leading")
     if opt.gpus > 1 and not LA.launched():
@@ -319,7 +346,8 @@ def main(argv=None):
         smp = plan = None                                            # the previous batch's plan and graphs go before the next are built
         plan = I.I2VVideoPlan(Wt, S, Fr, h, w, fe, ctx, ilf, streams=opt.streams, interp=opt.interp_ratio)
         inj = V.FeatureInjector(sch.injection_schedule(opt.injection_timestep), opt.interp_ratio, clips=2 * S, frames=Fr)
-        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs, solver=opt.solver, guidance_rescale=phi)
+        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs, solver=opt.solver, guidance_rescale=phi,
+                             eta=eta, noise_seeds=batch_noise_seeds([mine[i][1] for i in batch], n_real) if eta > 0.0 else None)
         lats.append(smp.sample(torch.cat([xs[i] for i in batch]).to(dev))[:n_real])
     smp = plan = None
     lat = torch.cat(lats) if lats else torch.zeros(0, 4, Fr, h, w, device=dev)

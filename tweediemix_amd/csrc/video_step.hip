@@ -4,7 +4,10 @@
 // The element's operations are step_core.h's (vpred_x0, vpred_ddim_move, vpred_ms_move), so the forms agree bit for bit -- device form with dense form,
 // factors of 1.0 with no rescale, the multistep x0 with the DDIM x0 -- because they are one loop.  Compiled with -ffp-contract=off so fp32 results are
 // bit-identical to the numpy restatements (guidance.vpred_rescaled_step_reference / vpred_rescaled_multistep_reference).
+// The stochastic step (tmix_vpred_step_noise[_dev]) is the same kernel with one trailing VideoNoiseArgs: the move of either solver
+// plus cz * z, z from noise.h (noise.vpred_step_reference restates it).
 #include "step_core.h"
+#include "noise.h"
 
 namespace {
 
@@ -37,14 +40,35 @@ struct RowsView {
     __device__ __forceinline__ void st(int64_t i, float o) const { x[i] = o; }
 };
 
+// NOISE: the presence of ONE trailing VideoNoiseArgs kernel argument (the mechanism of solver_step.hip's NoiseArgs); without it a kernel has the
+// arguments it had before the noise existed.  Element i of video s = i / per takes z of (index i % per, keys[s], step, NOISE_STREAM_VIDEO_STEP):
+// its own linear index in its video's [C][F][hw] layout under its video's key, so nothing of it depends on S, on the batch position or on the
+// grid.  prm null (dense): cz and step by value; else (plan rows) cz = prm[8], step = prm[9] of the 12 uploaded floats, so ONE captured launch
+// serves every schedule entry.
+struct VideoNoiseArgs { const uint32_t* keys; const float* prm; float cz; uint32_t step; };
+constexpr uint32_t NOISE_STREAM_VIDEO_STEP = 1u;        // noise.STREAM_VIDEO_STEP; 0 is the image sampler's step
+
 // MS: the multistep move; x0_prev [n] fp32 is then read and rewritten with this step's x0 (no other argument aliases it), and is not touched otherwise.
 // RS: element i uses the factor of its video, rs.fac[i / rs.per] (the video is the outermost index of i), for x0 AND for the DDIM move's eps; without
 // RS no factor is read and no product is formed, which is what keeps those instantiations' bits the ones they had before the rescale existed.
-template <typename View, bool MS, bool RS>
+// NzT: nothing, or {VideoNoiseArgs}: the stored value is then cz != 0 ? rnd(moved + rnd(cz * z)) : moved -- one product and one sum behind the
+// parent's operations, and no generator call at cz == 0 (rs.per is read for the video of i, so the launcher always fills it).
+template <typename View, bool MS, bool RS, typename... NzT>
 __global__ void __launch_bounds__(256)
-video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const RescaleArgs rs) {
+video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const RescaleArgs rs, const NzT... nz) {
     constexpr int DT = View::DT;
+    constexpr bool NZ = sizeof...(NzT) == 1;
+    static_assert(sizeof...(NzT) <= 1, "the trailing argument is one VideoNoiseArgs or nothing");
     const StepCoef k = vw.template coef<MS>();
+    float cz = 0.0f;
+    uint32_t step = 0;
+    const uint32_t* keys = nullptr;
+    if constexpr (NZ) {
+        const VideoNoiseArgs& a = (nz, ...);
+        cz = a.prm ? a.prm[8] : a.cz;
+        step = a.prm ? (uint32_t)a.prm[9] : a.step;
+        keys = a.keys;
+    }
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float xv = vw.xv(i);
@@ -52,19 +76,33 @@ video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const R
         if constexpr (MS) p = x0_prev[i];
         if constexpr (RS) f = rs.fac[i / rs.per];
         const VPred e = vpred_x0<DT, RS>(xv, vw.vu(i), vw.vc(i), k.g, k.sa, k.s1, f);
-        if constexpr (MS) {
-            vw.st(i, vpred_ms_move<DT>(xv, e.x0, p, k.a, k.b, k.c));
-            x0_prev[i] = e.x0;
-        } else vw.st(i, vpred_ddim_move<DT>(xv, e, k.sa, k.s1, k.a, k.b));
+        float moved;
+        if constexpr (MS) moved = vpred_ms_move<DT>(xv, e.x0, p, k.a, k.b, k.c);
+        else moved = vpred_ddim_move<DT>(xv, e, k.sa, k.s1, k.a, k.b);
+        if constexpr (NZ) {
+            if (cz != 0.0f) {
+                const int64_t s = i / rs.per;
+                const float z = noise_normal((uint64_t)(i - s * rs.per), keys[2 * s], keys[2 * s + 1], step, NOISE_STREAM_VIDEO_STEP);
+                moved = rnd<DT>(moved + rnd<DT>(cz * z));
+            }
+        }
+        vw.st(i, moved);
+        if constexpr (MS) x0_prev[i] = e.x0;
     }
 }
 
-template <bool MS, bool RS, typename View>
-int launch_video_step(const View& vw, float* x0_prev, int64_t n, const RescaleArgs& rs, hipStream_t st) {
+template <bool MS, bool RS, typename View, typename... NzT>
+int launch_video_step(const View& vw, float* x0_prev, int64_t n, const RescaleArgs& rs, hipStream_t st, const NzT&... nz) {
     int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
-    video_step_kernel<View, MS, RS><<<(unsigned)blocks, 256, 0, st>>>(vw, x0_prev, n, rs);
+    video_step_kernel<View, MS, RS, NzT...><<<(unsigned)blocks, 256, 0, st>>>(vw, x0_prev, n, rs, nz...);
     TMIX_LAUNCH_CHECK();
     return TMIX_OK;
+}
+
+// f(MS, RS as std::bool_constant) for the form a noise entry's nullable x0_prev / factors select
+template <typename F> int for_form(bool ms, bool rs, F&& f) {
+    if (ms) return rs ? f(std::true_type(), std::true_type()) : f(std::true_type(), std::false_type());
+    return rs ? f(std::false_type(), std::true_type()) : f(std::false_type(), std::false_type());
 }
 
 // the four dense entries: videos x per elements (the forms without the rescale: 1 x n, answered as "empty latent")
@@ -193,4 +231,38 @@ extern "C" int tmix_vpred_step_rs_dev(float* x, const float* v_u, int64_t clip_s
 extern "C" int tmix_vpred_step_ms_rs_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, float* x0_prev,
                                          const float* params, int videos, int channels, int frames, int64_t hw, const float* factors, void* stream) {
     return rows_step<true, true>("vpred_step_ms_rs_dev", x, v_u, clip_stride_u, v_c, clip_stride_c, x0_prev, params, videos, channels, frames, hw, factors, stream);
+}
+
+// ---- the stochastic step: ONE entry per layout for all four parents -- x0_prev null: the DDIM move, (a, b) = (sa_next, s1_dir);
+// else the multistep move (cx, c0, c1) and the history buffer; factors null: no rescale
+extern "C" int tmix_vpred_step_noise(const void* x, const void* v, void* out, float* x0_prev, int dtype, int videos, int64_t n_per_video, float g,
+                                     float sa, float s1, float a, float b, float c, float cz, const float* factors, const uint32_t* keys,
+                                     uint32_t step, void* stream) {
+    const char* me = "vpred_step_noise";
+    if (x && v && out && !keys) TMIX_FAIL(TMIX_EINVAL, "%s: null keys", me);
+    if (int rc = check_vpred_step(me, x && v && out, false, nullptr, false, nullptr, dtype, false, false, videos, 1, 1, n_per_video, n_per_video, n_per_video)) return rc;
+    const int64_t n = (int64_t)videos * n_per_video;
+    const StepCoef k = {g, sa, s1, a, b, x0_prev ? c : 0.0f};
+    const VideoNoiseArgs nz = {keys, nullptr, cz, step};
+    return for_dtype(dtype, me, "dtype", [&](auto dt) {
+        typedef typename EpsT<dt()>::T T;
+        const DenseView<dt()> vw = {(const T*)x, (const T*)v, (T*)out, n, k};
+        return for_form(x0_prev != nullptr, factors != nullptr, [&](auto ms, auto rs) {
+            return launch_video_step<ms(), rs()>(vw, x0_prev, n, RescaleArgs{factors, n_per_video}, (hipStream_t)stream, nz);
+        });
+    });
+}
+
+extern "C" int tmix_vpred_step_noise_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
+                                         const float* params, int videos, int channels, int frames, int64_t hw, float* x0_prev,
+                                         const float* factors, const uint32_t* keys, void* stream) {
+    const char* me = "vpred_step_noise_dev";
+    if (x && v_u && v_c && params && !keys) TMIX_FAIL(TMIX_EINVAL, "%s: null keys", me);
+    if (int rc = check_vpred_step(me, x && v_u && v_c && params, false, nullptr, false, nullptr, TMIX_F32, false, false, videos, channels, frames, hw, clip_stride_u, clip_stride_c)) return rc;
+    const int64_t per = (int64_t)channels * frames * hw;
+    const RowsView vw = {x, v_u, clip_stride_u, v_c, clip_stride_c, params, channels, frames, hw};
+    const VideoNoiseArgs nz = {keys, params, 0.0f, 0u};
+    return for_form(x0_prev != nullptr, factors != nullptr, [&](auto ms, auto rs) {
+        return launch_video_step<ms(), rs()>(vw, x0_prev, videos * per, RescaleArgs{factors, per}, (hipStream_t)stream, nz);
+    });
 }

@@ -14,7 +14,8 @@ U32, U64 = np.uint32, np.uint64
 
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
-STREAM_IMAGE_STEP = 0           # stream id of the image sampler's step; every other value is reserved
+STREAM_IMAGE_STEP = 0           # stream id of the image sampler's step
+STREAM_VIDEO_STEP = 1           # of the video sampler's step: the same seed draws unrelated noise there; every other value is reserved
 
 # the constants of csrc/noise.h, value for value
 SQRT2 = F32(1.41421354)
@@ -125,4 +126,46 @@ def step_reference(mode, x, eps, masks, x0_prev, params, key, factors=None, inde
         idx = np.arange(x.size, dtype=U64).reshape(x.shape) if index is None else np.asarray(index, U64).reshape(x.shape)
         z = normal(idx, key[0], key[1], int(p[9]))
         moved = (moved + (F32(p[8]) * z).astype(F32)).astype(F32)
+    return moved, x0
+
+
+def vpred_step_reference(x, v, x0_prev, params_or_coeffs, keys, step=None, factors=None, lowp=None):
+    """numpy restatement of tmix_vpred_step_noise and tmix_vpred_step_noise_dev -> (out, x0).  x [B, ...], v [2B, ...] (uncond rows
+    first) fp32 copies of values of the model dtype; x0_prev None: the DDIM move, else the fp32 history [B, ...] and the multistep move.
+    params_or_coeffs: the 12 floats the _dev entry reads -- the parent's 8 ({t, sa, s1, sa_next, s1_dir, g, 0, 0} when x0_prev is None, else
+    {t, sa, s1, cx, c0, c1, g, 0}), then {cz, step index, 0, 0} -- or the dense entry's seven coefficients (g, sa, s1, a, b, c, cz) with
+    (a, b) = (sa_next, s1_dir) or (a, b, c) = (cx, c0, c1).  keys [B] of (low word, high word); step: the schedule index (None: params[9]);
+    factors [B] or None; lowp as in guidance.vpred_rescaled_step_reference (None, np.float16, "bf16").  The parent's restatement
+    (guidance.vpred_rescaled_step_reference / vpred_rescaled_multistep_reference; a factor of 1.0 gives the unscaled parent bit for bit) forms
+    x0 and moved; then one product and one sum add cz * z, z = normal(the element's linear index in its video, the video's key, step,
+    STREAM_VIDEO_STEP), with the dtype's rounding points: fp16 rounds the product and the sum, bf16 the stored value alone.  Compared with
+    both kernels by equality."""
+    from . import guidance as G
+    from . import solver as SV
+    x = np.asarray(x, F32)
+    p = [float(F32(c)) for c in params_or_coeffs]
+    if len(p) == 12:
+        g, sa, s1, a, b, c = (p[5], p[1], p[2], p[3], p[4], 0.0) if x0_prev is None else (p[6], p[1], p[2], p[3], p[4], p[5])
+        cz, step = p[8], int(p[9]) if step is None else int(step)
+    elif len(p) == 7:
+        g, sa, s1, a, b, c, cz = p
+        step = int(step)
+    else:
+        raise ValueError(f"vpred_step_reference: {len(p)} values (12 device parameters or the 7 coefficients g, sa, s1, a, b, c, cz)")
+    B = x.shape[0]
+    if len(keys) != B:
+        raise ValueError(f"vpred_step_reference: {len(keys)} keys for {B} videos")
+    f = np.ones(B, F32) if factors is None else np.asarray(factors, F32).reshape(B)
+    bf16 = isinstance(lowp, str) and lowp == "bf16"
+    lp = None if bf16 else lowp                      # bf16: fp32 arithmetic, ONE rounding at the store -- behind the noise
+    if x0_prev is None:
+        moved, x0 = G.vpred_rescaled_step_reference(x, v, f, g, sa, s1, a, b, lp)
+    else:
+        moved, x0 = G.vpred_rescaled_multistep_reference(x, v, x0_prev, f, g, sa, s1, a, b, c, lp)
+    if cz != 0.0:
+        idx = np.arange(x[0].size, dtype=U64).reshape(x[0].shape)
+        z = np.stack([normal(idx, k[0], k[1], step, STREAM_VIDEO_STEP) for k in keys])
+        moved = SV._h((moved + SV._h((F32(cz) * z).astype(F32), lp)).astype(F32), lp).astype(F32)
+    if bf16:
+        moved = SV._bf16_round(moved)
     return moved, x0

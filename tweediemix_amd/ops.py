@@ -1050,6 +1050,55 @@ def vpred_step_rs_dev(x, v_u, v_c, params, factors, x0_prev=None, clip_stride_u=
     return _vpred_rows(x, v_u, v_c, params, x0_prev, factors, clip_stride_u, clip_stride_c)
 
 
+def _video_keys(keys, videos):
+    assert keys.is_cuda and keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() == 2 * videos, (tuple(keys.shape), videos)
+    return _p(keys)
+
+
+def vpred_step_noise(x, v, g, at, move, cz, keys, step, x0_prev=None, factors=None, out=None):
+    """tmix_vpred_step_noise: the stochastic form of vpred_step / vpred_step_rs (x0_prev None; move = (sa_next, s1_dir), the third
+    and fourth value of solver.ddim_eta_coeffs) and of vpred_step_ms / vpred_step_ms_rs (x0_prev the history buffer; move = (cx, c0, c1) of
+    solver.video_multistep_eta_coeffs); cz is the last value of either.  x [B,...], v [2B,...] of one dtype, factors [B] or None, keys int32 [B, 2]
+    (noise_keys), step the schedule index.  out may be x.  noise.vpred_step_reference gives the same bits.  Returns the next latents."""
+    _need_cuda(x, v, x0_prev, factors, keys)
+    assert x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
+    out = torch.empty_like(x) if out is None else out
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    sa, s1 = step_coeffs(at, at)[:2]
+    B = x.shape[0]
+    a, b, c = (float(m) for m in (tuple(move) + (0.0,))[:3])
+    prev = None if x0_prev is None else _history(x0_prev, x)
+    fac = None if factors is None else _video_factors(factors, B)
+    assert 0 <= int(step) < 2 ** 32, step
+    L.check(L.load().tmix_vpred_step_noise(_p(x), _p(v), _p(out), prev, _EPS_DT[x.dtype], B, x.numel() // B, float(g), sa, s1, a, b, c, float(cz),
+                                           fac, _video_keys(keys, B), int(step), _stream()), "tmix_vpred_step_noise")
+    return out
+
+
+def vpred_step_noise_dev(x, v_u, v_c, params, keys, x0_prev=None, factors=None, clip_stride_u=None, clip_stride_c=None):
+    """tmix_vpred_step_noise_dev: the stochastic form of vpred_step_dev / vpred_step_rs_dev (x0_prev None) and of vpred_step_ms_dev / its rescale
+    form (x0_prev the history buffer), factors [S] or None, keys int32 [S, 2] (noise_keys); params holds 12 floats (video_step_params_noise).
+    In place on x [S,C,F,h,w] fp32; returns x."""
+    _need_cuda(x, v_u, v_c, params, x0_prev, factors, keys)
+    S, Cc, Fr, hw, su, sc = _plan_rows(x, v_u, v_c, x.shape[1], clip_stride_u, clip_stride_c)
+    assert params.dtype == torch.float32 and params.numel() >= 12, params.numel()
+    prev = None if x0_prev is None else _history(x0_prev, x)
+    fac = None if factors is None else _video_factors(factors, S)
+    L.check(L.load().tmix_vpred_step_noise_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(params), S, Cc, Fr, hw, prev, fac, _video_keys(keys, S), _stream()),
+            "tmix_vpred_step_noise_dev")
+    return x
+
+
+def video_step_params_noise(t, g, at, coeffs_or_next, cz, step_index, out=None):
+    """the 12 floats tmix_vpred_step_noise_dev reads: the parent's 8, then {cz, step_index, 0, 0}.  coeffs_or_next: (sa_next, s1_dir) -- the DDIM
+    layout {t, sa, s1, sa_next, s1_dir, g, 0, 0} -- or (cx, c0, c1) -- the solver's {t, sa, s1, cx, c0, c1, g, 0}; sa, s1 as vpred_step forms them."""
+    m = [float(np.float32(c)) for c in coeffs_or_next]
+    assert len(m) in (2, 3), m
+    assert 0 <= int(step_index) < 2 ** 24, step_index            # exact in fp32
+    head = [float(t), *step_coeffs(at, at)[:2], *m, float(g)] + [0.0] * (4 - len(m))
+    return _fill_params(head + [float(np.float32(cz)), float(int(step_index)), 0.0, 0.0], out)
+
+
 def frame_inject(x, clips, frames, interp=None):
     """first-frame feature injection (video_gen/utils_attn.py:433-455), in place on x [(clips*frames), ...] contiguous."""
     _need_cuda(x)

@@ -167,6 +167,16 @@ def video_multistep_coeffs(t, a_prev, a, a_next, second_order):
     return multistep_coeffs(a_prev, a, a_next, second_order)
 
 
+def video_multistep_eta_coeffs(t, a_prev, a, a_next, second_order, eta):
+    """(cx, c0, c1, cz) of the stochastic video step: multistep_eta_coeffs on video_multistep_coeffs' edge cases -- a_next == 1 is
+    (0, 1, 0) with cz = 0 (the step lands on the data; there is no noise level left to add at), a == 0 is refused.  eta == 0: video_multistep_coeffs'
+    three values bit for bit and cz == 0.0"""
+    cx, c0, c1 = video_multistep_coeffs(t, a_prev, a, a_next, second_order)
+    if eta == 0.0 or float(F32(a_next)) >= 1.0:
+        return cx, c0, c1, 0.0
+    return multistep_eta_coeffs(a_prev, a, a_next, second_order, eta)
+
+
 def _bf16_round(a):
     """fp32 -> the nearest bf16 value (ties to even), as fp32: the one rounding of a TMIX_BF16 store"""
     u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)

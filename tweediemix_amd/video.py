@@ -94,7 +94,8 @@ class VideoSchedule:
 class SolverPhase:
     """the host's bookkeeping of solver="dpmpp2m": coeffs(t) -> the (cx, c0, c1) of the step at t and remembers it.  A step is second order
     exactly when the previous coeffs() call was for the preceding schedule entry, first order otherwise (the first step, any out-of-order or
-    off-grid call); the injection state does not enter."""
+    off-grid call); the injection state does not enter.  coeffs(t, eta) -> (cx, c0, c1, cz) of the SDE form of the same step
+    (solver.video_multistep_eta_coeffs; eta = 0.0 gives coeffs(t)'s three values bit for bit and cz == 0.0), with the same bookkeeping."""
 
     def __init__(self, schedule: VideoSchedule):
         self.schedule, self.prev = schedule, None
@@ -104,14 +105,15 @@ class SolverPhase:
         For callers that put a state and a history in place themselves (tools/video_solver_cost.py times a second-order step this way)."""
         self.prev = None if t is None else self.schedule.index(t)
 
-    def coeffs(self, t: int):
-        from .solver import video_multistep_coeffs
+    def coeffs(self, t: int, eta=None):
+        from .solver import video_multistep_coeffs, video_multistep_eta_coeffs
         sch, t = self.schedule, int(t)
         i = sch.index(t)
         second = i is not None and i > 0 and self.prev == i - 1
         self.prev = None                                   # a refused step leaves no history behind
         a = sch.alpha(t) if 0 <= t < len(sch.acp) else 0.0
-        out = video_multistep_coeffs(t, sch.alpha(int(sch.timesteps[i - 1])) if second else None, a, sch.next_alpha(t) if float(a) > 0 else 0.0, second)
+        a_prev, a_next = sch.alpha(int(sch.timesteps[i - 1])) if second else None, sch.next_alpha(t) if float(a) > 0 else 0.0
+        out = video_multistep_coeffs(t, a_prev, a, a_next, second) if eta is None else video_multistep_eta_coeffs(t, a_prev, a, a_next, second, eta)
         self.prev = i
         return out
 
@@ -177,18 +179,50 @@ def _check_solver(solver):
     return solver != "ddim"
 
 
+def _check_eta(eta, noise_seeds, videos):
+    """eta in [0, 1] and, for eta > 0, one integer noise seed per video -> (eta, seeds or None); host only"""
+    from .solver import validate_eta
+    eta = validate_eta(eta)
+    if noise_seeds is None:
+        if eta > 0.0:
+            raise ValueError(f"eta={eta}: noise_seeds (one integer per video) are what the step's noise is a function of")
+        return eta, None
+    seeds = [int(s) for s in noise_seeds]
+    if len(seeds) != int(videos):
+        raise ValueError(f"noise_seeds: {len(seeds)} values for {int(videos)} videos")
+    return eta, seeds
+
+
+def _noise_step(schedule, t, eta, phase):
+    """the stochastic step at timestep t (eta > 0) -> (move, cz, schedule index): move = (cx, c0, c1) of the SDE solver step when `phase` is the
+    solver's bookkeeping, else the DDIM step's (sa_next, s1_dir).  The noise is indexed by the schedule entry, so t must be on the grid."""
+    from .solver import ddim_eta_coeffs
+    i = schedule.index(t)
+    if i is None:
+        raise ValueError(f"eta={eta}: t = {int(t)} is not one of the schedule's timesteps (the noise is indexed by the schedule entry)")
+    if phase is not None:
+        cx, c0, c1, cz = phase.coeffs(int(t), eta)
+        return (cx, c0, c1), cz, i
+    _, _, san, s1d, cz = ddim_eta_coeffs(schedule.alpha(int(t)), schedule.next_alpha(int(t)), eta)
+    return (san, s1d), cz, i
+
+
 @torch.no_grad()
 def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None,
-                solver: str = "ddim", guidance_rescale: float = 0.0):
+                solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None):
     """pipeline_i2vgen_xl.py:680-719.  unet(latent_model_input [2B,C,F,H,W], t) -> v-prediction of the same shape (the
     caller closes over prompt/image conditioning; an i2vgen plan behind it needs its `inject` flag set for t, from
     injection_active); latents [B,C,F,H,W] on the GPU in the model dtype.  solver="dpmpp2m": every step is tmix_vpred_step_ms on the
     model dtype with an fp32 history of x0.  guidance_rescale = phi > 0: every step is tmix_vpred_rescale_factors on
-    v (one factor per video, g read from a small device tensor) and then the _rs form of the step entry; 0 is the loop without it, launch for launch."""
+    v (one factor per video, g read from a small device tensor) and then the _rs form of the step entry; 0 is the loop without it, launch for launch.
+    eta > 0 with noise_seeds, one integer per video: every step is tmix_vpred_step_noise, the same move plus cz * z with z a
+    function of (the video's seed, the schedule index, the element's index in its video); 0 is the loop without it, launch for launch."""
     from .guidance import validate_phi
     ms = _check_solver(solver)
     phi = validate_phi(guidance_rescale)
+    eta, seeds = _check_eta(eta, noise_seeds, latents.shape[0])
     x = latents.contiguous()
+    keys = ops.noise_keys(seeds, x.device) if eta > 0.0 else None
     if ms:
         phase, hist = SolverPhase(schedule), torch.zeros_like(x, dtype=torch.float32)
     if phi > 0.0:
@@ -202,6 +236,11 @@ def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_s
         v = unet(torch.cat([x, x]), int(t)).contiguous()
         if phi > 0.0:
             ops.vpred_rescale_factors(v, g_dev, 0, phi, out=fac, ws=ws)
+        if eta > 0.0:
+            move, cz, i = _noise_step(schedule, int(t), eta, phase if ms else None)
+            x = ops.vpred_step_noise(x, v, guidance_scale, schedule.alpha(int(t)), move, cz, keys, i, x0_prev=hist if ms else None,
+                                     factors=fac if phi > 0.0 else None)
+        elif phi > 0.0:
             if ms:
                 x = ops.vpred_step_ms_rs(x, v, guidance_scale, schedule.alpha(int(t)), phase.coeffs(int(t)), hist, fac)
             else:
@@ -230,19 +269,34 @@ class VideoSampler:
     into `rs_factors` [S], g read on the device from params) and the _rs_dev form of whichever step entry runs; the graphs are keyed (inject, "rs")
     and (inject, "ms", "rs"); phi is a launch argument fixed at capture, so a step stays one 32-byte upload and one replay.  The statistics'
     partition per video does not depend on S: video s of a batch is still bit for bit its single run.  phi = 0 is the sampler without it: no new
-    launch, buffer or graph key."""
+    launch, buffer or graph key.
+
+    eta > 0 with noise_seeds, one integer per video: the step ends in tmix_vpred_step_noise_dev, the stochastic form of whichever
+    of the four entries above would run; params and the staging slots are then 12 floats (the parent's 8, then {cz, schedule index, 0, 0}), the
+    graphs carry a trailing "eta" in their keys -- (inject, "eta"), (inject, "ms", "eta"), (inject, "rs", "eta"), (inject, "ms", "rs", "eta") --
+    and a step stays one (48-byte) upload and one replay.  `noise_keys` int32 [S, 2] holds the videos' key words at a fixed address and is
+    written once per sample(); set_noise_seeds replaces the seeds between runs.  A video's noise is a function of its own seed, the schedule
+    index and the element's index in the video: video s of a batch is still bit for bit its single run.  eta = 0 is the sampler without it: no
+    new launch, buffer, graph key or upload size."""
 
     def __init__(self, plan, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None, use_graphs: bool = True,
-                 solver: str = "ddim", guidance_rescale: float = 0.0):
+                 solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None):
         from .guidance import validate_phi
         self.plan, self.schedule, self.g, self.injector, self.use_graphs = plan, schedule, float(guidance_scale), injector, use_graphs
         self.solver, self.ms = solver, _check_solver(solver)
         self.guidance_rescale = validate_phi(guidance_rescale)
+        self.eta, self._noise_seeds = _check_eta(eta, noise_seeds, plan.videos)          # host only: refused before the GPU is touched
         cfg = plan.cfg
         dev = plan.plans[0].dev
         self.state = torch.zeros(plan.videos, cfg.in_channels, plan.frames, plan.h, plan.w, device=dev, dtype=torch.float32)
-        self.params = torch.zeros(8, device=dev, dtype=torch.float32)           # {t, sa, s1, sa_next, s1_next, g, -, -}; solver: {t, sa, s1, cx, c0, c1, g, -}
-        self._ring = ParamRing()                          # staging for the asynchronous parameter upload (as the image sampler's step_params)
+        # {t, sa, s1, sa_next, s1_next, g, -, -}; solver: {t, sa, s1, cx, c0, c1, g, -}; eta > 0: four more floats {cz, schedule index, 0, 0}
+        self.params = torch.zeros(12 if self.eta > 0.0 else 8, device=dev, dtype=torch.float32)
+        # staging for the asynchronous parameter upload (as the image sampler's step_params)
+        self._ring = ParamRing(width=12) if self.eta > 0.0 else ParamRing()
+        self.noise_keys = self._keys_stale = None
+        if self.eta > 0.0:                                # int32 [S, 2]: every video's key words at an address the captured steps keep
+            self.noise_keys = torch.zeros(plan.videos, 2, device=dev, dtype=torch.int32)
+            self._keys_stale = True
         self.graphs = {}
         self.x0_prev = torch.zeros_like(self.state) if self.ms else None
         self.phase = SolverPhase(schedule) if self.ms else None
@@ -251,6 +305,17 @@ class VideoSampler:
             self.rs_factors = torch.ones(plan.videos, device=dev, dtype=torch.float32)
             self._rs_ws = ops.vpred_rescale_ws(plan.videos, dev)
 
+    def set_noise_seeds(self, seeds):
+        """the integer seed of every video's step noise (eta > 0) for the runs that follow: the next sample() (or step()) writes the key words
+        into `noise_keys`, whose address the captured steps keep"""
+        _, self._noise_seeds = _check_eta(self.eta, seeds, self.plan.videos)
+        if self.eta > 0.0:
+            self._keys_stale = True
+
+    def _write_keys(self):
+        self.noise_keys.copy_(ops.noise_keys(self._noise_seeds, self.noise_keys.device))
+        self._keys_stale = False
+
     def _enqueue(self):
         (xu, tu, eu), (xc, tc, ec) = self.plan.halves
         ops.video_step_prologue(self.state, xu, tu, xc, tc, self.params)
@@ -258,6 +323,9 @@ class VideoSampler:
         if self.guidance_rescale > 0.0:
             ops.vpred_rescale_factors_dev(eu, ec, self.state.shape[0], self.state[0].numel(), self.params, 6 if self.ms else 5,
                                           self.guidance_rescale, out=self.rs_factors, ws=self._rs_ws)
+        if self.eta > 0.0:
+            ops.vpred_step_noise_dev(self.state, eu, ec, self.params, self.noise_keys, x0_prev=self.x0_prev, factors=self.rs_factors)
+        elif self.guidance_rescale > 0.0:
             ops.vpred_step_rs_dev(self.state, eu, ec, self.params, self.rs_factors, x0_prev=self.x0_prev)
         elif self.ms:
             ops.vpred_step_ms_dev(self.state, eu, ec, self.x0_prev, self.params)
@@ -266,6 +334,11 @@ class VideoSampler:
 
     def _upload(self, t):
         sch = self.schedule
+        if self.eta > 0.0:
+            move, cz, i = _noise_step(sch, t, self.eta, self.phase)          # first: a refused step rewrites no staging slot
+            ops.video_step_params_noise(t, self.g, sch.alpha(int(t)), move, cz, i, out=self._ring.next())
+            self._ring.upload(self.params)
+            return
         coeffs = self.phase.coeffs(t) if self.ms else None          # first: a refused step rewrites no staging slot
         hp = self._ring.next()
         if self.ms:
@@ -280,6 +353,8 @@ class VideoSampler:
             self.injector.register_time(t)
             inject = injection_active(int(t), self.injector.schedule)
             self.plan.inject, self.plan.interp = inject, self.injector.interp
+        if self._keys_stale:                              # a step() outside sample() after new seeds
+            self._write_keys()
         self._upload(t)
         if not self.use_graphs:
             self._enqueue()
@@ -287,6 +362,8 @@ class VideoSampler:
         key = (inject, "ms") if self.ms else inject
         if self.guidance_rescale > 0.0:
             key = (key if self.ms else (inject,)) + ("rs",)
+        if self.eta > 0.0:
+            key = (key if isinstance(key, tuple) else (inject,)) + ("eta",)
         g = self.graphs.get(key)
         if g is None:
             self._enqueue()                               # warm-up outside capture; it has already performed this step
@@ -307,6 +384,8 @@ class VideoSampler:
     def sample(self, latents: torch.Tensor) -> torch.Tensor:
         """latents [S,4,F,h,w] -> the final latents (a copy of the state)."""
         self.state.copy_(latents)
+        if self.eta > 0.0:
+            self._write_keys()
         for t in self.schedule.timesteps:
             self.step(int(t))
         return self.state.clone()
