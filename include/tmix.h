@@ -148,7 +148,7 @@ int tmix_fused_tweedie_step_ms_rs_dev(const float* x, const void* eps, int eps_d
  * word, index high word, step, stream_id}, then Box-Muller on output words 0 and 1:
  *   u1 = ((w0 >> 9) + 0.5) * 2^-23        angle = 2 pi ((w1 >> 9) + 0.5) * 2^-23        z = sqrt(-2 ln u1) cos(angle),   |z| < 5.8
  * with ln, sin and cos written out in integer operations and single-rounded fp32 add, sub, mul, div and sqrt (csrc/noise.h), so that
- * noise.normal (numpy) gives the same bits.  stream_id 0 is the image sampler's step, 1 the video sampler's; other values are reserved.
+ * noise.normal (numpy) gives the same bits.  stream_id 0 is the image sampler's step, 1 the video sampler's, 2 the fixed noise of its hold regions (7p); other values are reserved.
  * tmix_noise_normal: the generator on its own: z[i] = the normal of index first_index + i, i < n.  TMIX_EINVAL: null z.  TMIX_ESHAPE: n < 1,
  * first_index < 0.
  * tmix_fused_tweedie_step_noise_dev: ONE entry for the stochastic form of tmix_fused_tweedie_step_dev / _rs_dev / _ms_dev / _ms_rs_dev.  The
@@ -326,6 +326,39 @@ int tmix_vpred_step_noise(const void* x, const void* v, void* out, float* x0_pre
 int tmix_vpred_step_noise_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, const float* params,
                               int videos, int channels, int frames, int64_t hw, float* x0_prev, const float* factors, const uint32_t* keys,
                               void* stream);
+/* HOLD REGIONS IN THE VIDEO STEP (no reference counterpart): part of every frame is held at a clean latent while the rest is sampled.
+ * For element i = (video s, channel c, frame f, pixel p) of the state [videos][channels][frames][hw]:
+ *   kx    hold_x0 [videos or 1][channels][hold_x0_frames][hw] fp32, the clean latent to hold; hold_x0_frames 1: one image for every frame, `frames`:
+ *         a whole clip; video s starts at s * hold_x0_video_stride floats (0: one array for every video)
+ *   w     hold_w [videos or 1][hold_w_frames][hw] fp32 in [0, 1], 1 = held, 0 = sampled, the same for every channel; strides and frames as above
+ *   zh    the normal of (index i % (channels frames hw), key {keys[s][0], keys[s][1]}, step 0, stream_id 2): ONE fixed noise per element at every
+ *         noise level, so the held part walks the deterministic path sa_t kx + s1_t zh
+ *   ha, hs  sqrt(alpha), sqrt(1 - alpha) of the state the step WRITES; (1, 0) on the last step of a schedule
+ *   moved what tmix_vpred_step_noise[_dev] stores for the element (x0, the history write and the rescale statistics are the parent's, over the
+ *         whole video, held region included)
+ *   kept = hs != 0 ? rnd(rnd(ha * kx) + rnd(hs * zh)) : kx            hs == 0: no generator call, no product, kx with its sign bit
+ *   out  = w == 0 ? moved : w == 1 ? kept : rnd(rnd(w * kept) + rnd(rnd(1 - w) * moved))
+ * w == 0 leaves the noise entry's bits, w == 1 does not depend on the prediction (a NaN in v stays out of a held pixel).  Nothing is contracted.
+ * tmix_vpred_step_hold: the dense form: tmix_vpred_step_noise with (videos, channels, frames, hw) in place of (videos, n_per_video), ha and hs by
+ *   value behind `step`, then the hold arrays.
+ * tmix_vpred_step_hold_dev: the form on plan rows: the arguments of tmix_vpred_step_noise_dev, then the hold arrays.  params holds 12 floats: the
+ *   noise entry's {.., cz, step_index} with {ha, hs} in slots 10 and 11.
+ * tmix_video_hold_composite: the blend alone, in place on x of `dtype` with moved = x: x_T once, at the first timestep's (ha, hs).
+ * All three: the parent's answers first (TMIX_EINVAL on a null x, v / v_u, v_c, out / params, on null keys; TMIX_ESHAPE on a bad shape or clip stride;
+ * TMIX_EINVAL on a bad dtype), then TMIX_EINVAL on a null hold_x0 / hold_w, TMIX_ESHAPE on hold_x0_frames / hold_w_frames not in {1, frames} and on
+ * a video stride that is neither 0 nor at least one video's extent (channels * hold_x0_frames * hw, hold_w_frames * hw); all before any launch; one
+ * launch on `stream`, capturable; no workspace. */
+int tmix_vpred_step_hold(const void* x, const void* v, void* out, float* x0_prev, int dtype, int videos, int channels, int frames, int64_t hw,
+                         float g, float sa, float s1, float a, float b, float c, float cz, const float* factors, const uint32_t* keys,
+                         uint32_t step, float ha, float hs, const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames,
+                         const float* hold_w, int64_t hold_w_video_stride, int hold_w_frames, void* stream);
+int tmix_vpred_step_hold_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c, const float* params,
+                             int videos, int channels, int frames, int64_t hw, float* x0_prev, const float* factors, const uint32_t* keys,
+                             const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames, const float* hold_w,
+                             int64_t hold_w_video_stride, int hold_w_frames, void* stream);
+int tmix_video_hold_composite(void* x, int dtype, int videos, int channels, int frames, int64_t hw, float ha, float hs, const uint32_t* keys,
+                              const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames, const float* hold_w,
+                              int64_t hold_w_video_stride, int hold_w_frames, void* stream);
 /* First-frame feature injection of the patched ResnetBlock2D.forward (video_gen/utils_attn.py:433-455), in place on
  * x [clips][frames][per_frame]: frames 1.. <- frame 0 (hard) or interp*frame0 + one_minus_interp*frame. */
 int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,

@@ -44,7 +44,23 @@ Stochastic sampling (no reference counterpart: the reference hands `eta` to its 
                             step, the element's index in the video): the same bits alone, co-batched, on another GPU, eagerly or from a graph.
                             --solver ddim: the DDIM paper's eta; --solver dpmpp2m: SDE-DPM-Solver++(2M) in k-diffusion's eta form, the variant
                             meant for few steps (`--solver dpmpp2m --timestep_spacing logsnr --eta 1`); the two coincide at 0 and 1.  Combines
-                            with every flag above; a value outside [0, 1] is refused before the GPU is touched and before any rank starts."""
+                            with every flag above; a value outside [0, 1] is refused before the GPU is touched and before any rank starts.
+
+Hold regions (no reference counterpart: the reference's only controls are --injection_timestep and --interp_ratio):
+  --hold_masks a.png+b.png  white is HELD: in every frame the union of the masks stays at the held picture while the rest is sampled ("animate
+                            the dog, leave the cat and the mountains as they are").  The masks go to the latent grid like the image CLI's; the
+                            `<seg_concept>.jpg` files an image run leaves in its side-car directory work as they are.
+  --animate_masks a.png+b.png  white MOVES: the complement of the union is held.  One of the two flags at most.
+  --hold_feather PX / --hold_dilate PX  ramp width around, and growth of (negative: shrinking), the white region, in image pixels (divided by 8 for
+                            the latent grid; the distance-transform kernels of the image CLI's soft masks).  They need one of the mask flags.
+  --hold_latents FILE       what is held: by default frame 0 of the video's own conditional image latents -- what the UNet is conditioned on --
+                            in every frame; FILE is the `[1,4,F,h,w]` '.latent.pt' of an earlier run, held frame by frame: re-roll one region of a
+                            finished clip.  Needs one of the mask flags.
+                            The held part is x0 at the noise level of every state under one fixed noise keyed by the video's seed
+                            (tmix_video_hold_composite once on x_T, then tmix_vpred_step_hold_dev); the final latent equals the held latent bit
+                            for bit wherever the weight is 1.  Rank 0 writes the weight it used as <stem>_hold.png.  Combines with every flag
+                            above and --num_seeds N; one mask set describes one image, so several images are refused, like every misuse above,
+                            before the GPU is touched and before any rank starts."""
 import argparse
 import os
 import sys
@@ -96,6 +112,13 @@ def build_parser():
     # stochastic sampling; 0 is the run without it
     p.add_argument("--eta", type=float, default=0.0, help="in [0, 1]: every step adds noise computed inside the step kernel from (the video's seed, the "
                    "schedule step, the element's index); ddim: the DDIM paper's eta, dpmpp2m: SDE-DPM-Solver++(2M)'s; 0: off")
+    # hold regions; without a mask flag the run has none
+    p.add_argument("--hold_masks", default="", help="'+'-separated mask images: white is held at the picture in every frame, the rest is sampled")
+    p.add_argument("--animate_masks", default="", help="'+'-separated mask images: white is sampled, the rest is held (not with --hold_masks)")
+    p.add_argument("--hold_feather", type=float, default=0.0, help="ramp width in image pixels around the white region of the mask flag")
+    p.add_argument("--hold_dilate", type=float, default=0.0, help="grow the white region of the mask flag by this many image pixels (negative: shrink)")
+    p.add_argument("--hold_latents", default="", help="'.latent.pt' [1,4,F,h,w] of an earlier run, held frame by frame (default: frame 0 of the "
+                   "video's conditional image latents in every frame)")
     return p
 
 
@@ -152,6 +175,50 @@ def checked_eta(opt):
         return validate_eta(opt.eta, "--eta")
     except ValueError as e:
         raise SystemExit(str(e))
+
+
+def checked_hold(opt, images):
+    """the hold flags, on the host before anything touches the GPU or any rank is started -> None (no hold) or dict(masks=[paths], animate=bool,
+    soft=(feather, dilate) in latent pixels or None, latents=[1,4,F,h,w] fp32 or None)"""
+    flags = [("--hold_feather", opt.hold_feather), ("--hold_dilate", opt.hold_dilate), ("--hold_latents", opt.hold_latents)]
+    if opt.hold_masks and opt.animate_masks:
+        raise SystemExit("--hold_masks (white is held) and --animate_masks (white moves) describe the same region twice: give one of them")
+    spec = opt.hold_masks or opt.animate_masks
+    if not spec:
+        used = [f"{f} {v}" for f, v in flags if v]
+        if used:
+            raise SystemExit(f"{' / '.join(used)}: a hold needs its region: --hold_masks or --animate_masks")
+        return None
+    if len(images) > 1:
+        raise SystemExit(f"--hold_masks / --animate_masks: one mask set describes ONE image; this run has {len(images)} (--num_seeds N is fine)")
+    paths = [m for m in spec.split("+") if m]
+    for m in paths:
+        if not os.path.isfile(m):
+            raise SystemExit(f"{'--hold_masks' if opt.hold_masks else '--animate_masks'}: no mask file {m!r}")
+    if not np.isfinite(opt.hold_feather) or opt.hold_feather < 0.0 or not np.isfinite(opt.hold_dilate):
+        raise SystemExit(f"--hold_feather {opt.hold_feather} / --hold_dilate {opt.hold_dilate}: a width >= 0 and a finite distance, in image pixels")
+    lat = None
+    if opt.hold_latents:
+        want = (1, 4, opt.num_frames, opt.height // 8, opt.width // 8)
+        if not os.path.isfile(opt.hold_latents):
+            raise SystemExit(f"--hold_latents: no file {opt.hold_latents!r}")
+        lat = torch.load(opt.hold_latents, map_location="cpu")
+        if not torch.is_tensor(lat) or tuple(lat.shape) != want:
+            raise SystemExit(f"--hold_latents {opt.hold_latents!r}: {tuple(lat.shape) if torch.is_tensor(lat) else type(lat).__name__}; this run "
+                             f"holds a latent of shape {want}")
+        lat = lat.float().contiguous()
+    soft = (opt.hold_feather / 8.0, opt.hold_dilate / 8.0) if (opt.hold_feather or opt.hold_dilate) else None
+    return dict(masks=paths, animate=bool(opt.animate_masks), soft=soft, latents=lat)
+
+
+def hold_weight(hold, h, w, device):
+    """the weight of the held part [1,1,h,w] fp32 on `device` (1 = held): the union of the masks on the latent grid (masks.build_masks, as the
+    image CLI's), softened (masks.soft_region), and its complement under --animate_masks"""
+    from tweediemix_amd import masks as M
+    white = M.build_masks(hold["masks"], h, w, device)[:-1].sum(dim=0, keepdim=True).clamp(max=1.0)
+    if hold["soft"] is not None:
+        white = M.soft_region(white, hold["soft"][0], hold["soft"][1], device=device)
+    return ((1.0 - white) if hold["animate"] else white).clamp(0.0, 1.0).contiguous()
 
 
 def batch_noise_seeds(seeds, n_real):
@@ -286,6 +353,7 @@ def main(argv=None):
     images, videos = check_args(opt)
     phi = checked_rescale(opt)
     eta = checked_eta(opt)
+    hold = checked_hold(opt, images)
     from tweediemix_amd import dist as D, i2vgen as I, launch as LA, video as V
     few_step = (opt.solver, opt.timestep_spacing) != ("ddim", "leading")
     if opt.gpus > 1 and not LA.launched():
@@ -336,6 +404,7 @@ def main(argv=None):
     if sch is None:
         sch = video_schedule(opt)                                        # the defaults: built here, as always
     per = opt.seeds_per_batch or min(max(len(mine), 1), 4)
+    hold_w = hold_weight(hold, h, w, dev) if hold is not None and (mine or rank == 0) else None
     lats = []
     smp = plan = None
     for batch, n_real in padded_batches(list(range(len(mine))), per):
@@ -346,8 +415,12 @@ def main(argv=None):
         smp = plan = None                                            # the previous batch's plan and graphs go before the next are built
         plan = I.I2VVideoPlan(Wt, S, Fr, h, w, fe, ctx, ilf, streams=opt.streams, interp=opt.interp_ratio)
         inj = V.FeatureInjector(sch.injection_schedule(opt.injection_timestep), opt.interp_ratio, clips=2 * S, frames=Fr)
-        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs, solver=opt.solver, guidance_rescale=phi,
-                             eta=eta, noise_seeds=batch_noise_seeds([mine[i][1] for i in batch], n_real) if eta > 0.0 else None)
+        held = None
+        if hold is not None:                                         # frame 0 of every video's own conditional image latents, or the given clip
+            kx = hold["latents"] if hold["latents"] is not None else torch.cat([conds[i]["image_latents"][1:2, :, 0:1] for i in batch])
+            held = (kx.float().contiguous(), hold_w)
+        smp = V.VideoSampler(plan, sch, opt.guidance_scale, inj, use_graphs=not opt.no_graphs, solver=opt.solver, guidance_rescale=phi, eta=eta,
+                             noise_seeds=batch_noise_seeds([mine[i][1] for i in batch], n_real) if eta > 0.0 or hold is not None else None, hold=held)
         lats.append(smp.sample(torch.cat([xs[i] for i in batch]).to(dev))[:n_real])
     smp = plan = None
     lat = torch.cat(lats) if lats else torch.zeros(0, 4, Fr, h, w, device=dev)
@@ -372,6 +445,10 @@ def main(argv=None):
             if img is not None:
                 save_gif(img[i], stem + ".gif", opt.target_fps)
                 print("saved", stem + ".gif")
+            if hold_w is not None:                                   # the weight this run held with, on the latent grid
+                from PIL import Image
+                Image.fromarray((hold_w[0, 0].cpu().numpy() * 255.0).round().astype("uint8")).save(stem + "_hold.png")
+                print("saved", stem + "_hold.png")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -3,7 +3,8 @@
 // from every launch shape.  One call per element wastes two of the four words on purpose: packing four elements into a call would tie an
 // element's noise to the alignment of the window it is computed in.
 // Stream ids: 0 the image sampler's step (STREAM_IMAGE_STEP in noise.py), 1 the video sampler's step (STREAM_VIDEO_STEP): an image
-// run and a video run from one seed draw unrelated noise.  Every other value is reserved.
+// run and a video run from one seed draw unrelated noise; 2 the one fixed noise of the video sampler's hold regions (STREAM_VIDEO_HOLD, DESIGN.md 7p;
+// always at step 0).  Every other value is reserved.
 // ln, sin and cos are written out in integer operations and single-rounded fp32 add, sub, mul, div and sqrt, and every file that includes this
 // is compiled with -ffp-contract=off: tweediemix_amd/noise.py restates the same operations in numpy and is compared by equality.  The functions
 // are __host__ __device__ so that a host program can make the same comparison without a GPU.

@@ -6,6 +6,8 @@
 // bit-identical to the numpy restatements (guidance.vpred_rescaled_step_reference / vpred_rescaled_multistep_reference).
 // The stochastic step (tmix_vpred_step_noise[_dev]) is the same kernel with one trailing VideoNoiseArgs: the move of either solver
 // plus cz * z, z from noise.h (noise.vpred_step_reference restates it).
+// The hold (tmix_vpred_step_hold[_dev], tmix_video_hold_composite) is the same kernel again with a VideoHoldArgs behind the
+// VideoNoiseArgs: the stored value is hold_blend(moved, ...), the held part a clean latent at the written state's noise level under one fixed noise.
 #include "step_core.h"
 #include "noise.h"
 
@@ -47,27 +49,69 @@ struct RowsView {
 // serves every schedule entry.
 struct VideoNoiseArgs { const uint32_t* keys; const float* prm; float cz; uint32_t step; };
 constexpr uint32_t NOISE_STREAM_VIDEO_STEP = 1u;        // noise.STREAM_VIDEO_STEP; 0 is the image sampler's step
+constexpr uint32_t NOISE_STREAM_VIDEO_HOLD = 2u;        // noise.STREAM_VIDEO_HOLD: the held part's one fixed noise (step 0 at every noise level)
+
+// HOLD: the presence of ONE more trailing kernel argument behind VideoNoiseArgs.  kx: the clean latent to hold, fp32 [S or 1][C][kx_f][hw] with
+// kx_f in {1, F} (1: one image for every frame) and video s at s * kx_vs (0: one for all videos); w: its weight, fp32 in [0, 1], [S or 1][w_f][hw],
+// the same for every channel.  (ha, hs) = sqrt(alpha), sqrt(1 - alpha) of the state the step WRITES: prm null: by value; else prm[10], prm[11] of
+// the 12 uploaded floats.  F and hw locate (c, f, p) of an element in its video (rs.per = C F hw gives the video).
+struct VideoHoldArgs { const float* kx; int64_t kx_vs; int kx_f; const float* w; int64_t w_vs; int w_f; const float* prm; float ha, hs; int F; int64_t hw; };
+
+// where element r = (c, f, p) of video s reads its held latent and its weight
+struct HoldAt { int64_t kx, w; };
+__device__ __forceinline__ HoldAt hold_at(const VideoHoldArgs& h, int64_t s, int64_t r) {
+    const int64_t p = r % h.hw, cf = r / h.hw;
+    const int64_t f = cf % h.F, c = cf / h.F;
+    return {s * h.kx_vs + (c * h.kx_f + (h.kx_f == 1 ? 0 : f)) * h.hw + p, s * h.w_vs + (h.w_f == 1 ? 0 : f) * h.hw + p};
+}
+
+// THE blend of the hold, for the step entries and the composite entry alike:
+//   kept = hs != 0 ? rnd(rnd(ha kx) + rnd(hs zh)) : kx          zh = the normal of (r, the video's key, step 0, NOISE_STREAM_VIDEO_HOLD)
+//   out  = w == 0 ? moved : w == 1 ? kept : rnd(rnd(w kept) + rnd(rnd(1 - w) moved))
+// The selects are the point: w == 0 keeps the parent's bits, w == 1 does not look at moved (a NaN there stays out), hs == 0 gives kx back with its
+// sign bit and calls no generator.  zh is not formed where w == 0 (it would not be used).
+template <int DT>
+__device__ __forceinline__ float hold_blend(float moved, float kx, float w, float ha, float hs, uint64_t r, uint32_t key_lo, uint32_t key_hi) {
+    if (w == 0.0f) return moved;
+    float kept = kx;
+    if (hs != 0.0f) {
+        const float zh = noise_normal(r, key_lo, key_hi, 0u, NOISE_STREAM_VIDEO_HOLD);
+        kept = rnd<DT>(rnd<DT>(ha * kx) + rnd<DT>(hs * zh));
+    }
+    if (w == 1.0f) return kept;
+    return rnd<DT>(rnd<DT>(w * kept) + rnd<DT>(rnd<DT>(1.0f - w) * moved));
+}
+
+template <typename A, typename... R> __device__ __forceinline__ const A& pack_first(const A& a, const R&...) { return a; }
+template <typename A, typename B> __device__ __forceinline__ const B& pack_second(const A&, const B& b) { return b; }
 
 // MS: the multistep move; x0_prev [n] fp32 is then read and rewritten with this step's x0 (no other argument aliases it), and is not touched otherwise.
 // RS: element i uses the factor of its video, rs.fac[i / rs.per] (the video is the outermost index of i), for x0 AND for the DDIM move's eps; without
 // RS no factor is read and no product is formed, which is what keeps those instantiations' bits the ones they had before the rescale existed.
 // NzT: nothing, or {VideoNoiseArgs}: the stored value is then cz != 0 ? rnd(moved + rnd(cz * z)) : moved -- one product and one sum behind the
-// parent's operations, and no generator call at cz == 0 (rs.per is read for the video of i, so the launcher always fills it).
+// parent's operations, and no generator call at cz == 0 (rs.per is read for the video of i, so the launcher always fills it); or
+// {VideoNoiseArgs, VideoHoldArgs}: the stored value is then hold_blend of that one.
 template <typename View, bool MS, bool RS, typename... NzT>
 __global__ void __launch_bounds__(256)
 video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const RescaleArgs rs, const NzT... nz) {
     constexpr int DT = View::DT;
-    constexpr bool NZ = sizeof...(NzT) == 1;
-    static_assert(sizeof...(NzT) <= 1, "the trailing argument is one VideoNoiseArgs or nothing");
+    constexpr bool NZ = sizeof...(NzT) >= 1, HOLD = sizeof...(NzT) == 2;
+    static_assert(sizeof...(NzT) <= 2, "the trailing arguments are nothing, one VideoNoiseArgs, or that and one VideoHoldArgs");
     const StepCoef k = vw.template coef<MS>();
     float cz = 0.0f;
     uint32_t step = 0;
     const uint32_t* keys = nullptr;
     if constexpr (NZ) {
-        const VideoNoiseArgs& a = (nz, ...);
+        const VideoNoiseArgs& a = pack_first(nz...);
         cz = a.prm ? a.prm[8] : a.cz;
         step = a.prm ? (uint32_t)a.prm[9] : a.step;
         keys = a.keys;
+    }
+    float ha = 0.0f, hs = 0.0f;
+    if constexpr (HOLD) {
+        const VideoHoldArgs& h = pack_second(nz...);
+        ha = h.prm ? h.prm[10] : h.ha;
+        hs = h.prm ? h.prm[11] : h.hs;
     }
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -85,6 +129,12 @@ video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const R
                 const float z = noise_normal((uint64_t)(i - s * rs.per), keys[2 * s], keys[2 * s + 1], step, NOISE_STREAM_VIDEO_STEP);
                 moved = rnd<DT>(moved + rnd<DT>(cz * z));
             }
+        }
+        if constexpr (HOLD) {
+            const VideoHoldArgs& h = pack_second(nz...);
+            const int64_t s = i / rs.per, r = i - s * rs.per;
+            const HoldAt at = hold_at(h, s, r);
+            moved = hold_blend<DT>(moved, h.kx[at.kx], h.w[at.w], ha, hs, (uint64_t)r, keys[2 * s], keys[2 * s + 1]);
         }
         vw.st(i, moved);
         if constexpr (MS) x0_prev[i] = e.x0;
@@ -166,6 +216,32 @@ int launch_inject(void* x, int64_t per_frame, int frames, int64_t n, int hard, f
     int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
     frame_inject_kernel<DT><<<blocks, 256, 0, st>>>((T*)x, per_frame, frames, n, hard, a, b);
     TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+// x_T under the hold, once per run: the blend with moved = x, in place on x [S][C][F][hw] of the model dtype
+template <int DT>
+__global__ void __launch_bounds__(256)
+video_hold_composite_kernel(typename EpsT<DT>::T* __restrict__ x, int64_t n, int64_t per, const uint32_t* __restrict__ keys, const VideoHoldArgs h) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t s = i / per, r = i - s * per;
+        const HoldAt at = hold_at(h, s, r);
+        StT<DT>::st(x, i, hold_blend<DT>(EpsT<DT>::ld(x, i), h.kx[at.kx], h.w[at.w], h.ha, h.hs, (uint64_t)r, keys[2 * s], keys[2 * s + 1]));
+    }
+}
+
+// The hold's own arguments, answered behind the parent entry's checks (so channels, frames and hw are at least 1 here): null pointers, then the
+// frame counts, then the video strides -- 0 (one array for every video) or at least one video's extent.
+inline int check_hold(const char* me, const float* hold_x0, int64_t x0_stride, int x0_frames, const float* hold_w, int64_t w_stride, int w_frames,
+                      int channels, int frames, int64_t hw) {
+    if (!hold_x0 || !hold_w) TMIX_FAIL(TMIX_EINVAL, "%s: null hold_x0 / hold_w", me);
+    if ((x0_frames != 1 && x0_frames != frames) || (w_frames != 1 && w_frames != frames))
+        TMIX_FAIL(TMIX_ESHAPE, "%s: hold_x0_frames=%d hold_w_frames=%d (each 1 or frames=%d)", me, x0_frames, w_frames, frames);
+    const int64_t ex = (int64_t)channels * x0_frames * hw, ew = (int64_t)w_frames * hw;
+    if ((x0_stride != 0 && x0_stride < ex) || (w_stride != 0 && w_stride < ew))
+        TMIX_FAIL(TMIX_ESHAPE, "%s: hold video strides %lld / %lld (each 0 or at least one video's %lld / %lld floats)", me, (long long)x0_stride,
+                  (long long)w_stride, (long long)ex, (long long)ew);
     return TMIX_OK;
 }
 
@@ -264,5 +340,64 @@ extern "C" int tmix_vpred_step_noise_dev(float* x, const float* v_u, int64_t cli
     const VideoNoiseArgs nz = {keys, params, 0.0f, 0u};
     return for_form(x0_prev != nullptr, factors != nullptr, [&](auto ms, auto rs) {
         return launch_video_step<ms(), rs()>(vw, x0_prev, videos * per, RescaleArgs{factors, per}, (hipStream_t)stream, nz);
+    });
+}
+
+// ---- the hold: the noise entries' kernels with one more trailing argument; cz == 0 is the deterministic parent bit for bit
+extern "C" int tmix_vpred_step_hold(const void* x, const void* v, void* out, float* x0_prev, int dtype, int videos, int channels, int frames, int64_t hw,
+                                    float g, float sa, float s1, float a, float b, float c, float cz, const float* factors, const uint32_t* keys,
+                                    uint32_t step, float ha, float hs, const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames,
+                                    const float* hold_w, int64_t hold_w_video_stride, int hold_w_frames, void* stream) {
+    const char* me = "vpred_step_hold";
+    if (x && v && out && !keys) TMIX_FAIL(TMIX_EINVAL, "%s: null keys", me);
+    const int64_t clip = (int64_t)(channels > 0 ? channels : 0) * (frames > 0 ? frames : 0) * (hw > 0 ? hw : 0);
+    if (int rc = check_vpred_step(me, x && v && out, false, nullptr, false, nullptr, dtype, false, false, videos, channels, frames, hw, clip, clip)) return rc;
+    if (int rc = check_hold(me, hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, channels, frames, hw)) return rc;
+    const int64_t per = (int64_t)channels * frames * hw, n = (int64_t)videos * per;
+    const StepCoef k = {g, sa, s1, a, b, x0_prev ? c : 0.0f};
+    const VideoNoiseArgs nz = {keys, nullptr, cz, step};
+    const VideoHoldArgs hd = {hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, nullptr, ha, hs, frames, hw};
+    return for_dtype(dtype, me, "dtype", [&](auto dt) {
+        typedef typename EpsT<dt()>::T T;
+        const DenseView<dt()> vw = {(const T*)x, (const T*)v, (T*)out, n, k};
+        return for_form(x0_prev != nullptr, factors != nullptr, [&](auto ms, auto rs) {
+            return launch_video_step<ms(), rs()>(vw, x0_prev, n, RescaleArgs{factors, per}, (hipStream_t)stream, nz, hd);
+        });
+    });
+}
+
+extern "C" int tmix_vpred_step_hold_dev(float* x, const float* v_u, int64_t clip_stride_u, const float* v_c, int64_t clip_stride_c,
+                                        const float* params, int videos, int channels, int frames, int64_t hw, float* x0_prev,
+                                        const float* factors, const uint32_t* keys, const float* hold_x0, int64_t hold_x0_video_stride,
+                                        int hold_x0_frames, const float* hold_w, int64_t hold_w_video_stride, int hold_w_frames, void* stream) {
+    const char* me = "vpred_step_hold_dev";
+    if (x && v_u && v_c && params && !keys) TMIX_FAIL(TMIX_EINVAL, "%s: null keys", me);
+    if (int rc = check_vpred_step(me, x && v_u && v_c && params, false, nullptr, false, nullptr, TMIX_F32, false, false, videos, channels, frames, hw, clip_stride_u, clip_stride_c)) return rc;
+    if (int rc = check_hold(me, hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, channels, frames, hw)) return rc;
+    const int64_t per = (int64_t)channels * frames * hw;
+    const RowsView vw = {x, v_u, clip_stride_u, v_c, clip_stride_c, params, channels, frames, hw};
+    const VideoNoiseArgs nz = {keys, params, 0.0f, 0u};
+    const VideoHoldArgs hd = {hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, params, 0.0f, 0.0f, frames, hw};
+    return for_form(x0_prev != nullptr, factors != nullptr, [&](auto ms, auto rs) {
+        return launch_video_step<ms(), rs()>(vw, x0_prev, videos * per, RescaleArgs{factors, per}, (hipStream_t)stream, nz, hd);
+    });
+}
+
+extern "C" int tmix_video_hold_composite(void* x, int dtype, int videos, int channels, int frames, int64_t hw, float ha, float hs, const uint32_t* keys,
+                                         const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames, const float* hold_w,
+                                         int64_t hold_w_video_stride, int hold_w_frames, void* stream) {
+    const char* me = "video_hold_composite";
+    if (x && !keys) TMIX_FAIL(TMIX_EINVAL, "%s: null keys", me);
+    const int64_t clip = (int64_t)(channels > 0 ? channels : 0) * (frames > 0 ? frames : 0) * (hw > 0 ? hw : 0);
+    if (int rc = check_vpred_step(me, x != nullptr, false, nullptr, false, nullptr, dtype, false, false, videos, channels, frames, hw, clip, clip)) return rc;
+    if (int rc = check_hold(me, hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, channels, frames, hw)) return rc;
+    const int64_t per = (int64_t)channels * frames * hw, n = (int64_t)videos * per;
+    const VideoHoldArgs hd = {hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, nullptr, ha, hs, frames, hw};
+    return for_dtype(dtype, me, "dtype", [&](auto dt) -> int {
+        typedef typename EpsT<dt()>::T T;
+        int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+        video_hold_composite_kernel<dt()><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((T*)x, n, per, keys, hd);
+        TMIX_LAUNCH_CHECK();
+        return TMIX_OK;
     });
 }

@@ -15,7 +15,8 @@ U32, U64 = np.uint32, np.uint64
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
 STREAM_IMAGE_STEP = 0           # stream id of the image sampler's step
-STREAM_VIDEO_STEP = 1           # of the video sampler's step: the same seed draws unrelated noise there; every other value is reserved
+STREAM_VIDEO_STEP = 1           # of the video sampler's step: the same seed draws unrelated noise there
+STREAM_VIDEO_HOLD = 2           # of the one fixed noise of the video sampler's hold regions (always step 0); every other value is reserved
 
 # the constants of csrc/noise.h, value for value
 SQRT2 = F32(1.41421354)
@@ -169,3 +170,60 @@ def vpred_step_reference(x, v, x0_prev, params_or_coeffs, keys, step=None, facto
     if bf16:
         moved = SV._bf16_round(moved)
     return moved, x0
+
+
+def hold_blend_reference(moved, kx, w, ha, hs, keys, lowp=None):
+    """the blend of the video hold (csrc/video_step.hip's hold_blend) on fp32 arrays -> fp32, before the store's rounding.
+    moved [B, C, F, ...]; kx [B or 1, C, Fk, ...] with Fk in {1, F}; w [B or 1, Fw, ...] with Fw in {1, F}, broadcast over channels; keys [B] of
+    (low word, high word); lowp None or np.float16 (every product and sum rounds).
+      kept = hs != 0 ? rnd(rnd(ha kx) + rnd(hs zh)) : kx        zh = normal(the element's linear index in its video, the video's key, 0, STREAM_VIDEO_HOLD)
+      out  = w == 0 ? moved : w == 1 ? kept : rnd(rnd(w kept) + rnd(rnd(1 - w) moved))
+    The selects are np.where on the operands' own arrays: a NaN in moved stays out of w == 1, kx keeps its sign bit at hs == 0."""
+    from . import solver as SV
+    moved = np.asarray(moved, F32)
+    B = moved.shape[0]
+    if len(keys) != B:
+        raise ValueError(f"hold_blend_reference: {len(keys)} keys for {B} videos")
+    kx, w = np.asarray(kx, F32), np.asarray(w, F32)
+    if kx.ndim != moved.ndim or w.ndim != moved.ndim - 1:
+        raise ValueError(f"hold_blend_reference: kx {kx.shape} / w {w.shape} for a state {moved.shape}")
+    kx = np.ascontiguousarray(np.broadcast_to(kx, moved.shape))
+    w = np.ascontiguousarray(np.broadcast_to(w[:, None], moved.shape))
+    ha, hs = F32(ha), F32(hs)
+    kept = kx
+    if hs != 0.0:
+        idx = np.arange(moved[0].size, dtype=U64).reshape(moved[0].shape)
+        zh = np.stack([normal(idx, k[0], k[1], 0, STREAM_VIDEO_HOLD) for k in keys])
+        kept = SV._h((SV._h((ha * kx).astype(F32), lowp) + SV._h((hs * zh).astype(F32), lowp)).astype(F32), lowp).astype(F32)
+    with np.errstate(invalid="ignore"):
+        mix = SV._h((SV._h((w * kept).astype(F32), lowp) + SV._h((SV._h((F32(1) - w).astype(F32), lowp) * moved).astype(F32), lowp)).astype(F32), lowp)
+    return np.where(w == 0, moved, np.where(w == 1, kept, mix)).astype(F32)
+
+
+def vpred_hold_reference(x, v, x0_prev, params_or_coeffs, keys, kx, w, step=None, factors=None, lowp=None):
+    """numpy restatement of tmix_vpred_step_hold and tmix_vpred_step_hold_dev -> (out, x0), built on vpred_step_reference: that
+    gives moved (before the store's rounding) and x0, hold_blend_reference the stored value.  params_or_coeffs: the 12 floats the _dev entry
+    reads, (ha, hs) in slots 10 and 11, or the dense entry's nine (g, sa, s1, a, b, c, cz, ha, hs).  kx, w as in hold_blend_reference; everything
+    else as in vpred_step_reference.  Compared with both kernels by equality."""
+    from . import solver as SV
+    p = [float(F32(c)) for c in params_or_coeffs]
+    if len(p) == 12:
+        ha, hs, head = p[10], p[11], p
+    elif len(p) == 9:
+        ha, hs, head = p[7], p[8], p[:7]
+    else:
+        raise ValueError(f"vpred_hold_reference: {len(p)} values (12 device parameters or the 9 coefficients g, sa, s1, a, b, c, cz, ha, hs)")
+    bf16 = isinstance(lowp, str) and lowp == "bf16"
+    lp = None if bf16 else lowp                      # bf16: fp32 arithmetic, ONE rounding at the store -- behind the blend
+    moved, x0 = vpred_step_reference(x, v, x0_prev, head, keys, step, factors, lp)
+    out = hold_blend_reference(moved, kx, w, ha, hs, keys, lp)
+    return (SV._bf16_round(out) if bf16 else SV._h(out, lp).astype(F32)), x0
+
+
+def video_hold_composite_reference(x, kx, w, ha, hs, keys, lowp=None):
+    """numpy restatement of tmix_video_hold_composite: the blend with moved = x, then the store's rounding"""
+    from . import solver as SV
+    bf16 = isinstance(lowp, str) and lowp == "bf16"
+    lp = None if bf16 else lowp
+    out = hold_blend_reference(x, kx, w, ha, hs, keys, lp)
+    return SV._bf16_round(out) if bf16 else SV._h(out, lp).astype(F32)

@@ -1099,6 +1099,80 @@ def video_step_params_noise(t, g, at, coeffs_or_next, cz, step_index, out=None):
     return _fill_params(head + [float(np.float32(cz)), float(int(step_index)), 0.0, 0.0], out)
 
 
+def _video_hold(hold_x0, hold_w, S, Cc, Fr, h, w):
+    """the six hold arguments of the three hold entries: hold_x0 [S or 1, C, Fk, h, w], hold_w [S or 1, Fw, h, w], fp32 contiguous on the device,
+    Fk, Fw in {1, F}; a leading 1 is shared by every video (video stride 0)"""
+    for t in (hold_x0, hold_w):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), (t.dtype, tuple(t.shape))
+    assert hold_x0.dim() == 5 and hold_x0.shape[0] in (1, S) and hold_x0.shape[1] == Cc and hold_x0.shape[2] in (1, Fr), (tuple(hold_x0.shape), (S, Cc, Fr, h, w))
+    assert tuple(hold_x0.shape[3:]) == (h, w), (tuple(hold_x0.shape), (S, Cc, Fr, h, w))
+    assert hold_w.dim() == 4 and hold_w.shape[0] in (1, S) and hold_w.shape[1] in (1, Fr) and tuple(hold_w.shape[2:]) == (h, w), (tuple(hold_w.shape), (S, Fr, h, w))
+    sx = 0 if hold_x0.shape[0] == 1 and S > 1 else hold_x0[0].numel()
+    sw = 0 if hold_w.shape[0] == 1 and S > 1 else hold_w[0].numel()
+    return _p(hold_x0), sx, int(hold_x0.shape[2]), _p(hold_w), sw, int(hold_w.shape[1])
+
+
+def vpred_step_hold(x, v, g, at, move, cz, keys, step, at_written, hold_x0, hold_w, x0_prev=None, factors=None, out=None):
+    """tmix_vpred_step_hold: vpred_step_noise (cz may be 0: the deterministic step) whose stored value is blended with the held
+    latent: x [B,C,F,h,w], hold_x0 fp32 [B or 1, C, 1 or F, h, w], hold_w fp32 [B or 1, 1 or F, h, w] in [0, 1] (1 = held).  at_written: the alpha
+    of the state the step writes, None on the last step of a schedule ((ha, hs) = (1, 0): the held part is hold_x0 itself).
+    noise.vpred_hold_reference gives the same bits.  out may be x.  Returns the next latents."""
+    _need_cuda(x, v, x0_prev, factors, keys, hold_x0, hold_w)
+    assert x.dim() == 5 and x.is_contiguous() and v.is_contiguous() and v.numel() == 2 * x.numel() and v.dtype == x.dtype
+    out = torch.empty_like(x) if out is None else out
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    sa, s1 = step_coeffs(at, at)[:2]
+    ha, hs = hold_coeffs(at_written)
+    B, Cc, Fr, h, w = x.shape
+    a, b, c = (float(m) for m in (tuple(move) + (0.0,))[:3])
+    prev = None if x0_prev is None else _history(x0_prev, x)
+    fac = None if factors is None else _video_factors(factors, B)
+    assert 0 <= int(step) < 2 ** 32, step
+    L.check(L.load().tmix_vpred_step_hold(_p(x), _p(v), _p(out), prev, _EPS_DT[x.dtype], B, Cc, Fr, h * w, float(g), sa, s1, a, b, c, float(cz), fac,
+                                          _video_keys(keys, B), int(step), ha, hs, *_video_hold(hold_x0, hold_w, B, Cc, Fr, h, w), _stream()),
+            "tmix_vpred_step_hold")
+    return out
+
+
+def vpred_step_hold_dev(x, v_u, v_c, params, keys, hold_x0, hold_w, x0_prev=None, factors=None, clip_stride_u=None, clip_stride_c=None):
+    """tmix_vpred_step_hold_dev: vpred_step_noise_dev with the hold; params holds 12 floats (video_step_params_hold).  In place on
+    x [S,C,F,h,w] fp32; returns x."""
+    _need_cuda(x, v_u, v_c, params, x0_prev, factors, keys, hold_x0, hold_w)
+    S, Cc, Fr, hw, su, sc = _plan_rows(x, v_u, v_c, x.shape[1], clip_stride_u, clip_stride_c)
+    assert params.dtype == torch.float32 and params.numel() >= 12, params.numel()
+    prev = None if x0_prev is None else _history(x0_prev, x)
+    fac = None if factors is None else _video_factors(factors, S)
+    L.check(L.load().tmix_vpred_step_hold_dev(_p(x), _p(v_u), su, _p(v_c), sc, _p(params), S, Cc, Fr, hw, prev, fac, _video_keys(keys, S),
+                                              *_video_hold(hold_x0, hold_w, S, Cc, Fr, x.shape[3], x.shape[4]), _stream()), "tmix_vpred_step_hold_dev")
+    return x
+
+
+def video_hold_composite(x, at_written, keys, hold_x0, hold_w):
+    """tmix_video_hold_composite: the hold's blend in place on x [S,C,F,h,w] (any model dtype) with moved = x, at the noise level `at_written` of x
+    itself (None: (ha, hs) = (1, 0)): x_T once at the start of a run.  Returns x."""
+    _need_cuda(x, keys, hold_x0, hold_w)
+    assert x.dim() == 5 and x.is_contiguous()
+    S, Cc, Fr, h, w = x.shape
+    ha, hs = hold_coeffs(at_written)
+    L.check(L.load().tmix_video_hold_composite(_p(x), _EPS_DT[x.dtype], S, Cc, Fr, h * w, ha, hs, _video_keys(keys, S),
+                                               *_video_hold(hold_x0, hold_w, S, Cc, Fr, h, w), _stream()), "tmix_video_hold_composite")
+    return x
+
+
+def hold_coeffs(at_written):
+    """(ha, hs) of the hold: sqrt(alpha), sqrt(1 - alpha) of the written state as step_coeffs forms (sa, s1); None (the last step): (1, 0)"""
+    return (1.0, 0.0) if at_written is None else step_coeffs(at_written, at_written)[:2]
+
+
+def video_step_params_hold(t, g, at, coeffs_or_next, cz, step_index, at_written, out=None):
+    """the 12 floats tmix_vpred_step_hold_dev reads: video_step_params_noise's with slots 10 and 11 = (ha, hs) of the written state (hold_coeffs)"""
+    m = [float(np.float32(c)) for c in coeffs_or_next]
+    assert len(m) in (2, 3), m
+    assert 0 <= int(step_index) < 2 ** 24, step_index            # exact in fp32
+    head = [float(t), *step_coeffs(at, at)[:2], *m, float(g)] + [0.0] * (4 - len(m))
+    return _fill_params(head + [float(np.float32(cz)), float(int(step_index)), *hold_coeffs(at_written)], out)
+
+
 def frame_inject(x, clips, frames, interp=None):
     """first-frame feature injection (video_gen/utils_attn.py:433-455), in place on x [(clips*frames), ...] contiguous."""
     _need_cuda(x)

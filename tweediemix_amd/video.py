@@ -207,22 +207,66 @@ def _noise_step(schedule, t, eta, phase):
     return (san, s1d), cz, i
 
 
+def _check_hold(hold, noise_seeds, videos, channels, frames, h, w):
+    """hold = (x0, weight) of DESIGN.md 7p -> (x0 fp32 [S or 1, C, 1 or F, h, w], weight fp32 [S or 1, 1 or F, h, w]) as contiguous host tensors,
+    or None for hold None.  Shapes, finiteness and the weight's range are checked here, on the host, before the GPU is touched; the hold's fixed
+    noise is a function of the video's seed, so noise_seeds are needed at eta == 0 too."""
+    if hold is None:
+        return None
+    if noise_seeds is None:
+        raise ValueError("hold: noise_seeds (one integer per video) are what the held part's fixed noise is a function of, also at eta = 0")
+    if not isinstance(hold, (tuple, list)) or len(hold) != 2:
+        raise ValueError("hold: a pair (x0, weight)")
+    x0, wt = (torch.as_tensor(a).detach().to("cpu", torch.float32).contiguous() for a in hold)
+    S, C, F = int(videos), int(channels), int(frames)
+    if x0.dim() != 5 or x0.shape[0] not in (1, S) or x0.shape[1] != C or x0.shape[2] not in (1, F) or tuple(x0.shape[3:]) != (h, w):
+        raise ValueError(f"hold: x0 of shape {tuple(x0.shape)}; [{S} or 1, {C}, {F} or 1, {h}, {w}] is what this sampler holds")
+    if wt.dim() != 4 or wt.shape[0] not in (1, S) or wt.shape[1] not in (1, F) or tuple(wt.shape[2:]) != (h, w):
+        raise ValueError(f"hold: weight of shape {tuple(wt.shape)}; [{S} or 1, {F} or 1, {h}, {w}] is what this sampler holds")
+    if not bool(torch.isfinite(x0).all()):
+        raise ValueError("hold: x0 has values that are not finite")
+    if not bool(((wt >= 0.0) & (wt <= 1.0)).all()):
+        raise ValueError("hold: weight outside [0, 1] (1 = held, 0 = sampled)")
+    return x0, wt
+
+
+def _hold_step(schedule, t, eta, phase):
+    """the step at timestep t under a hold -> (move, cz, schedule index, the alpha of the state it writes or None on the schedule's last step).
+    eta > 0: _noise_step's values; eta == 0: the deterministic parent's own coefficients ((sa_next, s1_next) of ops.step_coeffs, phase.coeffs(t))
+    with cz = 0, so that a weight of 0 everywhere is the run without the hold bit for bit."""
+    t = int(t)
+    if eta > 0.0:
+        move, cz, i = _noise_step(schedule, t, eta, phase)
+    else:
+        i = schedule.index(t)
+        move = phase.coeffs(t) if phase is not None else ops.step_coeffs(schedule.alpha(t), schedule.next_alpha(t))[2:]
+        cz, i = 0.0, 0 if i is None else i
+    last = schedule.index(t) == len(schedule.timesteps) - 1
+    return tuple(move), cz, i, None if last else schedule.next_alpha(t)
+
+
 @torch.no_grad()
 def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None,
-                solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None):
+                solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None, hold=None):
     """pipeline_i2vgen_xl.py:680-719.  unet(latent_model_input [2B,C,F,H,W], t) -> v-prediction of the same shape (the
     caller closes over prompt/image conditioning; an i2vgen plan behind it needs its `inject` flag set for t, from
     injection_active); latents [B,C,F,H,W] on the GPU in the model dtype.  solver="dpmpp2m": every step is tmix_vpred_step_ms on the
     model dtype with an fp32 history of x0.  guidance_rescale = phi > 0: every step is tmix_vpred_rescale_factors on
     v (one factor per video, g read from a small device tensor) and then the _rs form of the step entry; 0 is the loop without it, launch for launch.
     eta > 0 with noise_seeds, one integer per video: every step is tmix_vpred_step_noise, the same move plus cz * z with z a
-    function of (the video's seed, the schedule index, the element's index in its video); 0 is the loop without it, launch for launch."""
+    function of (the video's seed, the schedule index, the element's index in its video); 0 is the loop without it, launch for launch.
+    hold = (x0, weight) with noise_seeds: x_T is composited once (tmix_video_hold_composite, on a copy) and every step is
+    tmix_vpred_step_hold, which keeps x0 under the weight at the noise level of the state it writes; None is the loop without it."""
     from .guidance import validate_phi
     ms = _check_solver(solver)
     phi = validate_phi(guidance_rescale)
     eta, seeds = _check_eta(eta, noise_seeds, latents.shape[0])
+    hold = _check_hold(hold, seeds, *latents.shape)
     x = latents.contiguous()
-    keys = ops.noise_keys(seeds, x.device) if eta > 0.0 else None
+    keys = ops.noise_keys(seeds, x.device) if eta > 0.0 or hold is not None else None
+    if hold is not None:
+        hx, hw_ = (a.to(x.device) for a in hold)
+        x = ops.video_hold_composite(x.clone(), schedule.alpha(int(schedule.timesteps[0])), keys, hx, hw_)
     if ms:
         phase, hist = SolverPhase(schedule), torch.zeros_like(x, dtype=torch.float32)
     if phi > 0.0:
@@ -236,7 +280,11 @@ def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_s
         v = unet(torch.cat([x, x]), int(t)).contiguous()
         if phi > 0.0:
             ops.vpred_rescale_factors(v, g_dev, 0, phi, out=fac, ws=ws)
-        if eta > 0.0:
+        if hold is not None:
+            move, cz, i, aw = _hold_step(schedule, int(t), eta, phase if ms else None)
+            x = ops.vpred_step_hold(x, v, guidance_scale, schedule.alpha(int(t)), move, cz, keys, i, aw, hx, hw_, x0_prev=hist if ms else None,
+                                    factors=fac if phi > 0.0 else None)
+        elif eta > 0.0:
             move, cz, i = _noise_step(schedule, int(t), eta, phase if ms else None)
             x = ops.vpred_step_noise(x, v, guidance_scale, schedule.alpha(int(t)), move, cz, keys, i, x0_prev=hist if ms else None,
                                      factors=fac if phi > 0.0 else None)
@@ -277,26 +325,39 @@ class VideoSampler:
     and a step stays one (48-byte) upload and one replay.  `noise_keys` int32 [S, 2] holds the videos' key words at a fixed address and is
     written once per sample(); set_noise_seeds replaces the seeds between runs.  A video's noise is a function of its own seed, the schedule
     index and the element's index in the video: video s of a batch is still bit for bit its single run.  eta = 0 is the sampler without it: no
-    new launch, buffer, graph key or upload size."""
+    new launch, buffer, graph key or upload size.
+
+    hold = (x0, weight) with noise_seeds (also at eta = 0: the held part's fixed noise is keyed by the video's seed): x0 fp32
+    [S or 1, C, 1 or F, h, w] is the clean latent held where weight fp32 [S or 1, 1 or F, h, w] is 1, sampled where it is 0, blended in between.
+    sample() composites x_T once (tmix_video_hold_composite at the first timestep's noise level) and every step ends in tmix_vpred_step_hold_dev,
+    the noise entry (cz = 0 at eta = 0) followed by the blend at the noise level of the state it writes ((1, 0) on the last step: the final latent
+    IS x0 wherever the weight is 1).  `hold_x0`, `hold_w` and `noise_keys` sit at fixed addresses (set_hold rewrites their contents), params is
+    12 floats with (ha, hs) in slots 10 and 11, the graph keys gain a trailing "hold", and a step stays one 48-byte upload and one replay.
+    hold = None is the sampler without it: no new launch, buffer, graph key or upload size."""
 
     def __init__(self, plan, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None, use_graphs: bool = True,
-                 solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None):
+                 solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None, hold=None):
         from .guidance import validate_phi
         self.plan, self.schedule, self.g, self.injector, self.use_graphs = plan, schedule, float(guidance_scale), injector, use_graphs
         self.solver, self.ms = solver, _check_solver(solver)
         self.guidance_rescale = validate_phi(guidance_rescale)
         self.eta, self._noise_seeds = _check_eta(eta, noise_seeds, plan.videos)          # host only: refused before the GPU is touched
         cfg = plan.cfg
+        hold = _check_hold(hold, self._noise_seeds, plan.videos, cfg.in_channels, plan.frames, plan.h, plan.w)      # host only, as above
+        wide = self.eta > 0.0 or hold is not None         # the 12-float parameter layout and the videos' keys
         dev = plan.plans[0].dev
         self.state = torch.zeros(plan.videos, cfg.in_channels, plan.frames, plan.h, plan.w, device=dev, dtype=torch.float32)
-        # {t, sa, s1, sa_next, s1_next, g, -, -}; solver: {t, sa, s1, cx, c0, c1, g, -}; eta > 0: four more floats {cz, schedule index, 0, 0}
-        self.params = torch.zeros(12 if self.eta > 0.0 else 8, device=dev, dtype=torch.float32)
+        # {t, sa, s1, sa_next, s1_next, g, -, -}; solver: {t, sa, s1, cx, c0, c1, g, -}; eta > 0 or a hold: four more floats {cz, schedule index, ha, hs}
+        self.params = torch.zeros(12 if wide else 8, device=dev, dtype=torch.float32)
         # staging for the asynchronous parameter upload (as the image sampler's step_params)
-        self._ring = ParamRing(width=12) if self.eta > 0.0 else ParamRing()
+        self._ring = ParamRing(width=12) if wide else ParamRing()
         self.noise_keys = self._keys_stale = None
-        if self.eta > 0.0:                                # int32 [S, 2]: every video's key words at an address the captured steps keep
+        if wide:                                          # int32 [S, 2]: every video's key words at an address the captured steps keep
             self.noise_keys = torch.zeros(plan.videos, 2, device=dev, dtype=torch.int32)
             self._keys_stale = True
+        self.hold_x0 = self.hold_w = None
+        if hold is not None:                              # at addresses the captured steps keep
+            self.hold_x0, self.hold_w = (a.to(dev) for a in hold)
         self.graphs = {}
         self.x0_prev = torch.zeros_like(self.state) if self.ms else None
         self.phase = SolverPhase(schedule) if self.ms else None
@@ -308,9 +369,22 @@ class VideoSampler:
     def set_noise_seeds(self, seeds):
         """the integer seed of every video's step noise (eta > 0) for the runs that follow: the next sample() (or step()) writes the key words
         into `noise_keys`, whose address the captured steps keep"""
-        _, self._noise_seeds = _check_eta(self.eta, seeds, self.plan.videos)
-        if self.eta > 0.0:
+        _, seeds = _check_eta(self.eta, seeds, self.plan.videos)
+        if seeds is None and self.hold_x0 is not None:
+            raise ValueError("hold: noise_seeds (one integer per video) are what the held part's fixed noise is a function of, also at eta = 0")
+        self._noise_seeds = seeds
+        if self.noise_keys is not None:
             self._keys_stale = True
+
+    def set_hold(self, x0, weight):
+        """new contents, of the shapes the sampler was built with, for the held latent and its weight in the runs that follow (the addresses stay)"""
+        if self.hold_x0 is None:
+            raise ValueError("set_hold: this sampler was built without hold=")
+        x0, wt = _check_hold((x0, weight), self._noise_seeds, *self.state.shape)
+        if x0.shape != self.hold_x0.shape or wt.shape != self.hold_w.shape:
+            raise ValueError(f"set_hold: shapes {tuple(x0.shape)} / {tuple(wt.shape)}; the sampler holds {tuple(self.hold_x0.shape)} / {tuple(self.hold_w.shape)}")
+        self.hold_x0.copy_(x0)
+        self.hold_w.copy_(wt)
 
     def _write_keys(self):
         self.noise_keys.copy_(ops.noise_keys(self._noise_seeds, self.noise_keys.device))
@@ -323,7 +397,10 @@ class VideoSampler:
         if self.guidance_rescale > 0.0:
             ops.vpred_rescale_factors_dev(eu, ec, self.state.shape[0], self.state[0].numel(), self.params, 6 if self.ms else 5,
                                           self.guidance_rescale, out=self.rs_factors, ws=self._rs_ws)
-        if self.eta > 0.0:
+        if self.hold_x0 is not None:
+            ops.vpred_step_hold_dev(self.state, eu, ec, self.params, self.noise_keys, self.hold_x0, self.hold_w, x0_prev=self.x0_prev,
+                                    factors=self.rs_factors)
+        elif self.eta > 0.0:
             ops.vpred_step_noise_dev(self.state, eu, ec, self.params, self.noise_keys, x0_prev=self.x0_prev, factors=self.rs_factors)
         elif self.guidance_rescale > 0.0:
             ops.vpred_step_rs_dev(self.state, eu, ec, self.params, self.rs_factors, x0_prev=self.x0_prev)
@@ -334,6 +411,11 @@ class VideoSampler:
 
     def _upload(self, t):
         sch = self.schedule
+        if self.hold_x0 is not None:
+            move, cz, i, aw = _hold_step(sch, t, self.eta, self.phase)       # first: a refused step rewrites no staging slot
+            ops.video_step_params_hold(t, self.g, sch.alpha(int(t)), move, cz, i, aw, out=self._ring.next())
+            self._ring.upload(self.params)
+            return
         if self.eta > 0.0:
             move, cz, i = _noise_step(sch, t, self.eta, self.phase)          # first: a refused step rewrites no staging slot
             ops.video_step_params_noise(t, self.g, sch.alpha(int(t)), move, cz, i, out=self._ring.next())
@@ -364,6 +446,8 @@ class VideoSampler:
             key = (key if self.ms else (inject,)) + ("rs",)
         if self.eta > 0.0:
             key = (key if isinstance(key, tuple) else (inject,)) + ("eta",)
+        if self.hold_x0 is not None:
+            key = (key if isinstance(key, tuple) else (inject,)) + ("hold",)
         g = self.graphs.get(key)
         if g is None:
             self._enqueue()                               # warm-up outside capture; it has already performed this step
@@ -384,8 +468,10 @@ class VideoSampler:
     def sample(self, latents: torch.Tensor) -> torch.Tensor:
         """latents [S,4,F,h,w] -> the final latents (a copy of the state)."""
         self.state.copy_(latents)
-        if self.eta > 0.0:
+        if self.noise_keys is not None:
             self._write_keys()
+        if self.hold_x0 is not None:                      # x_T under the hold, once, at the first timestep's noise level
+            ops.video_hold_composite(self.state, self.schedule.alpha(int(self.schedule.timesteps[0])), self.noise_keys, self.hold_x0, self.hold_w)
         for t in self.schedule.timesteps:
             self.step(int(t))
         return self.state.clone()
