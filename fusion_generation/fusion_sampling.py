@@ -71,6 +71,12 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          the DDIM paper's eta; --solver dpmpp2m: SDE-DPM-Solver++(2M) in k-diffusion's eta form; the two definitions coincide at
                          0 and 1 and differ in between.  0 (default): today's run bit for bit.  Does not combine with
                          --keep_latents / --keep_image
+  --guidance_interval T_HI,T_LO   guidance in a limited interval (arXiv:2404.07724): two integer timesteps, 1000 >= T_HI >= T_LO >= 0; a timestep
+                         t is guided iff T_LO <= t <= T_HI.  Outside it the trajectory step (behind the first timestep) uses the conditional
+                         prediction alone and its UNet call runs WITHOUT the unconditional row: K rows for a fusion call, one for a plain call
+                         (DESIGN.md 7q).  Timestep values, not schedule indices: the interval keeps its noise range under --timestep_spacing
+                         logsnr.  Without the flag, or with an interval that holds every timestep of the schedule: today's run bit for bit.
+                         Does not combine with --keep_latents / --keep_image
   --num_seeds N          N trajectories, seeds seed..seed+N-1 (trajectory i is exactly what `--seed seed+i` alone produces: its
                          x_T comes from its own generator), co-batched --seeds_per_batch at a time
   --gpus G               shard those seeds round-robin over G GPUs of this node: the script starts one process per GPU itself
@@ -166,6 +172,9 @@ def build_parser():
                    help='E in [0, 1]: noise added by every trajectory step, generated inside the step kernel from (seed, step, canvas coordinate). '
                         '--solver ddim: the DDIM paper\'s eta; --solver dpmpp2m: k-diffusion\'s SDE-DPM-Solver++(2M) eta; the two coincide at 0 and 1 '
                         'and differ in between (0: off)')
+    p.add_argument('--guidance_interval', type=str, default='',
+                   help='T_HI,T_LO: integer timesteps, 1000 >= T_HI >= T_LO >= 0; trajectory steps at timesteps outside [T_LO, T_HI] use the '
+                        'conditional prediction alone and run the UNet without the unconditional row (default: every step is guided)')
     p.add_argument('--timestep_spacing', type=str, default='leading', choices=['leading', 'logsnr'],
                    help="logsnr: n_timesteps uniform in log-SNR from the 'leading' grid's first timestep down to t = 1")
     p.add_argument('--num_seeds', type=int, default=1, help='trajectories to sample: seeds seed..seed+n-1')
@@ -346,7 +355,17 @@ def save_soft_weights(opt, tw, side_dir):
 
 
 def check_solver_args(opt):
-    """--solver / --timestep_spacing / --guidance_rescale / --eta: refuses what the sampler would refuse, before anything touches the GPU"""
+    """--solver / --timestep_spacing / --guidance_rescale / --eta / --guidance_interval: refuses what the sampler would refuse, before anything
+    touches the GPU.  opt.guidance_interval becomes None or (t_hi, t_lo)."""
+    from tweediemix_amd.guidance import validate_interval
+    try:
+        opt.guidance_interval = validate_interval(opt.guidance_interval or None, '--guidance_interval')
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if opt.guidance_interval is not None and (opt.keep_latents or opt.keep_image):
+        flag = '--keep_latents' if opt.keep_latents else '--keep_image'
+        raise SystemExit(f'--guidance_interval {opt.guidance_interval[0]},{opt.guidance_interval[1]} does not combine with {flag}: '
+                         f'the keep region exists on the guided step only')
     from tweediemix_amd.solver import validate_eta
     try:
         eta = validate_eta(opt.eta, '--eta')
@@ -631,7 +650,7 @@ def main(argv=None):
                       strict_reference=strict, use_graphs=not opt.no_graphs, n_seeds=per, n_streams=opt.streams, vae=vae,
                       fp8=(opt.dtype == 'fp8'), attention_masks=attn, mask_soften=soften,
                       solver=opt.solver, timestep_spacing=opt.timestep_spacing, guidance_rescale=opt.guidance_rescale,
-                      eta=opt.eta, noise_seeds=([opt.seed] * per if opt.eta > 0.0 else None),
+                      eta=opt.eta, noise_seeds=([opt.seed] * per if opt.eta > 0.0 else None), guidance_interval=opt.guidance_interval,
                       **(dict(canvas={k: canvas[k] for k in ('height', 'width', 'overlap')}) if canvas else {}))
     if vae_scaling:                                       # fusion_sampling.py:518 divides by vae.config.scaling_factor
         tw.vae_scaling_factor = float(vae_scaling)

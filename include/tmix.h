@@ -172,6 +172,27 @@ int tmix_fused_tweedie_step_noise_dev(const float* x, const void* eps, int eps_d
                                       float* out_x, float* out_x0, int K, int channels, int64_t hw, int mode, int rows, int seeds,
                                       const float* params, float* x0_prev, const float* factors, const uint32_t* keys, int w,
                                       int n_win, const int* win_yx, int canvas_h, int canvas_w, void* stream);
+/* UNGUIDED STEPS (guidance interval, arXiv:2404.07724; no reference counterpart).  The step of a UNet call that ran WITHOUT the
+ * unconditional row: eps is [seeds][rows][n] with row c the prediction of concept c (FUSION, rows >= K) or row 0 the scene prompt's (PLAIN,
+ * rows >= 1).  The arguments of tmix_fused_tweedie_step_dev, then
+ *   x0_prev  NULL: the DDIM params layout {t, sa, s1, sa_next, s1_next, is_last, -, -} and move; else the history buffer, read and rewritten:
+ *            the multistep layout {t, sa, s1, cx, c0, c1, is_last, -} and move.  The g slot of either layout is ignored.
+ *   keys     NULL: no noise, 8 floats are read and w, n_win, win_yx, canvas_h, canvas_w are not; else tmix_fused_tweedie_step_noise_dev's keys,
+ *            window table and 12 floats {.., cz, step_index, 0, 0}
+ * Per element, every product, sum and quotient its own fp32 operation (rnd: to fp16 and back when eps is fp16, else nothing):
+ *   t_c   = (x - rnd(s1 e_c)) / sa          e_c: row c's value itself -- no CFG, no rescale factor
+ *   x0    = 0; x0 = x0 + m_c t_c, c = 0..K-1  (FUSION)          x0 = t_0  (PLAIN)          tmix_fused_tweedie_step_dev's arithmetic and order
+ *   DDIM:       e0 = s1 != 0 ? (x - sa x0) / s1 : 0,   moved = sa_next x0 + rnd(s1_next e0)      the eps consistent with the blended estimate
+ *   multistep:  moved = cx x + (c1 != 0 ? c0 x0 + c1 x0_prev : c0 x0),   x0_prev = x0            tmix_fused_tweedie_step_ms_dev's move
+ *   out_x = is_last ? x0 : (cz != 0 ? moved + cz z : moved),   out_x0 = x0 (optional)
+ * x may alias out_x.  With the unconditional row a copy of the conditional one the parents give the same x0 (and the multistep parent the same
+ * out_x) bit for bit.  TMIX_EINVAL: null x / eps / out_x / params, a mode other than FUSION / PLAIN, FUSION without masks or K >= 1, a bad eps
+ * dtype, with keys the noise entry's n_win check.  TMIX_ESHAPE: channels / hw / seeds, rows < K (FUSION) or < 1 (PLAIN), with keys the noise
+ * entry's hw % w, seeds % n_win and window checks.  All before any launch. */
+int tmix_fused_tweedie_step_cond_dev(const float* x, const void* eps, int eps_dtype, const float* masks, int64_t mask_seed_stride,
+                                     float* out_x, float* out_x0, int K, int channels, int64_t hw, int mode, int rows, int seeds,
+                                     const float* params, float* x0_prev, const uint32_t* keys, int w, int n_win, const int* win_yx,
+                                     int canvas_h, int canvas_w, void* stream);
 /* Head of the captured step (fusion_sampling.py:324-327, `latent_model_input = torch.cat([x] * rows)`, and the timestep
  * argument of the UNet call :340): latent[(s*rows + r)][n] = x[s][n] for every row r, t_dev[s*rows + r] = params[0]. */
 int tmix_step_prologue(const float* x, float* latent, float* t_dev, const float* params, int seeds, int rows,

@@ -5,7 +5,8 @@
 // Compiled with -ffp-contract=off so fp32 results are bit-identical to the numpy restatement (solver.multistep_step_reference).
 // The image sampler's kernel and entries only: the same move on the video sampler's v-prediction is video_step.hip's.
 // The stochastic step (tmix_fused_tweedie_step_noise_dev) is this kernel with a trailing NoiseArgs: the move of either solver plus
-// cz * z, z from noise.h.
+// cz * z, z from noise.h.  The unguided step (tmix_fused_tweedie_step_cond_dev) is this kernel with a trailing CondArgs: eps rows
+// without the unconditional one, each used as it is, and a DDIM move on the eps consistent with the blended estimate.
 #include "step_core.h"
 #include "noise.h"
 
@@ -16,6 +17,11 @@ namespace {
 // the counter of its noise; keys [rows / n_win][2] are the trajectories' {low, high} key words.  The offsets travel by value, so a captured
 // launch carries them.  prm holds 12 floats then: the parent's 8, {cz, step index, 0, 0}.
 struct NoiseArgs { const uint32_t* keys; int n_win, w, canvas_w; int64_t canvas_hw; int oy[TMIX_MAX_WINDOWS], ox[TMIX_MAX_WINDOWS]; };
+// COND (tmix_fused_tweedie_step_cond_dev): one trailing CondArgs, an empty tag (behind the NoiseArgs when both are there; never with
+// a RescaleArgs).  eps holds NO unconditional row and every row's prediction is used as it is (step_core.h's blended_x0<.., COND>); like NOISE it
+// may come without a history buffer, and its DDIM move takes the eps that is consistent with the blended estimate in the place of the
+// unconditional row: e0 = (x - sa x0) / s1 in fp32 (0 where s1 == 0), moved = sa_next x0 + rnd(s1_next e0).
+struct CondArgs {};
 template <typename A, typename... T> constexpr bool pack_has = (__is_same(T, A) || ...);
 template <typename A, typename T0, typename... T> __device__ __forceinline__ const A& pack_get(const T0& t0, const T&... t) {
     if constexpr (__is_same(T0, A)) return t0; else return pack_get<A>(t...);
@@ -33,11 +39,12 @@ __global__ void __launch_bounds__(256)
 solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps, const float* __restrict__ masks, float* out_x,
                    float* __restrict__ out_x0, float* x0_prev, int K, int64_t n, int64_t hw, const float* __restrict__ prm, int rows,
                    int64_t mask_seed_stride, ExT... ex) {
-    constexpr bool RS = pack_has<RescaleArgs, ExT...>, NZ = pack_has<NoiseArgs, ExT...>;
-    static_assert(sizeof...(ExT) == (RS ? 1 : 0) + (NZ ? 1 : 0), "the trailing arguments are a RescaleArgs, a NoiseArgs or both");
+    constexpr bool RS = pack_has<RescaleArgs, ExT...>, NZ = pack_has<NoiseArgs, ExT...>, COND = pack_has<CondArgs, ExT...>;
+    static_assert(sizeof...(ExT) == (RS ? 1 : 0) + (NZ ? 1 : 0) + (COND ? 1 : 0) && !(RS && COND),
+                  "the trailing arguments are a RescaleArgs, a NoiseArgs or both, or a CondArgs behind an optional NoiseArgs");
     const float* fac = nullptr;
     if constexpr (RS) fac = pack_get<RescaleArgs>(ex...).fac + (int64_t)blockIdx.y * (rows - 1);
-    const bool ddim = NZ && !x0_prev;
+    const bool ddim = (NZ || COND) && !x0_prev;
     const float sa = prm[1], s1 = prm[2], cx = prm[3], c0 = prm[4], c1 = prm[5], g = prm[ddim ? 6 : 7];
     const bool is_last = prm[ddim ? 5 : 6] != 0.0f;
     const int64_t sd = blockIdx.y;
@@ -61,11 +68,14 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float xv = x[i];
         const float p = ddim ? 0.0f : x0_prev[i];
-        const float eu = EpsT<DT>::ld(eps, i);
-        const float x0 = blended_x0<DT, MODE, RS>(eps, masks, fac, K, n, hw, i, xv, eu, g, sa, s1);
+        float eu = 0.0f;
+        if constexpr (!COND) eu = EpsT<DT>::ld(eps, i);
+        const float x0 = blended_x0<DT, MODE, RS, COND>(eps, masks, fac, K, n, hw, i, xv, eu, g, sa, s1);
         float moved;
-        if (ddim) moved = cx * x0 + rnd<DT>(c0 * eu);            // prm[3], prm[4] hold sa_next, s1_next
-        else {
+        if (ddim) {                                  // prm[3], prm[4] hold sa_next, s1_next
+            if constexpr (COND) eu = s1 != 0.0f ? (xv - sa * x0) / s1 : 0.0f;       // e0: the eps consistent with x0 stands in for the missing row
+            moved = cx * x0 + rnd<DT>(c0 * eu);
+        } else {
             float m = c0 * x0;
             if (c1 != 0.0f) m = m + c1 * p;          // a first-order step never touches the history value: a NaN left there stays out
             moved = cx * xv + m;
@@ -84,7 +94,7 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
     }
 }
 
-template <int DT, typename... RsT>      // RsT: the kernel's trailing arguments -- none, {RescaleArgs}, {NoiseArgs} or {RescaleArgs, NoiseArgs}
+template <int DT, typename... RsT>      // RsT: the kernel's trailing arguments -- none, {RescaleArgs}, {NoiseArgs}, {RescaleArgs, NoiseArgs}, {CondArgs} or {NoiseArgs, CondArgs}
 int launch_ms(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, float* x0_prev, int K, int64_t n,
               int64_t hw, int mode, int rows, int seeds, const float* prm, hipStream_t st, RsT... rs) {
     typedef typename EpsT<DT>::T T;
@@ -96,6 +106,28 @@ int launch_ms(const float* x, const void* eps, const float* masks, int64_t mss, 
     else
         solver_step_kernel<DT, TMIX_STEP_PLAIN, RsT...><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss, rs...);
     TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+// The checks of a noise entry's window arguments and the NoiseArgs they give (tmix_fused_tweedie_step_noise_dev, tmix_fused_tweedie_step_cond_dev
+// with keys).  Without win_yx the latent is its own grid.
+int make_noise_args(const char* me, NoiseArgs& nz, const uint32_t* keys, int64_t hw, int seeds, int w, int n_win, const int* win_yx, int canvas_h,
+                    int canvas_w) {
+    if (n_win < 1 || n_win > TMIX_MAX_WINDOWS || (!win_yx && n_win != 1))
+        TMIX_FAIL(TMIX_EINVAL, "%s: n_win=%d (1..%d; without win_yx 1)", me, n_win, TMIX_MAX_WINDOWS);
+    if (w < 1 || hw % w != 0) TMIX_FAIL(TMIX_ESHAPE, "%s: hw=%lld is not a multiple of the row width w=%d", me, (long long)hw, w);
+    if (seeds % n_win != 0) TMIX_FAIL(TMIX_ESHAPE, "%s: seeds=%d is not a multiple of n_win=%d", me, seeds, n_win);
+    const int h = (int)(hw / w);
+    nz = {};
+    nz.keys = keys; nz.n_win = n_win; nz.w = w;
+    if (!win_yx) { canvas_h = h; canvas_w = w; }        // no canvas: the latent is its own grid
+    for (int k = 0; win_yx && k < n_win; ++k) {
+        const int oy = win_yx[2 * k], ox = win_yx[2 * k + 1];
+        if (oy < 0 || ox < 0 || oy > canvas_h - h || ox > canvas_w - w)
+            TMIX_FAIL(TMIX_ESHAPE, "%s: window %d at (%d, %d) of %d x %d reaches outside the %d x %d canvas", me, k, oy, ox, h, w, canvas_h, canvas_w);
+        nz.oy[k] = oy; nz.ox[k] = ox;
+    }
+    nz.canvas_w = canvas_w; nz.canvas_hw = (int64_t)canvas_h * canvas_w;
     return TMIX_OK;
 }
 
@@ -147,25 +179,30 @@ extern "C" int tmix_fused_tweedie_step_noise_dev(const float* x, const void* eps
                                                  int n_win, const int* win_yx, int canvas_h, int canvas_w, void* stream) {
     const char* me = "tweedie_step_noise_dev";
     if (int rc = check_dev_step(me, false, false, x, eps, out_x, params, nullptr, keys ? nullptr : "null keys", masks, K, channels, hw, mode, rows, seeds)) return rc;
-    if (n_win < 1 || n_win > TMIX_MAX_WINDOWS || (!win_yx && n_win != 1))
-        TMIX_FAIL(TMIX_EINVAL, "%s: n_win=%d (1..%d; without win_yx 1)", me, n_win, TMIX_MAX_WINDOWS);
-    if (w < 1 || hw % w != 0) TMIX_FAIL(TMIX_ESHAPE, "%s: hw=%lld is not a multiple of the row width w=%d", me, (long long)hw, w);
-    if (seeds % n_win != 0) TMIX_FAIL(TMIX_ESHAPE, "%s: seeds=%d is not a multiple of n_win=%d", me, seeds, n_win);
-    const int h = (int)(hw / w);
-    NoiseArgs nz = {};
-    nz.keys = keys; nz.n_win = n_win; nz.w = w;
-    if (!win_yx) { canvas_h = h; canvas_w = w; }        // no canvas: the latent is its own grid
-    for (int k = 0; win_yx && k < n_win; ++k) {
-        const int oy = win_yx[2 * k], ox = win_yx[2 * k + 1];
-        if (oy < 0 || ox < 0 || oy > canvas_h - h || ox > canvas_w - w)
-            TMIX_FAIL(TMIX_ESHAPE, "%s: window %d at (%d, %d) of %d x %d reaches outside the %d x %d canvas", me, k, oy, ox, h, w, canvas_h, canvas_w);
-        nz.oy[k] = oy; nz.ox[k] = ox;
-    }
-    nz.canvas_w = canvas_w; nz.canvas_hw = (int64_t)canvas_h * canvas_w;
+    NoiseArgs nz;
+    if (int rc = make_noise_args(me, nz, keys, hw, seeds, w, n_win, win_yx, canvas_h, canvas_w)) return rc;
     const int64_t n = (int64_t)channels * hw;
     const RescaleArgs rs = {factors};
     return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
         if (factors) return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, rs, nz);
         return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, nz);
+    });
+}
+
+// The unguided step: eps [seeds][rows][n] holds NO unconditional row; every row's prediction is used as it is.  x0_prev NULL: the
+// DDIM params layout and the move on the eps consistent with x0; else the multistep layout and move.  keys NULL: no noise (8 floats, the window
+// arguments are not read); else the noise entry's 12 floats and canvas indexing.
+extern "C" int tmix_fused_tweedie_step_cond_dev(const float* x, const void* eps, int eps_dtype, const float* masks, int64_t mask_seed_stride,
+                                                float* out_x, float* out_x0, int K, int channels, int64_t hw, int mode, int rows, int seeds,
+                                                const float* params, float* x0_prev, const uint32_t* keys, int w, int n_win, const int* win_yx,
+                                                int canvas_h, int canvas_w, void* stream) {
+    const char* me = "tweedie_step_cond_dev";
+    if (int rc = check_dev_step(me, false, false, x, eps, out_x, params, nullptr, nullptr, masks, K, channels, hw, mode, rows, seeds, true)) return rc;
+    NoiseArgs nz;
+    if (keys) if (int rc = make_noise_args(me, nz, keys, hw, seeds, w, n_win, win_yx, canvas_h, canvas_w)) return rc;
+    const int64_t n = (int64_t)channels * hw;
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        if (keys) return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, nz, CondArgs());
+        return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, CondArgs());
     });
 }

@@ -47,7 +47,9 @@ __device__ __forceinline__ RescaleArgs rescale_args(const RescaleArgs& r) { retu
 // The blended Tweedie estimate of element i, the x0 of EVERY fused step (fusion_sampling.py:376-385,392-403,406-412): CFG per eps row, the rescale
 // (RS), x0 per row, then the mask blend (FUSION), the one row (PLAIN) or (K-1)*x0_multi - sum_{c<K-1} x0_single_c (RESAMPLE).  eps / masks / fac are
 // the seed's own; xv = x[i], eu = the unconditional row's value at i.
-template <int DT, int MODE, bool RS>
+// COND (the unguided step; FUSION and PLAIN): eps has NO unconditional row -- row c is concept c's (PLAIN: row 0 the scene prompt's) -- and
+// e_c is the row's prediction itself: no CFG, no factor; eu, g and fac are not read.  Everything behind e_c is the same operations in the same order.
+template <int DT, int MODE, bool RS, bool COND = false>
 __device__ __forceinline__ float blended_x0(const typename EpsT<DT>::T* eps, const float* masks, const float* fac, int K, int64_t n, int64_t hw,
                                             int64_t i, float xv, float eu, float g, float sa, float s1) {
     float x0;
@@ -55,16 +57,21 @@ __device__ __forceinline__ float blended_x0(const typename EpsT<DT>::T* eps, con
         const int64_t p = i % hw;
         x0 = 0.0f;
         for (int c = 0; c < K; ++c) {
-            float e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
+            float e;
+            if constexpr (COND) e = EpsT<DT>::ld(eps, (int64_t)c * n + i);
+            else e = cfg<DT>(eu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), g);
             if constexpr (RS) e = rnd<DT>(fac[c] * e);
             const float t = (xv - rnd<DT>(s1 * e)) / sa;
             x0 = x0 + masks[(int64_t)c * hw + p] * t;
         }
     } else if constexpr (MODE == TMIX_STEP_PLAIN) {
-        float e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
+        float e;
+        if constexpr (COND) e = EpsT<DT>::ld(eps, i);
+        else e = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
         if constexpr (RS) e = rnd<DT>(fac[0] * e);
         x0 = (xv - rnd<DT>(s1 * e)) / sa;
     } else {
+        static_assert(!COND, "the unguided step has no RESAMPLE form");
         float em = cfg<DT>(eu, EpsT<DT>::ld(eps, n + i), g);
         if constexpr (RS) em = rnd<DT>(fac[0] * em);
         x0 = (float)(K - 1) * ((xv - rnd<DT>(s1 * em)) / sa);
@@ -123,12 +130,14 @@ template <typename F> int for_dtype(int dt, const char* me, const char* word, F&
     TMIX_FAIL(TMIX_EINVAL, "%s: bad %s %d", me, word, dt);
 }
 
-// The argument checks of the five device-parameter step entries (tmix_fused_tweedie_step_dev / _keep_dev / _rs_dev / _ms_dev / _ms_rs_dev), under
-// the entry's short name `me`.  resample: RESAMPLE is one of the entry's modes (the DDIM forms; the multistep forms take FUSION or PLAIN).
+// The argument checks of the device-parameter step entries (tmix_fused_tweedie_step_dev / _keep_dev / _rs_dev / _ms_dev / _ms_rs_dev / _noise_dev /
+// _cond_dev), under the entry's short name `me`.  resample: RESAMPLE is one of the entry's modes (the DDIM forms; the multistep forms take FUSION or PLAIN).
 // need_prev: the entry has the history buffer x0_prev, which must not be null.  missing: the entry's complaint about a null pointer of its own
 // (factors, the keep arrays), or nullptr when it has none to make; it is reported behind the shared pointers and in front of the mode.
+// cond: the entry's eps has no unconditional row (tmix_fused_tweedie_step_cond_dev), so a mode needs one row less.
 inline int check_dev_step(const char* me, bool resample, bool need_prev, const void* x, const void* eps, const void* out_x, const void* params,
-                          const void* x0_prev, const char* missing, const float* masks, int K, int channels, int64_t hw, int mode, int rows, int seeds) {
+                          const void* x0_prev, const char* missing, const float* masks, int K, int channels, int64_t hw, int mode, int rows, int seeds,
+                          bool cond = false) {
     if (!x || !eps || !out_x || !params) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
     if (need_prev && !x0_prev) TMIX_FAIL(TMIX_EINVAL, "%s: null x0_prev (the history buffer is read and written by every step)", me);
     if (missing) TMIX_FAIL(TMIX_EINVAL, "%s: %s", me, missing);
@@ -138,7 +147,7 @@ inline int check_dev_step(const char* me, bool resample, bool need_prev, const v
     if (mode == TMIX_STEP_FUSION && (!masks || K < 1)) TMIX_FAIL(TMIX_EINVAL, "%s: FUSION needs masks and K>=1", me);
     if (mode == TMIX_STEP_RESAMPLE && K < 1) TMIX_FAIL(TMIX_EINVAL, "%s: RESAMPLE needs K>=1", me);
     if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "%s: channels=%d hw=%lld seeds=%d", me, channels, (long long)hw, seeds);
-    const int need = mode == TMIX_STEP_PLAIN ? 2 : K + 1;
+    const int need = (mode == TMIX_STEP_PLAIN ? 2 : K + 1) - (cond ? 1 : 0);
     if (rows < need) TMIX_FAIL(TMIX_ESHAPE, "%s: mode %d needs %d eps rows per seed, got %d", me, mode, need, rows);
     return TMIX_OK;
 }

@@ -13,6 +13,9 @@ Everything here is host code and loads no library: the kernels (csrc/cfg_rescale
 
 The video sampler's form (the second half of this file) takes the statistics per video of the guided v-prediction and puts the
 rescaled prediction into x0 AND into the move's eps term.
+
+The guidance interval (between the two halves) is the other host-side definition about guidance kept here: which timesteps are
+guided, and the restatement of the step that runs without the unconditional row (tmix_fused_tweedie_step_cond_dev).
 """
 from __future__ import annotations
 
@@ -112,6 +115,87 @@ def rescaled_multistep_reference(mode, x, eps, masks, x0_prev, factors, g, sa, s
     K = 1 if mode == STEP_PLAIN else np.asarray(masks).shape[0]
     ep = rescaled_rows(eps[:K + 1], np.asarray(factors, F32)[:K], g, lowp)
     return SV.multistep_step_reference(mode, x, _as_guided(ep), masks, x0_prev, 1.0, sa, s1, cx, c0, c1, is_last, lowp)
+
+
+# ------------------------------------------------------------------------------------------------ guidance interval
+# Kynkaanniemi et al. 2024 (arXiv:2404.07724): guidance is applied on a middle range of noise levels only.  Here the range is a pair of TIMESTEP
+# values (t_hi, t_lo); a timestep is guided iff t_lo <= t <= t_hi.  An unguided trajectory step runs the UNet without the unconditional row and
+# tmix_fused_tweedie_step_cond_dev on what it returns.
+def validate_interval(interval, what="guidance_interval"):
+    """the ONE check of the interval (constructor, CLI): None, a 'T_HI,T_LO' string or a pair of integers with 1000 >= t_hi >= t_lo >= 0
+    -> None or (t_hi, t_lo) as ints"""
+    if interval is None:
+        return None
+    bad = ValueError(f"{what}={interval!r}: two integer timesteps T_HI,T_LO with 1000 >= T_HI >= T_LO >= 0 (a timestep t is guided iff T_LO <= t <= T_HI)")
+    if isinstance(interval, str):
+        parts = interval.split(",")
+        try:
+            interval = [int(p.strip()) for p in parts]       # int() refuses '7.5', '', 'a'
+        except ValueError:
+            raise bad from None
+    try:
+        vals = list(interval)
+    except TypeError:
+        raise bad from None
+    if len(vals) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in vals):
+        raise bad
+    hi, lo = int(vals[0]), int(vals[1])
+    if not 1000 >= hi >= lo >= 0:
+        raise bad
+    return hi, lo
+
+
+def is_guided(interval, t):
+    """is timestep t inside the interval (None: every timestep is)?"""
+    return interval is None or interval[1] <= int(t) <= interval[0]
+
+
+def cond_x0_reference(mode, x, eps, masks, sa, s1, lowp=None):
+    """the x0 of an unguided step, solver.blended_x0_reference's operations with e_c = the row itself: eps [rows, C, h, w] holds NO unconditional
+    row (FUSION: row c is concept c's, masks [K, 1, h, w]; PLAIN: row 0)"""
+    x, eps = np.asarray(x, F32), np.asarray(eps, F32)
+    if mode == STEP_PLAIN:
+        return SV._tweedie(x, eps[0:1], sa, s1, lowp)
+    if mode != STEP_FUSION:
+        raise ValueError(f"unguided step: mode {mode} (FUSION or PLAIN)")
+    masks = np.asarray(masks, F32)
+    x0 = np.zeros_like(x, dtype=F32)
+    for c in range(masks.shape[0]):
+        x0 = (x0 + masks[c][None] * SV._tweedie(x, eps[c:c + 1], sa, s1, lowp)).astype(F32)
+    return x0
+
+
+def cond_step_reference(mode, x, eps, masks, x0_prev, params, key=None, index=None, lowp=None):
+    """numpy fp32 restatement of tmix_fused_tweedie_step_cond_dev for one row -> (out_x, x0); x0 is also the new history when x0_prev is given.
+    x [1, C, h, w]; eps [rows, C, h, w] fp32 copies of values of the eps dtype, no unconditional row; params: the floats the entry reads --
+    {t, sa, s1, sa_next, s1_next, is_last, -, -} when x0_prev is None, else {t, sa, s1, cx, c0, c1, is_last, -}, and with key = (low word, high
+    word) four more, {cz, step index, 0, 0}; index: the canvas index of every element (noise.canvas_index), None = its own linear index.
+    lowp = np.float16 for fp16 eps.  Every product, sum and quotient is a separate fp32 operation.  Compared with the kernel by equality."""
+    x = np.asarray(x, F32)
+    p = [F32(v) for v in params]
+    sa, s1 = p[1], p[2]
+    x0 = cond_x0_reference(mode, x, eps, masks, sa, s1, lowp)
+    if x0_prev is None:
+        is_last = p[5] != 0
+        if s1 != 0:
+            e0 = ((x - (sa * x0).astype(F32)).astype(F32) / s1).astype(F32)
+        else:
+            e0 = np.zeros_like(x0)
+        moved = ((p[3] * x0).astype(F32) + SV._h((p[4] * e0).astype(F32), lowp)).astype(F32)
+    else:
+        is_last = p[6] != 0
+        m = (p[4] * x0).astype(F32)
+        if p[5] != 0:
+            m = (m + (p[5] * np.asarray(x0_prev, F32)).astype(F32)).astype(F32)
+        moved = ((p[3] * x).astype(F32) + m).astype(F32)
+    if is_last:
+        return x0, x0
+    if key is not None and p[8] != 0:
+        from . import noise as NZ
+        idx = np.arange(x.size, dtype=np.uint64).reshape(x.shape) if index is None else np.asarray(index, np.uint64).reshape(x.shape)
+        z = NZ.normal(idx, key[0], key[1], int(p[9]))
+        moved = (moved + (p[8] * z).astype(F32)).astype(F32)
+    return moved, x0
 
 
 # ------------------------------------------------------------------------------------------------ video sampler (v-prediction; DESIGN.md 7m)

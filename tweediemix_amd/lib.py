@@ -77,6 +77,7 @@ SIGNATURES = {
     "tmix_fused_tweedie_step_ms_rs_dev": (C.c_int, _DEV_STEP_MS + [vp, vp]),
     "tmix_noise_normal": (C.c_int, [vp, i64, i64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     "tmix_fused_tweedie_step_noise_dev": (C.c_int, _DEV_STEP + [vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, vp]),
+    "tmix_fused_tweedie_step_cond_dev": (C.c_int, _DEV_STEP + [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, vp]),
     "tmix_step_prologue": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, i64, vp]),
     "tmix_window_consensus": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "tmix_mask_edt": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),

@@ -191,6 +191,27 @@ def fused_tweedie_step_noise_dev(x, eps, masks, mode, K, params, keys, x0_prev=N
     return out_x
 
 
+def fused_tweedie_step_cond_dev(x, eps, masks, mode, K, params, x0_prev=None, keys=None, windows=None, canvas_hw=None, out_x=None, out_x0=None):
+    """tmix_fused_tweedie_step_cond_dev, the unguided step: eps [S*rows,C,h,w] f32|f16|bf16 holds NO unconditional row (FUSION:
+    rows >= K, row c concept c's; PLAIN: rows >= 1).  x0_prev None: params {t, sa, s1, sa_next, s1_next, is_last, -, -} and the DDIM move on the
+    eps consistent with x0; else the history buffer and {t, sa, s1, cx, c0, c1, is_last, -}.  keys None: no noise; else int32 [S / n_win, 2]
+    (noise_keys), params holds 12 floats and windows / canvas_hw are fused_tweedie_step_noise_dev's.  guidance.cond_step_reference gives the
+    same bits.  out_x may be x itself.  Returns out_x."""
+    _need_cuda(x, eps, masks, params, keys, x0_prev)
+    S, _n, _hw, _rows, out_x, head = _dev_step_head(x, eps, masks, mode, K, params, out_x, out_x0, x0_prev)
+    n_win = 1 if windows is None else len(windows)
+    if keys is not None:
+        assert params.numel() >= 12, params.numel()
+        assert keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() == 2 * (S // n_win) and S % n_win == 0, (tuple(keys.shape), S, n_win)
+    yx, ch, cw = None, 0, 0
+    if windows is not None:
+        yx = (C.c_int32 * (2 * n_win))(*[int(v) for o in windows for v in o])
+        ch, cw = int(canvas_hw[0]), int(canvas_hw[1])
+    L.check(L.load().tmix_fused_tweedie_step_cond_dev(*head, _p(x0_prev), _p(keys), x.shape[-1], n_win, yx, ch, cw, _stream()),
+            "tmix_fused_tweedie_step_cond_dev")
+    return out_x
+
+
 def window_consensus(x, groups, offsets, canvas_hw, weight=None):
     """tmix_window_consensus, in place on x [groups * n_win, C, h, w] fp32 (group-major: b = group * n_win + window): every canvas pixel
     that several windows cover becomes their weighted mean in all of them.  offsets [(oy, ox), ...] the windows' corners on the canvas

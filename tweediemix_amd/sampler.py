@@ -18,6 +18,8 @@ Same method names, argument meaning and step semantics as fusion_generation/fusi
   conditional prediction (tmix_cfg_rescale_factors in front of the *_rs_dev form of whichever step entry runs), in every step of every phase,
 * optionally (eta > 0) noise added by every step that advances the trajectory, generated inside the step kernel from (seed, schedule index,
   canvas coordinate) (tmix_fused_tweedie_step_noise_dev: one entry for the stochastic form of the DDIM, solver and rescale steps),
+* optionally (guidance_interval=(t_hi, t_lo)) trajectory steps at timesteps outside the interval that run the UNet without the unconditional row
+  (plan kinds "fusion_c" / "fusion_base_c" / "plain_c") and tmix_fused_tweedie_step_cond_dev on its rows,
 * ONE hipGraph per (call kind, step mode) holding the whole step -- latent broadcast + timestep
   (tmix_step_prologue), the UNet launch chains, the fused step for all co-batched seeds: a timestep is one 32-byte
   parameter upload and one graph replay.
@@ -37,7 +39,7 @@ import torch
 from . import lib as L
 from . import ops
 from .schedule import Schedule
-from .guidance import validate_phi
+from .guidance import is_guided, validate_interval, validate_phi
 from .plan import ParamRing
 from .solver import SOLVERS, ddim_eta_coeffs, multistep_coeffs, multistep_eta_coeffs, validate_eta
 from .unet import KVCache, PlanGroup, TokenMapSpec, TokenPropSpec, UNetPlan, UNetWeights
@@ -128,6 +130,15 @@ class Tweediemix:
                       the first timestep stays a DDIM step); the two definitions coincide at eta = 0 and 1.  Resampling round trips, the
                       look-ahead, the probe and the propagate rounds stay on today's entries.  Needs noise_seeds.  Not with set_keep.
                       DESIGN.md 7n.
+    guidance_interval None (every step is guided: today's entries, plan kinds, launches, graph keys, uploads and bits), or (t_hi, t_lo), integer
+                      TIMESTEPS with 1000 >= t_hi >= t_lo >= 0 (arXiv:2404.07724): a timestep t is guided iff t_lo <= t <= t_hi.  The
+                      trajectory-advancing fusion / plain step (DDIM or solver) of an unguided timestep behind the first runs the UNet WITHOUT
+                      the unconditional row (plan kinds "fusion_c" / "fusion_base_c": K rows, "plain_c": one row) and
+                      tmix_fused_tweedie_step_cond_dev on its rows: e_c is the conditional prediction itself, the DDIM move takes the eps
+                      consistent with the blended estimate, no rescale factors are computed (the factor of g = 1 is 1), and a solver step is
+                      second order only when the step before had the same guidedness.  The whole first timestep, the look-ahead, the probe and
+                      the propagate rounds stay guided.  An interval that holds every timestep of the schedule is None's run bit for bit.  Not
+                      with set_keep.  DESIGN.md 7q.
     noise_seeds       one integer (a 64-bit seed value) per trajectory the caller sees; set_noise_seeds replaces them between runs.  A
                       trajectory's noise depends on its own seed alone: not on what it is co-batched with, the GPU, graphs or windows.
     """
@@ -136,8 +147,9 @@ class Tweediemix:
                  concept_num: int, lora: bool = False, strict_reference: bool = True, use_graphs: bool = False,
                  n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None,
                  mask_soften=None, solver: str = "ddim", timestep_spacing: str = "leading", guidance_rescale: float = 0.0,
-                 eta: float = 0.0, noise_seeds=None):
+                 eta: float = 0.0, noise_seeds=None, guidance_interval=None):
         self.config = config
+        self.guidance_interval = validate_interval(guidance_interval)
         self.guidance_rescale = validate_phi(guidance_rescale)
         self.eta = validate_eta(eta)
         if self.eta > 0.0 and noise_seeds is None:
@@ -237,7 +249,7 @@ class Tweediemix:
         if noise_seeds is not None:
             self.set_noise_seeds(noise_seeds)
         # solver="dpmpp2m": the blended estimate of the solver step before (tmix_fused_tweedie_step_ms_dev reads and rewrites it; its steps
-        # upload {t, sa, s1, cx, c0, c1, is_last, g} into step_params instead) and which step wrote it: (schedule index, step mode) or None
+        # upload {t, sa, s1, cx, c0, c1, is_last, g} into step_params instead) and which step wrote it: (schedule index, step mode, guided) or None
         self._x0_prev = torch.zeros_like(self.x_state) if solver != "ddim" else None
         self._ms_last = None
         # guidance_rescale > 0: the factors [seeds][rows - 1] of the step being run and the fp64 workspace of their reduction, allocated once for
@@ -315,6 +327,8 @@ class Tweediemix:
         the fixed noise of every seed's kept part.  From the next run_fusion / sample_loop on every step writes
         weight * (sa' x0 + s1' eps) + (1 - weight) * (its own result), with sa' / s1' of the state it writes (tmix_fused_tweedie_step_keep_dev),
         x_T is composited the same way once, and the final latent holds x0 itself.  The tensors are copied: captured steps read these buffers."""
+        if self.guidance_interval is not None:      # the unguided entry holds no keep region
+            raise ValueError(f"set_keep: not with guidance_interval={self.guidance_interval} (the keep region exists on the guided step only)")
         if self.eta > 0.0:               # the kept part is re-noised with ONE fixed eps at every level: fresh noise has no place in it (DESIGN.md 7n)
             raise ValueError(f"set_keep: not with eta={self.eta} (the keep region exists on the deterministic step only)")
         if self.guidance_rescale > 0.0:  # a keep entry that takes factors does not exist (yet)
@@ -373,6 +387,12 @@ class Tweediemix:
             routed, wsel = False, [0] * (K + 1)
         elif kind in ("plain", "probe", "propagate"):
             ehs, pooled, routed, wsel = te[0:2], tp[0:2], False, [0, 0]
+        elif kind in ("fusion_c", "fusion_base_c"):   # the unguided twins (guidance_interval): the same rows without the unconditional one
+            ehs, pooled = te[2:2 + K], tp[2:2 + K]
+            routed = kind == "fusion_c" and self._routes(K + 1) and self.W.kind != "none"     # routed exactly where the guided twin is
+            wsel = list(range(1, K + 1)) if routed else [0] * K
+        elif kind == "plain_c":
+            ehs, pooled, routed, wsel = te[1:2], tp[1:2], False, [0]
         else:
             raise ValueError(kind)
         S = self.n_seeds
@@ -447,7 +467,7 @@ class Tweediemix:
 
     def _enqueue_step(self, kind, mode, ms=False, nz=False):
         """the launches of one denoising step on the current stream: prologue, UNet chains, fused step (in place; ms: the multistep entry;
-        nz: the noise entry in its DDIM or multistep form)."""
+        nz: the noise entry in its DDIM or multistep form; a kind without the unconditional row, "*_c": the unguided entry)."""
         p = self.plan(kind)
         S = self.n_seeds
         rows = p.B // S
@@ -457,19 +477,28 @@ class Tweediemix:
         L.check(lib.tmix_step_prologue(self.x_state.data_ptr(), p.latent.data_ptr(), p.t_dev.data_ptr(),
                                        self.step_params.data_ptr(), S, rows, n, st), "tmix_step_prologue")
         p.run()
-        self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st, ms, **(dict(nz=True) if nz else {}))
+        self._fused_step(p.eps.data_ptr(), L.F32, rows, mode, st, ms, **(dict(nz=True) if nz else {}), **(dict(cond=True) if kind.endswith("_c") else {}))
         if self.windows is not None:
             self._consensus(self.x_state)
 
-    def _fused_step(self, eps_ptr, eps_dt, rows, mode, st, ms=False, nz=False):
+    def _fused_step(self, eps_ptr, eps_dt, rows, mode, st, ms=False, nz=False, cond=False):
         """the fused step for every seed, in place on x_state; with a keep region set (set_keep) through the entry that holds it; ms: the
-        multistep entry, which also reads and rewrites the history buffer; nz: the noise entry (eta > 0), which is all four forms"""
+        multistep entry, which also reads and rewrites the history buffer; nz: the noise entry (eta > 0), which is all four forms; cond: the
+        eps rows hold no unconditional row (an unguided step): the one entry that is all four forms of it, and no rescale factors"""
         lib = L.load()
         m = self._mask_buf if mode == L.STEP_FUSION else None
         mss = 0 if (m is None or m.dim() == 4) else self.concept_num * self.h * self.w
         hw = self.h * self.w
         head = (self.x_state.data_ptr(), eps_ptr, eps_dt, None if m is None else m.data_ptr(), mss, self.x_state.data_ptr(),
                 self.x0_state.data_ptr(), self.concept_num, 4, hw, mode, rows, self.n_seeds, self.step_params.data_ptr())
+        if cond:                         # x0_prev / keys present or NULL select the move and the noise; the factor of an unguided row is exactly 1
+            yx = None
+            if nz and self.windows is not None:
+                yx = (C.c_int32 * (2 * len(self.windows)))(*[int(v) for o in self.windows for v in o])
+            L.check(lib.tmix_fused_tweedie_step_cond_dev(*head, self._x0_prev.data_ptr() if ms else None, self._noise_keys.data_ptr() if nz else None,
+                                                         self.w, 1 if yx is None else len(self.windows), yx, self.canvas_h, self.canvas_w, st),
+                    "tmix_fused_tweedie_step_cond_dev")
+            return
         if self.guidance_rescale > 0.0:  # the factors of these eps rows (g read on the device from the layout the step uploaded), then the rs form of the step
             if rows > self._rs_rows:
                 raise ValueError(f"guidance_rescale: {rows} eps rows per seed, the buffers were sized for {self._rs_rows}")
@@ -511,6 +540,7 @@ class Tweediemix:
             self.unet_calls.append((kind, self.plan(kind).B // self.n_seeds, int(t)))
         nz = step_index is not None
         nzk = dict(nz=True) if nz else {}                 # a deterministic step calls _enqueue_step / _fused_step with today's arguments
+        cond = kind.endswith("_c")                        # an unguided step: the kind has no unconditional row (guidance_interval)
         sa, s1, san, s1n = ops.step_coeffs(at, at_next)
         cz = 0.0
         if nz:
@@ -531,7 +561,7 @@ class Tweediemix:
             # module in): the same fused step, eagerly, on whatever eps dtype the stand-in returns
             eps = self._unet(kind, self.x_state, t).contiguous()
             self._fused_step(eps.data_ptr(), ops._EPS_DT[eps.dtype], eps.shape[0] // self.n_seeds, mode,
-                             torch.cuda.current_stream().cuda_stream, ms is not None, **nzk)
+                             torch.cuda.current_stream().cuda_stream, ms is not None, **nzk, **(dict(cond=True) if cond else {}))
             if self.windows is not None:
                 self._consensus(self.x_state)
             return
@@ -541,7 +571,7 @@ class Tweediemix:
         # a step captured with a keep region is another graph (another kernel, three more pointers): the ones captured without it stay valid
         # and so is a multistep step (another kernel, one more pointer): one graph serves both orders, the order is in the uploaded coefficients
         gkey = (kind, mode, "ms") if ms is not None else (kind, mode) if self._keep is None else (kind, mode, "keep")
-        if self.guidance_rescale > 0.0:                   # two more launches and another step kernel: graphs of their own
+        if self.guidance_rescale > 0.0 and not cond:      # two more launches and another step kernel: graphs of their own (an unguided step has neither)
             gkey = gkey + ("rs",)
         if nz:                                            # another entry, two more pointers and the window table: graphs of their own
             gkey = gkey + ("eta",)
@@ -642,18 +672,20 @@ class Tweediemix:
             if t not in self.scheduler.timesteps:
                 raise ValueError(f"eta={self.eta}: t = {t} is not one of the schedule's timesteps (the noise is indexed by the schedule entry)")
             adv = dict(step_index=self.scheduler.timesteps.index(t))
+        # guidance_interval: the trajectory step of a timestep outside it (behind the first timestep) runs without the unconditional row
+        c = "" if (t == self.start_t or is_guided(self.guidance_interval, t)) else "_c"
         if solver_step:
             self._solver_step(t, at, at_next, last)
         elif self._in_fusion(t):
             kind = "fusion" if (t in self._window) else "fusion_base"
-            self._run_step(kind, L.STEP_FUSION, t, at, at_next, last, **adv)
+            self._run_step(kind + c, L.STEP_FUSION, t, at, at_next, last, **adv)
         elif t == self.start_t:
             for _ in range(cfg.resampling_steps):
                 self._run_step("start", L.STEP_RESAMPLE, t, at, at_next)
                 self._run_step("plain", L.STEP_PLAIN, next_t, at_next, at)        # Tweedie at next_t, re-noise to t
             self._run_step("start", L.STEP_PLAIN, t, at, at_next, last, **adv)
         else:
-            self._run_step("plain", L.STEP_PLAIN, t, at, at_next, last, **adv)
+            self._run_step("plain" + c, L.STEP_PLAIN, t, at, at_next, last, **adv)
 
         if t == self.t_cond_prev:                       # fusion_sampling.py:431-469
             self._x_backup.copy_(self.x_state)          # the look-ahead does not move the trajectory
@@ -693,8 +725,9 @@ class Tweediemix:
 
     def _solver_step(self, t, at, at_next, last):
         """one trajectory step behind the first timestep through the multistep entry.  Second order exactly when the previous
-        _denoise_inplace call ran a solver step of the same mode on the preceding schedule entry -- so the first solver step, the first fusion
-        step, the first plain step behind a LoRA t_stop and any step asked for out of order are first order.  The whole first timestep, the
+        _denoise_inplace call ran a solver step of the same mode and the same guidedness (guidance_interval) on the preceding schedule entry
+        -- so the first solver step, the first fusion step, the first plain step behind a LoRA t_stop, the first step on either side of an
+        interval border and any step asked for out of order are first order.  The whole first timestep, the
         look-ahead and the propagate rounds run the DDIM entry and leave the history buffer alone."""
         ts = self.scheduler.timesteps
         if t not in ts:
@@ -704,7 +737,10 @@ class Tweediemix:
             kind, mode = ("fusion" if (t in self._window) else "fusion_base"), L.STEP_FUSION
         else:
             kind, mode = "plain", L.STEP_PLAIN
-        second = self._ms_last == (i - 1, mode)
+        guided = is_guided(self.guidance_interval, t)       # the data prediction jumps where g goes from 9 to 1: no extrapolation across a border
+        if not guided:
+            kind += "_c"
+        second = self._ms_last == (i - 1, mode, guided)
         # the last step writes x0 itself: its move (to alpha = 1, or on the 'leading' grid to the alpha it stands on) has no finite h
         if self.eta > 0.0:
             ms = (0.0, 1.0, 0.0, 0.0) if last else multistep_eta_coeffs(self.alpha(ts[i - 1]), at, at_next, second, self.eta)
@@ -712,7 +748,7 @@ class Tweediemix:
         else:
             ms = (0.0, 1.0, 0.0) if last else multistep_coeffs(self.alpha(ts[i - 1]), at, at_next, second)
             self._run_step(kind, mode, t, at, at_next, last, ms=ms)
-        self._ms_last = (i, mode)
+        self._ms_last = (i, mode, guided)
 
     def _propagate_rounds(self, t):
         """the token maps pushed propagate times through the self-attention of the last look-ahead call (input _x_look, timestep t): round
