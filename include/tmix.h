@@ -380,6 +380,36 @@ int tmix_vpred_step_hold_dev(float* x, const float* v_u, int64_t clip_stride_u, 
 int tmix_video_hold_composite(void* x, int dtype, int videos, int channels, int frames, int64_t hw, float ha, float hs, const uint32_t* keys,
                               const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames, const float* hold_w,
                               int64_t hold_w_video_stride, int hold_w_frames, void* stream);
+/* The UNGUIDED video step (the guidance interval of arXiv:2404.07724 in the video loop): a step outside the interval runs the text
+ * half alone.  Per element the operations are the guided entries' with v'' = v_c, the conditional prediction itself:
+ *   x0    = rnd(rnd(sa * x) - rnd(s1 * v_c))
+ *   DDIM  : eps = rnd(rnd(sa * v_c) + rnd(s1 * x)),  moved = rnd(rnd(a * x0) + rnd(b * eps))            (a, b) = (sa_next, s1_next or s1_dir)
+ *   2M    : moved = the multistep move of tmix_vpred_step_ms on (x, x0, x0_prev) with (a, b, c) = (cx, c0, c1); x0_prev <- x0
+ *   then `+ rnd(cz * z)` of tmix_vpred_step_noise and the blend of tmix_vpred_step_hold, exactly as in those entries.
+ * No CFG: there is no unconditional prediction, no g and no factors argument, and a -0.0 prediction keeps its sign.  With guidance rescale an
+ * unguided step uses these entries as well and no tmix_vpred_rescale_factors runs (at g = 1 the rescaled prediction is the conditional one).
+ * tmix_video_step_prologue_cond: tmix_video_step_prologue for the text half alone: x [videos][channels][frames][hw] fp32 -> channels [0, channels)
+ *   of x_c's frame rows [(clip*frames + f)][row_channels][hw] (clip s at s * clip_stride_c floats), params[0] -> t_c [videos].  Nothing else is
+ *   written.  TMIX_EINVAL on a null pointer, TMIX_ESHAPE on a bad shape or clip stride (tmix_video_step_prologue's checks).
+ * tmix_vpred_step_cond: the dense form in the model dtype: x, out [videos][channels][frames][hw] and v_c of the same shape (NOT [2 videos]); out may
+ *   alias x.  ONE entry for every form: x0_prev null: the DDIM move, else the multistep move and the fp32 history (read and rewritten); keys null:
+ *   no noise (cz and step are not read), else keys [videos][2] and the noise of tmix_vpred_step_noise; hold_x0 and hold_w both null: no hold, else
+ *   the hold of tmix_vpred_step_hold with (ha, hs).
+ * tmix_vpred_step_cond_dev: the form on plan rows, in place on x fp32: v_c the text half's prediction rows [(clip*frames + f)][channels][hw], clip s at
+ *   s * clip_stride_c floats.  params has the guided entries' layouts unchanged -- 8 floats without keys, 12 with ({.., cz, step_index, ha, hs}) -- so
+ *   a sampler uploads the same floats on guided and unguided steps; the g slot (5, or 6 in the multistep layout) is not read.
+ * Both step entries: TMIX_EINVAL on a null x, v_c, out / params; TMIX_ESHAPE on a bad shape or clip stride; TMIX_EINVAL on a bad dtype; then
+ * TMIX_EINVAL on a hold without keys and on exactly one of hold_x0 / hold_w null, TMIX_ESHAPE on the hold's frame counts and video strides as in
+ * tmix_vpred_step_hold; all before any launch; one launch on `stream`, capturable; no workspace. */
+int tmix_video_step_prologue_cond(const float* x, float* x_c, int64_t clip_stride_c, float* t_c, const float* params, int videos, int channels,
+                                  int frames, int64_t hw, int row_channels, void* stream);
+int tmix_vpred_step_cond(const void* x, const void* v_c, void* out, float* x0_prev, int dtype, int videos, int channels, int frames, int64_t hw,
+                         float sa, float s1, float a, float b, float c, float cz, const uint32_t* keys, uint32_t step, float ha, float hs,
+                         const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames, const float* hold_w,
+                         int64_t hold_w_video_stride, int hold_w_frames, void* stream);
+int tmix_vpred_step_cond_dev(float* x, const float* v_c, int64_t clip_stride_c, const float* params, int videos, int channels, int frames,
+                             int64_t hw, float* x0_prev, const uint32_t* keys, const float* hold_x0, int64_t hold_x0_video_stride,
+                             int hold_x0_frames, const float* hold_w, int64_t hold_w_video_stride, int hold_w_frames, void* stream);
 /* First-frame feature injection of the patched ResnetBlock2D.forward (video_gen/utils_attn.py:433-455), in place on
  * x [clips][frames][per_frame]: frames 1.. <- frame 0 (hard) or interp*frame0 + one_minus_interp*frame. */
 int tmix_frame_inject(void* x, int dtype, int clips, int frames, int64_t per_frame, int hard, float interp,

@@ -95,6 +95,11 @@ template <int DT, bool RS = false> __device__ __forceinline__ VPred vpred_x0(flo
     if constexpr (RS) vv = rnd<DT>(f * vv);
     return {vv, rnd<DT>(rnd<DT>(sa * xv) - rnd<DT>(s1 * vv))};
 }
+// the UNGUIDED element: v'' is the conditional prediction itself -- no CFG, no factor; neither an unconditional value nor g exists
+// here, and a -0.0 prediction keeps its sign (cfg(-0, -0, g) gives +0).  Everything behind v'' is the operations above in the same order.
+template <int DT> __device__ __forceinline__ VPred vpred_x0(float xv, float vc, float sa, float s1) {
+    return {vc, rnd<DT>(rnd<DT>(sa * xv) - rnd<DT>(s1 * vc))};
+}
 // the DDIM move of that element: eps from (x, v), then sa_n * x0 + s1_n * eps
 template <int DT> __device__ __forceinline__ float vpred_ddim_move(float xv, const VPred& p, float sa, float s1, float sa_n, float s1_n) {
     const float eps = rnd<DT>(rnd<DT>(sa * p.vv) + rnd<DT>(s1 * xv));

@@ -8,6 +8,8 @@
 // plus cz * z, z from noise.h (noise.vpred_step_reference restates it).
 // The hold (tmix_vpred_step_hold[_dev], tmix_video_hold_composite) is the same kernel again with a VideoHoldArgs behind the
 // VideoNoiseArgs: the stored value is hold_blend(moved, ...), the held part a clean latent at the written state's noise level under one fixed noise.
+// The unguided step of a guidance interval (tmix_video_step_prologue_cond, tmix_vpred_step_cond[_dev]) is the same kernel over a
+// COND view: one prediction per element, the conditional one, and no CFG (guidance.vpred_cond_step_reference restates it).
 #include "step_core.h"
 #include "noise.h"
 
@@ -21,6 +23,7 @@ struct StepCoef { float g, sa, s1, a, b, c; };
 // (element i of every array is read before it is written), so the view both moves share promises nothing about its pointers.
 template <int D> struct DenseView {
     static constexpr int DT = D;
+    static constexpr bool COND = false;
     typedef typename EpsT<D>::T T;
     const T* x; const T* v; T* out; int64_t n; StepCoef k;
     template <bool MS> __device__ __forceinline__ StepCoef coef() const { return k; }
@@ -34,10 +37,33 @@ template <int D> struct DenseView {
 // prm = {t, sa, s1, sa_next, s1_next, g, 0, 0} for the DDIM move and {t, sa, s1, cx, c0, c1, g, 0} for the multistep move.
 struct RowsView {
     static constexpr int DT = TMIX_F32;
+    static constexpr bool COND = false;
     float* x; const float* v_u; int64_t su; const float* v_c; int64_t sc; const float* prm; int C, F; int64_t hw;
     template <bool MS> __device__ __forceinline__ StepCoef coef() const { return {prm[MS ? 6 : 5], prm[1], prm[2], prm[3], prm[4], MS ? prm[5] : 0.0f}; }
     __device__ __forceinline__ float xv(int64_t i) const { return x[i]; }
     __device__ __forceinline__ float vu(int64_t i) const { return v_u[video_row_offset(i, C, F, hw, C, su)]; }
+    __device__ __forceinline__ float vc(int64_t i) const { return v_c[video_row_offset(i, C, F, hw, C, sc)]; }
+    __device__ __forceinline__ void st(int64_t i, float o) const { x[i] = o; }
+};
+// COND (the unguided step): the same views without an unconditional prediction -- vu does not exist, the kernel takes step_core.h's
+// unguided vpred_x0 and reads ONE prediction per element.  Dense: v [videos][per] is the conditional prediction alone; plan rows: the text half's
+// prediction rows alone.  The parameter layouts are the parents' (g is still uploaded at slot 5 or 6) and g is not read: coef() leaves it 0.
+template <int D> struct DenseCondView {
+    static constexpr int DT = D;
+    static constexpr bool COND = true;
+    typedef typename EpsT<D>::T T;
+    const T* x; const T* v; T* out; StepCoef k;
+    template <bool MS> __device__ __forceinline__ StepCoef coef() const { return k; }
+    __device__ __forceinline__ float xv(int64_t i) const { return EpsT<D>::ld(x, i); }
+    __device__ __forceinline__ float vc(int64_t i) const { return EpsT<D>::ld(v, i); }
+    __device__ __forceinline__ void st(int64_t i, float o) const { StT<D>::st(out, i, o); }
+};
+struct RowsCondView {
+    static constexpr int DT = TMIX_F32;
+    static constexpr bool COND = true;
+    float* x; const float* v_c; int64_t sc; const float* prm; int C, F; int64_t hw;
+    template <bool MS> __device__ __forceinline__ StepCoef coef() const { return {0.0f, prm[1], prm[2], prm[3], prm[4], MS ? prm[5] : 0.0f}; }
+    __device__ __forceinline__ float xv(int64_t i) const { return x[i]; }
     __device__ __forceinline__ float vc(int64_t i) const { return v_c[video_row_offset(i, C, F, hw, C, sc)]; }
     __device__ __forceinline__ void st(int64_t i, float o) const { x[i] = o; }
 };
@@ -91,6 +117,7 @@ template <typename A, typename B> __device__ __forceinline__ const B& pack_secon
 // NzT: nothing, or {VideoNoiseArgs}: the stored value is then cz != 0 ? rnd(moved + rnd(cz * z)) : moved -- one product and one sum behind the
 // parent's operations, and no generator call at cz == 0 (rs.per is read for the video of i, so the launcher always fills it); or
 // {VideoNoiseArgs, VideoHoldArgs}: the stored value is then hold_blend of that one.
+// View::COND: v'' is the view's one prediction (no vu, no g, no factor; never with RS); the moves, the noise and the hold behind it are the same lines.
 template <typename View, bool MS, bool RS, typename... NzT>
 __global__ void __launch_bounds__(256)
 video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const RescaleArgs rs, const NzT... nz) {
@@ -119,7 +146,11 @@ video_step_kernel(const View vw, float* __restrict__ x0_prev, int64_t n, const R
         float p = 0.0f, f = 1.0f;
         if constexpr (MS) p = x0_prev[i];
         if constexpr (RS) f = rs.fac[i / rs.per];
-        const VPred e = vpred_x0<DT, RS>(xv, vw.vu(i), vw.vc(i), k.g, k.sa, k.s1, f);
+        VPred e;
+        if constexpr (View::COND) {
+            static_assert(!RS, "the unguided step has no rescale form: at g = 1 the rescaled prediction is the conditional one");
+            e = vpred_x0<DT>(xv, vw.vc(i), k.sa, k.s1);
+        } else e = vpred_x0<DT, RS>(xv, vw.vu(i), vw.vc(i), k.g, k.sa, k.s1, f);
         float moved;
         if constexpr (MS) moved = vpred_ms_move<DT>(xv, e.x0, p, k.a, k.b, k.c);
         else moved = vpred_ddim_move<DT>(xv, e, k.sa, k.s1, k.a, k.b);
@@ -153,6 +184,15 @@ int launch_video_step(const View& vw, float* x0_prev, int64_t n, const RescaleAr
 template <typename F> int for_form(bool ms, bool rs, F&& f) {
     if (ms) return rs ? f(std::true_type(), std::true_type()) : f(std::true_type(), std::false_type());
     return rs ? f(std::false_type(), std::true_type()) : f(std::false_type(), std::false_type());
+}
+
+// the unguided entries' form: nz null: no trailing argument; hd null: the noise alone; else the noise and the hold.  Never RS; no factor exists.
+template <bool MS, typename View>
+int launch_cond_step(const View& vw, float* x0_prev, int64_t n, int64_t per, hipStream_t st, const VideoNoiseArgs* nz, const VideoHoldArgs* hd) {
+    const RescaleArgs rs = {nullptr, per};
+    if (nz && hd) return launch_video_step<MS, false>(vw, x0_prev, n, rs, st, *nz, *hd);
+    if (nz) return launch_video_step<MS, false>(vw, x0_prev, n, rs, st, *nz);
+    return launch_video_step<MS, false>(vw, x0_prev, n, rs, st);
 }
 
 // the four dense entries: videos x per elements (the forms without the rescale: 1 x n, answered as "empty latent")
@@ -191,6 +231,19 @@ video_prologue_kernel(const float* __restrict__ x, float* __restrict__ xu, int64
     if (blockIdx.x == 0) {
         const float t = prm[0];
         for (int k = threadIdx.x; k < videos; k += blockDim.x) { tu[k] = t; tc[k] = t; }
+    }
+}
+
+// head of the captured UNGUIDED step: the text half alone -- the unconditional half's inputs are not named, so not touched
+__global__ void __launch_bounds__(256)
+video_prologue_cond_kernel(const float* __restrict__ x, float* __restrict__ xc, int64_t sc, float* __restrict__ tc, const float* __restrict__ prm,
+                           int videos, int C, int F, int64_t hw, int row_channels, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        xc[video_row_offset(i, C, F, hw, row_channels, sc)] = x[i];
+    if (blockIdx.x == 0) {
+        const float t = prm[0];
+        for (int k = threadIdx.x; k < videos; k += blockDim.x) tc[k] = t;
     }
 }
 
@@ -400,4 +453,70 @@ extern "C" int tmix_video_hold_composite(void* x, int dtype, int videos, int cha
         TMIX_LAUNCH_CHECK();
         return TMIX_OK;
     });
+}
+
+// ---- the unguided step: the text half alone.  The prologue fills the text half's inputs; ONE step entry per layout serves every
+// form -- x0_prev null: the DDIM move (a, b) = (sa_next, s1_next or s1_dir), else the multistep move (a, b, c) and the history buffer; keys null:
+// no noise (cz and step are not read) and then no hold either; hold_x0 and hold_w both null: no hold.  No g, no factors: neither is an argument.
+extern "C" int tmix_video_step_prologue_cond(const float* x, float* x_c, int64_t clip_stride_c, float* t_c, const float* params, int videos,
+                                             int channels, int frames, int64_t hw, int row_channels, void* stream) {
+    const char* me = "video_step_prologue_cond";
+    if (!x || !x_c || !t_c || !params) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
+    if (int rc = check_video_step(me, videos, channels, frames, hw, row_channels, true, clip_stride_c, clip_stride_c)) return rc;
+    const int64_t n = (int64_t)videos * channels * frames * hw;
+    int64_t blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
+    video_prologue_cond_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, x_c, clip_stride_c, t_c, params, videos, channels, frames, hw,
+                                                                                  row_channels, n);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
+namespace {
+// the unguided entries' own answers behind check_vpred_step: a hold needs the videos' keys (its fixed noise is keyed by them), then check_hold
+// (one of hold_x0 / hold_w null: EINVAL).  *held: is there a hold?
+inline int check_cond_hold(const char* me, const uint32_t* keys, const float* hold_x0, int64_t x0_stride, int x0_frames, const float* hold_w,
+                           int64_t w_stride, int w_frames, int channels, int frames, int64_t hw, bool* held) {
+    *held = hold_x0 || hold_w;
+    if (!*held) return TMIX_OK;
+    if (!keys) TMIX_FAIL(TMIX_EINVAL, "%s: a hold without keys (the held part's fixed noise is keyed by the video)", me);
+    return check_hold(me, hold_x0, x0_stride, x0_frames, hold_w, w_stride, w_frames, channels, frames, hw);
+}
+}  // namespace
+
+extern "C" int tmix_vpred_step_cond(const void* x, const void* v_c, void* out, float* x0_prev, int dtype, int videos, int channels, int frames,
+                                    int64_t hw, float sa, float s1, float a, float b, float c, float cz, const uint32_t* keys, uint32_t step,
+                                    float ha, float hs, const float* hold_x0, int64_t hold_x0_video_stride, int hold_x0_frames,
+                                    const float* hold_w, int64_t hold_w_video_stride, int hold_w_frames, void* stream) {
+    const char* me = "vpred_step_cond";
+    const int64_t clip = (int64_t)(channels > 0 ? channels : 0) * (frames > 0 ? frames : 0) * (hw > 0 ? hw : 0);
+    if (int rc = check_vpred_step(me, x && v_c && out, false, nullptr, false, nullptr, dtype, false, false, videos, channels, frames, hw, clip, clip)) return rc;
+    bool held;
+    if (int rc = check_cond_hold(me, keys, hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, channels, frames, hw, &held)) return rc;
+    const int64_t per = (int64_t)channels * frames * hw, n = (int64_t)videos * per;
+    const StepCoef k = {0.0f, sa, s1, a, b, x0_prev ? c : 0.0f};
+    const VideoNoiseArgs nz = {keys, nullptr, cz, step};
+    const VideoHoldArgs hd = {hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, nullptr, ha, hs, frames, hw};
+    return for_dtype(dtype, me, "dtype", [&](auto dt) {
+        typedef typename EpsT<dt()>::T T;
+        const DenseCondView<dt()> vw = {(const T*)x, (const T*)v_c, (T*)out, k};
+        if (x0_prev) return launch_cond_step<true>(vw, x0_prev, n, per, (hipStream_t)stream, keys ? &nz : nullptr, held ? &hd : nullptr);
+        return launch_cond_step<false>(vw, nullptr, n, per, (hipStream_t)stream, keys ? &nz : nullptr, held ? &hd : nullptr);
+    });
+}
+
+// params: the parents' layouts -- 8 floats without keys ({t, sa, s1, sa_next, s1_next, g, 0, 0} / {t, sa, s1, cx, c0, c1, g, 0}), 12 with
+// (then {cz, schedule index, ha, hs}); the g slot is not read
+extern "C" int tmix_vpred_step_cond_dev(float* x, const float* v_c, int64_t clip_stride_c, const float* params, int videos, int channels, int frames,
+                                        int64_t hw, float* x0_prev, const uint32_t* keys, const float* hold_x0, int64_t hold_x0_video_stride,
+                                        int hold_x0_frames, const float* hold_w, int64_t hold_w_video_stride, int hold_w_frames, void* stream) {
+    const char* me = "vpred_step_cond_dev";
+    if (int rc = check_vpred_step(me, x && v_c && params, false, nullptr, false, nullptr, TMIX_F32, false, false, videos, channels, frames, hw, clip_stride_c, clip_stride_c)) return rc;
+    bool held;
+    if (int rc = check_cond_hold(me, keys, hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, channels, frames, hw, &held)) return rc;
+    const int64_t per = (int64_t)channels * frames * hw;
+    const RowsCondView vw = {x, v_c, clip_stride_c, params, channels, frames, hw};
+    const VideoNoiseArgs nz = {keys, params, 0.0f, 0u};
+    const VideoHoldArgs hd = {hold_x0, hold_x0_video_stride, hold_x0_frames, hold_w, hold_w_video_stride, hold_w_frames, params, 0.0f, 0.0f, frames, hw};
+    if (x0_prev) return launch_cond_step<true>(vw, x0_prev, videos * per, per, (hipStream_t)stream, keys ? &nz : nullptr, held ? &hd : nullptr);
+    return launch_cond_step<false>(vw, nullptr, videos * per, per, (hipStream_t)stream, keys ? &nz : nullptr, held ? &hd : nullptr);
 }

@@ -15,7 +15,8 @@ The video sampler's form (the second half of this file) takes the 
 rescaled prediction into x0 AND into the move's eps term.
 
 The guidance interval (between the two halves) is the other host-side definition about guidance kept here: which timesteps are
-guided, and the restatement of the step that runs without the unconditional row (tmix_fused_tweedie_step_cond_dev).
+guided, and the restatement of the step that runs without the unconditional row (tmix_fused_tweedie_step_cond_dev).  The video sampler's unguided
+step (tmix_vpred_step_cond / tmix_vpred_step_cond_dev) is restated in the second half, vpred_cond_step_reference.
 """
 from __future__ import annotations
 
@@ -150,6 +151,11 @@ def is_guided(interval, t):
     return interval is None or interval[1] <= int(t) <= interval[0]
 
 
+def unguided_count(interval, timesteps):
+    """how many of the schedule's timesteps lie outside the interval (None: 0)"""
+    return sum(0 if is_guided(interval, t) else 1 for t in timesteps)
+
+
 def cond_x0_reference(mode, x, eps, masks, sa, s1, lowp=None):
     """the x0 of an unguided step, solver.blended_x0_reference's operations with e_c = the row itself: eps [rows, C, h, w] holds NO unconditional
     row (FUSION: row c is concept c's, masks [K, 1, h, w]; PLAIN: row 0)"""
@@ -254,6 +260,60 @@ def vpred_rescaled_step_reference(x, v, factors, g, sa, s1, sa_next, s1_next, lo
     if lp is not lowp:
         out = SV._bf16_round(out)
     return out, x0
+
+
+def vpred_cond_step_reference(x, v_c, x0_prev, sa, s1, move, cz=0.0, keys=None, step=0, hold=None, lowp=None):
+    """numpy restatement of tmix_vpred_step_cond and (lowp None) tmix_vpred_step_cond_dev, the UNGUIDED video step -> (out, x0),
+    written from the definition: v'' = v_c, the conditional prediction itself -- no CFG, no g, no factor.
+      x0    = rnd(rnd(sa x) - rnd(s1 v_c))
+      DDIM  (x0_prev None, move = (sa_n, s1_n)):  eps = rnd(rnd(sa v_c) + rnd(s1 x)),  moved = rnd(rnd(sa_n x0) + rnd(s1_n eps))
+      2M    (x0_prev the fp32 history, move = (cx, c0, c1)):  m = rnd(c0 x0), c1 != 0: m = rnd(m + rnd(c1 x0_prev)),  moved = rnd(rnd(cx x) + m)
+      keys [B] of (low word, high word) and cz != 0:  moved = rnd(moved + rnd(cz z)), z of noise.vpred_step_reference (schedule index `step`)
+      hold = (kx, w, ha, hs) (needs keys):  moved = noise.hold_blend_reference(moved, ...)
+    x, v_c [B, ...] hold fp32 copies of values of the model dtype.  lowp: None; np.float16 (rnd rounds to fp16 everywhere, x0 included);
+    "bf16" (fp32 arithmetic, ONE rounding of out at the store).  Compared with both kernels by equality."""
+    from . import noise as NZ
+    x, vc = np.asarray(x, F32), np.asarray(v_c, F32)
+    if vc.shape != x.shape:
+        raise ValueError(f"vpred_cond_step_reference: v_c {vc.shape} for a state {x.shape} (the conditional prediction alone)")
+    bf16 = isinstance(lowp, str) and lowp == "bf16"
+    lp = _lp(lowp)
+    h = lambda a: SV._h(np.asarray(a, F32), lp)
+    sa, s1 = F32(sa), F32(s1)
+    m_ = [F32(c) for c in move]
+    x0 = h(h(sa * x) - h(s1 * vc)).astype(F32)
+    if x0_prev is None:
+        eps = h(h(sa * vc) + h(s1 * x))
+        moved = h(h(m_[0] * x0) + h(m_[1] * eps))
+    else:
+        m = h(m_[1] * x0)
+        if m_[2] != 0:
+            m = h(m + h(m_[2] * np.asarray(x0_prev, F32)))
+        moved = h(h(m_[0] * x) + m)
+    moved = moved.astype(F32)
+    if hold is not None and keys is None:
+        raise ValueError("vpred_cond_step_reference: a hold without keys")
+    if keys is not None and len(keys) != x.shape[0]:
+        raise ValueError(f"vpred_cond_step_reference: {len(keys)} keys for {x.shape[0]} videos")
+    if keys is not None and F32(cz) != 0:
+        idx = np.arange(x[0].size, dtype=np.uint64).reshape(x[0].shape)
+        z = np.stack([NZ.normal(idx, k[0], k[1], int(step), NZ.STREAM_VIDEO_STEP) for k in keys])
+        moved = h(moved + h(F32(cz) * z)).astype(F32)
+    if hold is not None:
+        kx, w, ha, hs = hold
+        moved = NZ.hold_blend_reference(moved, kx, w, ha, hs, keys, lp)
+    return (SV._bf16_round(moved) if bf16 else h(moved).astype(F32)), x0
+
+
+def vpred_cond_step_from_params(x, v_c, x0_prev, params, keys=None, hold=None):
+    """vpred_cond_step_reference on the floats tmix_vpred_step_cond_dev reads: the guided step's 8 ({t, sa, s1, sa_n, s1_n, g, 0, 0} when x0_prev is
+    None, else {t, sa, s1, cx, c0, c1, g, 0}) without keys, 12 (then {cz, schedule index, ha, hs}) with; hold = (kx, w).  The g slot is not read."""
+    p = [F32(v) for v in params]
+    if len(p) < (8 if keys is None else 12):
+        raise ValueError(f"vpred_cond_step_from_params: {len(p)} floats")
+    move = (p[3], p[4]) if x0_prev is None else (p[3], p[4], p[5])
+    cz, step = (p[8], int(p[9])) if keys is not None else (0.0, 0)
+    return vpred_cond_step_reference(x, v_c, x0_prev, p[1], p[2], move, cz, keys, step, None if hold is None else (hold[0], hold[1], p[10], p[11]))
 
 
 def vpred_rescaled_multistep_reference(x, v, x0_prev, factors, g, sa, s1, cx, c0, c1, lowp=None):

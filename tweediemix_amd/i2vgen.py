@@ -446,7 +446,8 @@ class I2VVideoPlan:
     HIP stream -- a dependent chain leaves the chip idle at every kernel boundary, the other half's chain fills the holes (as the image
     sampler's PlanGroup; measured 103 -> 97 ms per step at one 16 x 768 x 448 video); streams=1: one I2VPlan(clips=2S).  `halves` are
     the (input rows, timestep input, prediction rows) of the unconditional and the text half; the sampler's kernels read and write them
-    in place, so no copy or permute sits between the chains and the step."""
+    in place, so no copy or permute sits between the chains and the step.  `cond_half` / `run_cond()` / `cond_flops` are the same three, the run
+    and the work of the S text clips ALONE, for the unguided step of a guidance interval."""
 
     def __init__(self, W: I2VWeights, videos: int, frames: int, h: int, w: int, fps_emb, context, il_feat, streams: int = 2,
                  autotune: bool = True, interp: float = 0.7):
@@ -464,15 +465,45 @@ class I2VVideoPlan:
             self.halves = [(p.x_in[i * S * Fr:(i + 1) * S * Fr], p.t_dev[i * S:(i + 1) * S], p.eps[i * S * Fr:(i + 1) * S * Fr]) for i in range(2)]
         self.flops = sum(p.flops for p in self.plans)
         self.ops = [op for p in self.plans for op in p.ops]
+        # the unguided step runs the text half alone.  streams=2: that IS plans[1].  streams=1: the text clips sit inside the one
+        # 2S-clip chain, so a chain of their own, I2VPlan(clips=S), is built on the first unguided step from what is kept here.
+        self._cond = self.plans[1] if streams == 2 else None
+        self._cond_args = None if streams == 2 else (W, fps_emb[S:], context[S:], il_feat[S:], autotune)
+        self.cond_flops = self.plans[1].flops if streams == 2 else self.flops // 2       # every launch's work is linear in the clip count
 
-    inject = property(lambda self: self.plans[0].inject, lambda self, v: [setattr(p, "inject", v) for p in self.plans])
-    interp = property(lambda self: self.plans[0].interp, lambda self, v: [setattr(p, "interp", v) for p in self.plans])
+    def _chains(self):
+        return self.plans if self._cond is None or self._cond in self.plans else self.plans + [self._cond]
+
+    inject = property(lambda self: self.plans[0].inject, lambda self, v: [setattr(p, "inject", v) for p in self._chains()])
+    interp = property(lambda self: self.plans[0].interp, lambda self, v: [setattr(p, "interp", v) for p in self._chains()])
 
     def refine(self, **kw):
         return refine_group(self, **kw)
 
     def run(self):
         run_chains(self.plans, self.streams)
+
+    @property
+    def cond_plan(self):
+        """the chain of the S text clips alone.  streams=1: built on first use (outside any capture: it allocates, tunes and synchronises) with
+        its own _KV and activation buffers, on the text rows of the conditioning, and with the flags the other chain holds at that moment."""
+        if self._cond is None:
+            W, fps_emb, context, il_feat, autotune = self._cond_args
+            p = I2VPlan(W, self.videos, self.frames, self.h, self.w, fps_emb, context, il_feat, autotune=autotune, interp=self.interp)
+            p.inject = self.inject
+            self._cond = p
+        return self._cond
+
+    @property
+    def cond_half(self):
+        """(input rows, timestep input, prediction rows) of the unguided step: the text half's own at streams=2"""
+        p = self.cond_plan
+        return p.x_in, p.t_dev, p.eps
+
+    def run_cond(self):
+        """the text half alone on the current stream: no fork, no events -- a captured unguided step has no parallel branch.  streams=2: the
+        launches run() records for that half, so its prediction rows are the guided step's text rows bit for bit."""
+        self.cond_plan.run()
 
 
 class I2VPlanGroup(I2VVideoPlan):

@@ -136,6 +136,10 @@ SIGNATURES = {
                                        f32, f32, vp, i64, C.c_int, vp, i64, C.c_int, vp]),
     "tmix_vpred_step_hold_dev": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, vp, i64, C.c_int, vp, i64, C.c_int, vp]),
     "tmix_video_hold_composite": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, f32, f32, vp, vp, i64, C.c_int, vp, i64, C.c_int, vp]),
+    "tmix_video_step_prologue_cond": (C.c_int, [vp, vp, i64, vp, vp, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp]),
+    "tmix_vpred_step_cond": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, f32, f32, f32, f32, f32, f32, vp, C.c_uint32,
+                                       f32, f32, vp, i64, C.c_int, vp, i64, C.c_int, vp]),
+    "tmix_vpred_step_cond_dev": (C.c_int, [vp, vp, i64, vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, i64, C.c_int, vp, i64, C.c_int, vp]),
     "tmix_gemm_tile_shape": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tmix_gemm_stats_parts": (C.c_int, [C.c_int, C.c_int]),
     "tmix_gemm_resolve_tile": (C.c_int, [C.POINTER(GemmDesc), C.c_int]),

@@ -1194,6 +1194,58 @@ def video_step_params_hold(t, g, at, coeffs_or_next, cz, step_index, at_written,
     return _fill_params(head + [float(np.float32(cz)), float(int(step_index)), *hold_coeffs(at_written)], out)
 
 
+def video_step_prologue_cond(x, x_c, t_c, params, clip_stride_c=None):
+    """tmix_video_step_prologue_cond, the head of an unguided video step: video_step_prologue for the text half alone -- x
+    [S,C,F,h,w] fp32 -> channels [0, C) of x_c's frame rows [(S*F), R, h, w], params[0] -> t_c [S]; nothing else is written."""
+    _need_cuda(x, x_c, t_c, params)
+    R = x_c.shape[1]
+    S, Cc, Fr, hw, _, sc = _plan_rows(x, x_c, x_c, R, clip_stride_c, clip_stride_c)
+    assert t_c.numel() >= S
+    L.check(L.load().tmix_video_step_prologue_cond(_p(x), _p(x_c), sc, _p(t_c), _p(params), S, Cc, Fr, hw, R, _stream()),
+            "tmix_video_step_prologue_cond")
+
+
+def _cond_hold(hold_x0, hold_w, at_written, S, Cc, Fr, h, w):
+    """(ha, hs, the six hold arguments) of the unguided entries; no hold: nulls"""
+    if hold_x0 is None and hold_w is None:
+        return 0.0, 0.0, None, 0, 1, None, 0, 1
+    return (*hold_coeffs(at_written), *_video_hold(hold_x0, hold_w, S, Cc, Fr, h, w))
+
+
+def vpred_step_cond(x, v_c, at, move, x0_prev=None, cz=0.0, keys=None, step=0, at_written=None, hold_x0=None, hold_w=None, out=None):
+    """tmix_vpred_step_cond, the unguided video step on the model dtype: x, v_c [B,C,F,h,w] of one dtype -- v_c is the
+    conditional prediction alone, no CFG is applied.  x0_prev None: the DDIM move, move = (sa_next, s1_next or s1_dir); else the fp32 history and
+    move = (cx, c0, c1).  keys int32 [B, 2] (noise_keys) with cz and step: the noise of vpred_step_noise; hold_x0 / hold_w with at_written: the hold
+    of vpred_step_hold (needs keys).  out may be x.  guidance.vpred_cond_step_reference gives the same bits.  Returns the next latents."""
+    _need_cuda(x, v_c, x0_prev, keys, hold_x0, hold_w)
+    assert x.dim() == 5 and x.is_contiguous() and v_c.is_contiguous() and v_c.numel() == x.numel() and v_c.dtype == x.dtype
+    out = torch.empty_like(x) if out is None else out
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    sa, s1 = step_coeffs(at, at)[:2]
+    B, Cc, Fr, h, w = x.shape
+    a, b, c = (float(m) for m in (tuple(move) + (0.0,))[:3])
+    prev = None if x0_prev is None else _history(x0_prev, x)
+    assert 0 <= int(step) < 2 ** 32, step
+    ha, hs, *hold = _cond_hold(hold_x0, hold_w, at_written, B, Cc, Fr, h, w)
+    L.check(L.load().tmix_vpred_step_cond(_p(x), _p(v_c), _p(out), prev, _EPS_DT[x.dtype], B, Cc, Fr, h * w, sa, s1, a, b, c, float(cz),
+                                          None if keys is None else _video_keys(keys, B), int(step), ha, hs, *hold, _stream()), "tmix_vpred_step_cond")
+    return out
+
+
+def vpred_step_cond_dev(x, v_c, params, x0_prev=None, keys=None, hold_x0=None, hold_w=None, clip_stride_c=None):
+    """tmix_vpred_step_cond_dev, the unguided video step on plan rows, in place on x [S,C,F,h,w] fp32: v_c the text half's prediction rows
+    [(S*F), C, h, w] (clip s at s * clip_stride floats); params the floats of the guided step that would run -- video_step_params[_ms] (8) without
+    keys, video_step_params_noise / _hold (12) with -- of which g is not read.  Returns x."""
+    _need_cuda(x, v_c, params, x0_prev, keys, hold_x0, hold_w)
+    S, Cc, Fr, hw, _, sc = _plan_rows(x, v_c, v_c, x.shape[1], clip_stride_c, clip_stride_c)
+    assert params.dtype == torch.float32 and params.numel() >= (8 if keys is None else 12), params.numel()
+    prev = None if x0_prev is None else _history(x0_prev, x)
+    hold = _cond_hold(hold_x0, hold_w, None, S, Cc, Fr, x.shape[3], x.shape[4])[2:]
+    L.check(L.load().tmix_vpred_step_cond_dev(_p(x), _p(v_c), sc, _p(params), S, Cc, Fr, hw, prev, None if keys is None else _video_keys(keys, S),
+                                              *hold, _stream()), "tmix_vpred_step_cond_dev")
+    return x
+
+
 def frame_inject(x, clips, frames, interp=None):
     """first-frame feature injection (video_gen/utils_attn.py:433-455), in place on x [(clips*frames), ...] contiguous."""
     _need_cuda(x)

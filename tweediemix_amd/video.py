@@ -95,7 +95,9 @@ class SolverPhase:
     """the host's bookkeeping of solver="dpmpp2m": coeffs(t) -> the (cx, c0, c1) of the step at t and remembers it.  A step is second order
     exactly when the previous coeffs() call was for the preceding schedule entry, first order otherwise (the first step, any out-of-order or
     off-grid call); the injection state does not enter.  coeffs(t, eta) -> (cx, c0, c1, cz) of the SDE form of the same step
-    (solver.video_multistep_eta_coeffs; eta = 0.0 gives coeffs(t)'s three values bit for bit and cz == 0.0), with the same bookkeeping."""
+    (solver.video_multistep_eta_coeffs; eta = 0.0 gives coeffs(t)'s three values bit for bit and cz == 0.0), with the same bookkeeping.
+    Under a guidance interval the loops call set_previous(None) in front of a step whose predecessor had the other guidedness
+    (_at_border): the data prediction jumps where g goes from 9 to 1, so a border step is first order."""
 
     def __init__(self, schedule: VideoSchedule):
         self.schedule, self.prev = schedule, None
@@ -116,6 +118,15 @@ class SolverPhase:
         out = video_multistep_coeffs(t, a_prev, a, a_next, second) if eta is None else video_multistep_eta_coeffs(t, a_prev, a, a_next, second, eta)
         self.prev = i
         return out
+
+
+def _at_border(phase, guided, prev_guided):
+    """the order rule of a guidance interval, in front of the step that is about to ask `phase` (a SolverPhase, or None without the
+    solver) for its coefficients: where the step's guidedness differs from its predecessor's the history holds an x0 of the other kind and is not
+    usable -- set_previous(None), so the border step is first order.  -> guided, the next call's prev_guided (True in front of the first step)"""
+    if phase is not None and bool(guided) != bool(prev_guided):
+        phase.set_previous(None)
+    return bool(guided)
 
 
 def alphas_from_scheduler_config(cfg: dict):
@@ -247,7 +258,8 @@ def _hold_step(schedule, t, eta, phase):
 
 @torch.no_grad()
 def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None,
-                solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None, hold=None):
+                solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None, hold=None, guidance_interval=None,
+                unet_cond=None):
     """pipeline_i2vgen_xl.py:680-719.  unet(latent_model_input [2B,C,F,H,W], t) -> v-prediction of the same shape (the
     caller closes over prompt/image conditioning; an i2vgen plan behind it needs its `inject` flag set for t, from
     injection_active); latents [B,C,F,H,W] on the GPU in the model dtype.  solver="dpmpp2m": every step is tmix_vpred_step_ms on the
@@ -256,10 +268,16 @@ def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_s
     eta > 0 with noise_seeds, one integer per video: every step is tmix_vpred_step_noise, the same move plus cz * z with z a
     function of (the video's seed, the schedule index, the element's index in its video); 0 is the loop without it, launch for launch.
     hold = (x0, weight) with noise_seeds: x_T is composited once (tmix_video_hold_composite, on a copy) and every step is
-    tmix_vpred_step_hold, which keeps x0 under the weight at the noise level of the state it writes; None is the loop without it."""
-    from .guidance import validate_phi
+    tmix_vpred_step_hold, which keeps x0 under the weight at the noise level of the state it writes; None is the loop without it.
+    guidance_interval = (t_hi, t_lo): a timestep outside it is unguided -- unet_cond(latents [B,C,F,H,W], t) -> the conditional
+    v-prediction [B,...] alone, then tmix_vpred_step_cond (no factors launch, whatever guidance_rescale is); a solver step next to a border is
+    first order.  None, or an interval holding every timestep, is the loop without it, launch for launch."""
+    from .guidance import is_guided, validate_interval, validate_phi
     ms = _check_solver(solver)
     phi = validate_phi(guidance_rescale)
+    interval = validate_interval(guidance_interval)
+    if unet_cond is None and any(not is_guided(interval, t) for t in schedule.timesteps):
+        raise ValueError(f"guidance_interval={interval}: the schedule has unguided timesteps and unet_cond, the network on the text half alone, is None")
     eta, seeds = _check_eta(eta, noise_seeds, latents.shape[0])
     hold = _check_hold(hold, seeds, *latents.shape)
     x = latents.contiguous()
@@ -269,6 +287,7 @@ def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_s
         x = ops.video_hold_composite(x.clone(), schedule.alpha(int(schedule.timesteps[0])), keys, hx, hw_)
     if ms:
         phase, hist = SolverPhase(schedule), torch.zeros_like(x, dtype=torch.float32)
+    was_guided = True
     if phi > 0.0:
         B = x.shape[0]
         g_dev = torch.zeros(8, device=x.device, dtype=torch.float32)
@@ -277,6 +296,22 @@ def sample_loop(unet, latents: torch.Tensor, schedule: VideoSchedule, guidance_s
     for t in schedule.timesteps:
         if injector is not None:
             injector.register_time(t)
+        if ms and interval is not None:
+            was_guided = _at_border(phase, is_guided(interval, t), was_guided)      # a border step is first order
+        if not is_guided(interval, t):                    # the text half alone: no CFG, no factors launch
+            v = unet_cond(x, int(t)).contiguous()
+            phs = phase if ms else None
+            at, hist_ = schedule.alpha(int(t)), hist if ms else None
+            if hold is not None:
+                move, cz, i, aw = _hold_step(schedule, int(t), eta, phs)
+                x = ops.vpred_step_cond(x, v, at, move, hist_, cz, keys, i, aw, hx, hw_)
+            elif eta > 0.0:
+                move, cz, i = _noise_step(schedule, int(t), eta, phs)
+                x = ops.vpred_step_cond(x, v, at, move, hist_, cz, keys, i)
+            else:
+                move = phase.coeffs(int(t)) if ms else ops.step_coeffs(at, schedule.next_alpha(int(t)))[2:]
+                x = ops.vpred_step_cond(x, v, at, move, hist_)
+            continue
         v = unet(torch.cat([x, x]), int(t)).contiguous()
         if phi > 0.0:
             ops.vpred_rescale_factors(v, g_dev, 0, phi, out=fac, ws=ws)
@@ -333,11 +368,20 @@ class VideoSampler:
     the noise entry (cz = 0 at eta = 0) followed by the blend at the noise level of the state it writes ((1, 0) on the last step: the final latent
     IS x0 wherever the weight is 1).  `hold_x0`, `hold_w` and `noise_keys` sit at fixed addresses (set_hold rewrites their contents), params is
     12 floats with (ha, hs) in slots 10 and 11, the graph keys gain a trailing "hold", and a step stays one 48-byte upload and one replay.
-    hold = None is the sampler without it: no new launch, buffer, graph key or upload size."""
+    hold = None is the sampler without it: no new launch, buffer, graph key or upload size.
+
+    guidance_interval = (t_hi, t_lo) (guidance.validate_interval): a timestep outside it is unguided and its step is
+    tmix_video_step_prologue_cond (state and t into the text half's inputs alone) -> plan.run_cond() (the text half's chain alone, on the current
+    stream) -> tmix_vpred_step_cond_dev in the form of whichever step entry would run (history, keys, hold arrays) -- S clips instead of 2S, no
+    factors launch whatever guidance_rescale is.  The uploaded floats are the guided step's (g is not read), so a step stays one 32- or 48-byte
+    upload and one replay; the graph key is the guided key without "rs" and with a trailing "cond": (inject, "cond"), (inject, "ms", "eta",
+    "hold", "cond").  A solver step whose predecessor had the other guidedness is first order (SolverPhase).  None, or an interval that holds
+    every timestep of the schedule, is the sampler without it: no new launch, buffer, graph key or upload size."""
 
     def __init__(self, plan, schedule: VideoSchedule, guidance_scale: float, injector: FeatureInjector | None = None, use_graphs: bool = True,
-                 solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None, hold=None):
-        from .guidance import validate_phi
+                 solver: str = "ddim", guidance_rescale: float = 0.0, eta: float = 0.0, noise_seeds=None, hold=None, guidance_interval=None):
+        from .guidance import validate_interval, validate_phi
+        self.guidance_interval = validate_interval(guidance_interval)                     # host only: refused before the GPU is touched
         self.plan, self.schedule, self.g, self.injector, self.use_graphs = plan, schedule, float(guidance_scale), injector, use_graphs
         self.solver, self.ms = solver, _check_solver(solver)
         self.guidance_rescale = validate_phi(guidance_rescale)
@@ -361,6 +405,7 @@ class VideoSampler:
         self.graphs = {}
         self.x0_prev = torch.zeros_like(self.state) if self.ms else None
         self.phase = SolverPhase(schedule) if self.ms else None
+        self._was_guided = True                           # the guidedness of the step before (read under a guidance interval only)
         self.rs_factors = self._rs_ws = None
         if self.guidance_rescale > 0.0:                   # allocated once; the workspace needs no initial contents
             self.rs_factors = torch.ones(plan.videos, device=dev, dtype=torch.float32)
@@ -389,6 +434,13 @@ class VideoSampler:
     def _write_keys(self):
         self.noise_keys.copy_(ops.noise_keys(self._noise_seeds, self.noise_keys.device))
         self._keys_stale = False
+
+    def _enqueue_cond(self):
+        """the unguided step: the text half alone, then the COND form of the step entry that would run; no factors launch"""
+        xc, tc, ec = self.plan.cond_half
+        ops.video_step_prologue_cond(self.state, xc, tc, self.params)
+        self.plan.run_cond()
+        ops.vpred_step_cond_dev(self.state, ec, self.params, x0_prev=self.x0_prev, keys=self.noise_keys, hold_x0=self.hold_x0, hold_w=self.hold_w)
 
     def _enqueue(self):
         (xu, tu, eu), (xc, tc, ec) = self.plan.halves
@@ -437,9 +489,15 @@ class VideoSampler:
             self.plan.inject, self.plan.interp = inject, self.injector.interp
         if self._keys_stale:                              # a step() outside sample() after new seeds
             self._write_keys()
+        guided = True
+        if self.guidance_interval is not None:            # without an interval nothing below differs from the sampler without the feature
+            from .guidance import is_guided
+            guided = is_guided(self.guidance_interval, t)
+            self._was_guided = _at_border(self.phase, guided, self._was_guided)      # a border step is first order
+        enqueue = self._enqueue if guided else self._enqueue_cond
         self._upload(t)
         if not self.use_graphs:
-            self._enqueue()
+            enqueue()
             return
         key = (inject, "ms") if self.ms else inject
         if self.guidance_rescale > 0.0:
@@ -448,15 +506,17 @@ class VideoSampler:
             key = (key if isinstance(key, tuple) else (inject,)) + ("eta",)
         if self.hold_x0 is not None:
             key = (key if isinstance(key, tuple) else (inject,)) + ("hold",)
+        if not guided:                                    # the guided key without "rs", then "cond"
+            key = tuple(k for k in (key if isinstance(key, tuple) else (inject,)) if k != "rs") + ("cond",)
         g = self.graphs.get(key)
         if g is None:
-            self._enqueue()                               # warm-up outside capture; it has already performed this step
+            enqueue()                                     # warm-up outside capture; it has already performed this step
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             keep = self.state.clone()
             keep_h = self.x0_prev.clone() if self.ms else None
             with torch.cuda.graph(g):
-                self._enqueue()
+                enqueue()
             self.state.copy_(keep)
             if self.ms:
                 self.x0_prev.copy_(keep_h)
