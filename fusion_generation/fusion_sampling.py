@@ -77,6 +77,13 @@ the loop through the HF hub (checkpoint download) takes local paths here:
                          (DESIGN.md 7q).  Timestep values, not schedule indices: the interval keeps its noise range under --timestep_spacing
                          logsnr.  Without the flag, or with an interval that holds every timestep of the schedule: today's run bit for bit.
                          Does not combine with --keep_latents / --keep_image
+  --apg                  adaptive projected guidance (Sadat, Hilliges and Weber, arXiv:2410.02416): every guided step forms its guidance on the
+                         rows' Tweedie estimates, splits the update D_c - D_u into the part parallel to the conditional estimate D_c (the one
+                         that inflates contrast and saturation at a high --guidance_scale) and the rest, keeps the rest, scales the parallel
+                         part by --apg_eta ETA (default 0; 1 is CFG) and clips the update's norm over one UNet row at --apg_norm R (default 0:
+                         no clip).  Statistics are per UNet row (on a canvas: per window); two small launches per guided step, no UNet call
+                         (DESIGN.md 7s).  No momentum.  Without the flag: today's run bit for bit; --apg_eta / --apg_norm without it are
+                         refused.  Does not combine with --guidance_rescale, --keep_latents / --keep_image
   --num_seeds N          N trajectories, seeds seed..seed+N-1 (trajectory i is exactly what `--seed seed+i` alone produces: its
                          x_T comes from its own generator), co-batched --seeds_per_batch at a time
   --gpus G               shard those seeds round-robin over G GPUs of this node: the script starts one process per GPU itself
@@ -175,6 +182,11 @@ def build_parser():
     p.add_argument('--guidance_interval', type=str, default='',
                    help='T_HI,T_LO: integer timesteps, 1000 >= T_HI >= T_LO >= 0; trajectory steps at timesteps outside [T_LO, T_HI] use the '
                         'conditional prediction alone and run the UNet without the unconditional row (default: every step is guided)')
+    p.add_argument('--apg', action='store_true',
+                   help='adaptive projected guidance (arXiv:2410.02416): guidance on the Tweedie estimates, the part of the update parallel to the '
+                        'conditional estimate scaled by --apg_eta, the update\'s norm clipped at --apg_norm (default: off)')
+    p.add_argument('--apg_eta', type=float, default=0.0, help='ETA in [0, 1]: weight of the parallel part of the update under --apg (0: dropped; 1: CFG)')
+    p.add_argument('--apg_norm', type=float, default=0.0, help='R >= 0: clip of the update\'s norm over one UNet row under --apg (0: no clip)')
     p.add_argument('--timestep_spacing', type=str, default='leading', choices=['leading', 'logsnr'],
                    help="logsnr: n_timesteps uniform in log-SNR from the 'leading' grid's first timestep down to t = 1")
     p.add_argument('--num_seeds', type=int, default=1, help='trajectories to sample: seeds seed..seed+n-1')
@@ -355,8 +367,8 @@ def save_soft_weights(opt, tw, side_dir):
 
 
 def check_solver_args(opt):
-    """--solver / --timestep_spacing / --guidance_rescale / --eta / --guidance_interval: refuses what the sampler would refuse, before anything
-    touches the GPU.  opt.guidance_interval becomes None or (t_hi, t_lo)."""
+    """--solver / --timestep_spacing / --guidance_rescale / --eta / --guidance_interval / --apg: refuses what the sampler would refuse, before
+    anything touches the GPU.  opt.guidance_interval becomes None or (t_hi, t_lo), opt.apg None or dict(eta, norm_threshold)."""
     from tweediemix_amd.guidance import validate_interval
     try:
         opt.guidance_interval = validate_interval(opt.guidance_interval or None, '--guidance_interval')
@@ -385,6 +397,22 @@ def check_solver_args(opt):
     if phi > 0.0 and (opt.keep_latents or opt.keep_image):
         flag = '--keep_latents' if opt.keep_latents else '--keep_image'
         raise SystemExit(f'--guidance_rescale {phi} does not combine with {flag}: the keep region exists on the unscaled step only')
+    # --apg: opt.apg becomes None or dict(eta, norm_threshold), what Tweediemix(apg=...) takes
+    from tweediemix_amd.guidance import validate_apg
+    if not opt.apg:
+        if opt.apg_eta != 0.0 or opt.apg_norm != 0.0:
+            raise SystemExit(f'--apg_eta {opt.apg_eta} / --apg_norm {opt.apg_norm} set the adaptive projected guidance of --apg: give --apg too')
+        opt.apg = None
+    else:
+        try:
+            opt.apg = validate_apg(dict(eta=opt.apg_eta, norm_threshold=opt.apg_norm), '--apg')
+        except ValueError:
+            raise SystemExit(f'--apg_eta {opt.apg_eta} --apg_norm {opt.apg_norm}: ETA in [0, 1] and R >= 0 (0: no clip), both finite')
+        if phi > 0.0:
+            raise SystemExit(f'--apg does not combine with --guidance_rescale {phi}: both re-shape the guided prediction and no order between them is defined')
+        if opt.keep_latents or opt.keep_image:
+            flag = '--keep_latents' if opt.keep_latents else '--keep_image'
+            raise SystemExit(f'--apg does not combine with {flag}: the keep region exists on the step without adaptive projected guidance only')
     if opt.timestep_spacing == 'logsnr':
         from tweediemix_amd.schedule import Schedule
         try:
@@ -651,6 +679,7 @@ def main(argv=None):
                       fp8=(opt.dtype == 'fp8'), attention_masks=attn, mask_soften=soften,
                       solver=opt.solver, timestep_spacing=opt.timestep_spacing, guidance_rescale=opt.guidance_rescale,
                       eta=opt.eta, noise_seeds=([opt.seed] * per if opt.eta > 0.0 else None), guidance_interval=opt.guidance_interval,
+                      **(dict(apg=opt.apg) if opt.apg else {}),
                       **(dict(canvas={k: canvas[k] for k in ('height', 'width', 'overlap')}) if canvas else {}))
     if vae_scaling:                                       # fusion_sampling.py:518 divides by vae.config.scaling_factor
         tw.vae_scaling_factor = float(vae_scaling)

@@ -7,7 +7,10 @@
 // very values the step kernel will scale.
 // Second entry, the same method per VIDEO for the v-prediction step kernels (tmix_vpred_rescale_factors): one accumulation function
 // (rescale_partial_sums) and one finalise kernel serve both.
+// Third entry, the same method for adaptive projected guidance (tmix_apg_coeffs): three sums of products of the rows' Tweedie
+// estimates over the same partition, and per (seed, row) the two coefficients the APG step kernel combines them with.
 #include "step_core.h"
+#include "../../include/tmix_apg.h"
 
 namespace {
 
@@ -120,7 +123,102 @@ int launch_vpred_rescale(const void* vu, int64_t su, const void* vc, int64_t sc,
     return TMIX_OK;
 }
 
+// ---- APG (adaptive projected guidance): the same two launches on the rows' Tweedie estimates.
+// grid (RS_P, rows - 1, seeds).  Workgroup (p, r - 1, s) writes {Sdd, Sdc, Scc, 0} of its share of eps row r of seed s to slot ws[s][r - 1][p]:
+// d and tc are step_core.h's apg_term (the fp32 values the step kernel combines), products and sums in fp64.  A workgroup without elements
+// writes zeros.  Rows the mode does not read (r > used) are left alone: finalise does not read them.
+template <int DT>
+__global__ void __launch_bounds__(RS_THREADS)
+apg_partials_kernel(const float* __restrict__ x, const typename EpsT<DT>::T* __restrict__ eps, double* __restrict__ ws, int64_t n, int rows, int used,
+                    const float* __restrict__ prm) {
+    const int r = blockIdx.y + 1;
+    if (r > used) return;
+    const int64_t sd = blockIdx.z;
+    const float sa = prm[1], s1 = prm[2];
+    const float* xs = x + sd * n;
+    const typename EpsT<DT>::T* eu = eps + sd * rows * n;
+    const typename EpsT<DT>::T* ec = eu + (int64_t)r * n;
+    double dd = 0.0, dc = 0.0, cc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x; i < n; i += (int64_t)RS_P * RS_THREADS) {
+        const float xv = xs[i];
+        const ApgTerm t = apg_term<DT>(xv, apg_tu<DT>(xv, EpsT<DT>::ld(eu, i), sa, s1), EpsT<DT>::ld(ec, i), sa, s1);
+        const double d = (double)t.d, c = (double)t.tc;
+        dd = dd + d * d; dc = dc + d * c; cc = cc + c * c;
+    }
+    dd = wave_sum(dd); dc = wave_sum(dc); cc = wave_sum(cc);
+    __shared__ double part[RS_WAVES][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { part[wave][0] = dd; part[wave][1] = dc; part[wave][2] = cc; part[wave][3] = 0.0; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double a = part[0][threadIdx.x];
+        for (int w = 1; w < RS_WAVES; ++w) a = a + part[w][threadIdx.x];
+        ws[((sd * (rows - 1) + (r - 1)) * RS_P + blockIdx.x) * 4 + threadIdx.x] = a;
+    }
+}
+
+// one lane per (seed, row): the RS_P partials in index order, then in fp64 s = R / sqrt(Sdd) where R > 0 and Sdd > R^2 (else 1),
+// p = s Sdc / Scc (0 where Scc is not positive), A = 1 - (g - 1)(1 - eta) p, B = (g - 1) s, each rounded once to fp32.
+// {1, g - 1} -- CFG in data space -- where a sum is not finite, and for the rows the mode does not read.
+__global__ void __launch_bounds__(RS_THREADS)
+apg_finalise_kernel(const double* __restrict__ ws, float* __restrict__ coeffs, int rows, int used, int seeds, const float* __restrict__ prm, int g_slot,
+                    float eta, float norm_threshold) {
+    const int idx = blockIdx.x * RS_THREADS + threadIdx.x;
+    if (idx >= seeds * (rows - 1)) return;
+    const double gm1 = (double)prm[g_slot] - 1.0;
+    double A = 1.0, B = gm1;
+    if (idx % (rows - 1) < used) {
+        const double* p = ws + (int64_t)idx * RS_P * 4;
+        double dd = 0.0, dc = 0.0, cc = 0.0;
+        for (int k = 0; k < RS_P; ++k) { dd = dd + p[4 * k]; dc = dc + p[4 * k + 1]; cc = cc + p[4 * k + 2]; }
+        if (isfinite(dd) && isfinite(dc) && isfinite(cc)) {
+            const double R = (double)norm_threshold;
+            const double s = (R > 0.0 && dd > R * R) ? R / sqrt(dd) : 1.0;
+            const double pr = cc > 0.0 ? s * dc / cc : 0.0;
+            A = 1.0 - gm1 * (1.0 - (double)eta) * pr;
+            B = gm1 * s;
+        }
+    }
+    coeffs[2 * idx] = (float)A;
+    coeffs[2 * idx + 1] = (float)B;
+}
+
+template <int DT>
+int launch_apg(const float* x, const void* eps, float* coeffs, double* ws, int64_t n, int rows, int used, int seeds, const float* prm, int g_slot,
+               float eta, float norm_threshold, hipStream_t st) {
+    typedef typename EpsT<DT>::T T;
+    apg_partials_kernel<DT><<<dim3(RS_P, (unsigned)(rows - 1), (unsigned)seeds), RS_THREADS, 0, st>>>(x, (const T*)eps, ws, n, rows, used, prm);
+    TMIX_LAUNCH_CHECK();
+    const int lanes = seeds * (rows - 1);
+    apg_finalise_kernel<<<(unsigned)((lanes + RS_THREADS - 1) / RS_THREADS), RS_THREADS, 0, st>>>(ws, coeffs, rows, used, seeds, prm, g_slot, eta,
+                                                                                                 norm_threshold);
+    TMIX_LAUNCH_CHECK();
+    return TMIX_OK;
+}
+
 }  // namespace
+
+// APG coefficients: x [seeds][n] fp32 the state the step will read, eps [seeds][rows][n]; coeffs [seeds][rows - 1][2] = {A, B};
+// ws: tmix_cfg_rescale_ws_doubles(rows, seeds) doubles (four per slot, three used), written before read.  g = params[g_slot], sa = params[1],
+// s1 = params[2] are read on the device.  eta in [0, 1] scales the part of the update parallel to the conditional estimate (1: CFG);
+// norm_threshold >= 0 clips the update's norm (0: no clip).
+extern "C" int tmix_apg_coeffs(const float* x, const void* eps, int eps_dtype, float* coeffs, double* ws, int K, int channels, int64_t hw, int mode,
+                               int rows, int seeds, const float* params, int g_slot, float eta, float norm_threshold, void* stream) {
+    const char* me = "apg_coeffs";
+    if (!x || !eps || !coeffs || !ws || !params) TMIX_FAIL(TMIX_EINVAL, "%s: null pointer", me);
+    if (eps_dtype != TMIX_F32 && eps_dtype != TMIX_F16 && eps_dtype != TMIX_BF16) TMIX_FAIL(TMIX_EINVAL, "%s: bad eps dtype %d", me, eps_dtype);
+    if (mode < TMIX_STEP_FUSION || mode > TMIX_STEP_RESAMPLE) TMIX_FAIL(TMIX_EINVAL, "%s: bad mode %d", me, mode);
+    if (mode != TMIX_STEP_PLAIN && K < 1) TMIX_FAIL(TMIX_EINVAL, "%s: mode %d needs K>=1", me, mode);
+    if (g_slot < 0 || g_slot > 7) TMIX_FAIL(TMIX_EINVAL, "%s: g_slot %d outside 0..7", me, g_slot);
+    if (!(eta >= 0.0f && eta <= 1.0f)) TMIX_FAIL(TMIX_EINVAL, "%s: eta %g outside [0, 1]", me, (double)eta);
+    if (!(norm_threshold >= 0.0f) || __builtin_isinf(norm_threshold)) TMIX_FAIL(TMIX_EINVAL, "%s: norm_threshold %g is not a finite number >= 0", me, (double)norm_threshold);
+    if (channels < 1 || hw < 1 || seeds < 1 || seeds > 65535) TMIX_FAIL(TMIX_ESHAPE, "%s: channels=%d hw=%lld seeds=%d", me, channels, (long long)hw, seeds);
+    const int used = mode == TMIX_STEP_PLAIN ? 1 : K;
+    if (rows < used + 1 || rows > 256) TMIX_FAIL(TMIX_ESHAPE, "%s: mode %d needs %d..256 eps rows per seed, got %d", me, mode, used + 1, rows);
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        return launch_apg<dt()>(x, eps, coeffs, ws, (int64_t)channels * hw, rows, used, seeds, params, g_slot, eta, norm_threshold, (hipStream_t)stream);
+    });
+}
 
 extern "C" int64_t tmix_cfg_rescale_ws_doubles(int rows, int seeds) {
     if (rows < 2 || rows > 256 || seeds < 1 || seeds > 65535) return 0;

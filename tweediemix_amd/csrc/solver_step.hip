@@ -6,9 +6,11 @@
 // The image sampler's kernel and entries only: the same move on the video sampler's v-prediction is video_step.hip's.
 // The stochastic step (tmix_fused_tweedie_step_noise_dev) is this kernel with a trailing NoiseArgs: the move of either solver plus
 // cz * z, z from noise.h.  The unguided step (tmix_fused_tweedie_step_cond_dev) is this kernel with a trailing CondArgs: eps rows
-// without the unconditional one, each used as it is, and a DDIM move on the eps consistent with the blended estimate.
+// without the unconditional one, each used as it is, and a DDIM move on the eps consistent with the blended estimate.  The APG step
+// (tmix_fused_tweedie_step_apg_dev) is this kernel with a trailing ApgArgs: every row's estimate is A tc + B (tc - tu).
 #include "step_core.h"
 #include "noise.h"
+#include "../../include/tmix_apg.h"
 
 namespace {
 
@@ -32,6 +34,8 @@ template <typename A, typename T0, typename... T> __device__ __forceinline__ con
 // every array is read at i before it is written at i.  x0_prev is read AND written, so it carries no __restrict__.
 // RESCALE: the presence of a trailing RescaleArgs kernel argument (step_core.h; tweedie_step.hip's KeepArgs mechanism); without a trailing
 // argument the kernel has the arguments it had before.
+// APG (step_core.h's ApgArgs and blended_x0_apg): the rows' estimates are combined in data space with the {A, B} pairs of tmix_apg_coeffs; g is
+// not read.  Like NOISE and COND it may come without a history buffer, and then has a RESAMPLE form too.
 // NOISE (above) alone may come without a history buffer: x0_prev == nullptr selects the DDIM entry's params layout {t, sa, s1, sa_next, s1_next,
 // is_last, g, -} and its move sa_next x0 + rnd(s1_next eu), formed as tweedie_step.hip forms it.
 template <int DT, int MODE, typename... ExT>
@@ -40,11 +44,13 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
                    float* __restrict__ out_x0, float* x0_prev, int K, int64_t n, int64_t hw, const float* __restrict__ prm, int rows,
                    int64_t mask_seed_stride, ExT... ex) {
     constexpr bool RS = pack_has<RescaleArgs, ExT...>, NZ = pack_has<NoiseArgs, ExT...>, COND = pack_has<CondArgs, ExT...>;
-    static_assert(sizeof...(ExT) == (RS ? 1 : 0) + (NZ ? 1 : 0) + (COND ? 1 : 0) && !(RS && COND),
-                  "the trailing arguments are a RescaleArgs, a NoiseArgs or both, or a CondArgs behind an optional NoiseArgs");
+    constexpr bool APG = pack_has<ApgArgs, ExT...>;
+    static_assert(sizeof...(ExT) == (RS ? 1 : 0) + (NZ ? 1 : 0) + (COND ? 1 : 0) + (APG ? 1 : 0) && !(RS && COND) && !(APG && (RS || COND)),
+                  "the trailing arguments are a RescaleArgs, a NoiseArgs or both, a CondArgs behind an optional NoiseArgs, or an ApgArgs in front of an optional NoiseArgs");
     const float* fac = nullptr;
     if constexpr (RS) fac = pack_get<RescaleArgs>(ex...).fac + (int64_t)blockIdx.y * (rows - 1);
-    const bool ddim = (NZ || COND) && !x0_prev;
+    if constexpr (APG) fac = pack_get<ApgArgs>(ex...).ab + (int64_t)blockIdx.y * (rows - 1) * 2;      // the seed's {A, B} pairs
+    const bool ddim = (NZ || COND || APG) && !x0_prev;
     const float sa = prm[1], s1 = prm[2], cx = prm[3], c0 = prm[4], c1 = prm[5], g = prm[ddim ? 6 : 7];
     const bool is_last = prm[ddim ? 5 : 6] != 0.0f;
     const int64_t sd = blockIdx.y;
@@ -70,7 +76,9 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
         const float p = ddim ? 0.0f : x0_prev[i];
         float eu = 0.0f;
         if constexpr (!COND) eu = EpsT<DT>::ld(eps, i);
-        const float x0 = blended_x0<DT, MODE, RS, COND>(eps, masks, fac, K, n, hw, i, xv, eu, g, sa, s1);
+        float x0;
+        if constexpr (APG) x0 = blended_x0_apg<DT, MODE>(eps, masks, fac, K, n, hw, i, xv, eu, sa, s1);
+        else x0 = blended_x0<DT, MODE, RS, COND>(eps, masks, fac, K, n, hw, i, xv, eu, g, sa, s1);
         float moved;
         if (ddim) {                                  // prm[3], prm[4] hold sa_next, s1_next
             if constexpr (COND) eu = s1 != 0.0f ? (xv - sa * x0) / s1 : 0.0f;       // e0: the eps consistent with x0 stands in for the missing row
@@ -94,13 +102,21 @@ solver_step_kernel(const float* x, const typename EpsT<DT>::T* __restrict__ eps,
     }
 }
 
-template <int DT, typename... RsT>      // RsT: the kernel's trailing arguments -- none, {RescaleArgs}, {NoiseArgs}, {RescaleArgs, NoiseArgs}, {CondArgs} or {NoiseArgs, CondArgs}
+template <int DT, typename... RsT>      // RsT: the kernel's trailing arguments -- none, {RescaleArgs}, {NoiseArgs}, {RescaleArgs, NoiseArgs}, {CondArgs}, {NoiseArgs, CondArgs},
+                                        // {ApgArgs} or {ApgArgs, NoiseArgs}
 int launch_ms(const float* x, const void* eps, const float* masks, int64_t mss, float* out_x, float* out_x0, float* x0_prev, int K, int64_t n,
               int64_t hw, int mode, int rows, int seeds, const float* prm, hipStream_t st, RsT... rs) {
     typedef typename EpsT<DT>::T T;
     int64_t bx = (n + 255) / 256; if (bx > 2048) bx = 2048;
     const dim3 grid((unsigned)bx, (unsigned)seeds);
     const T* e = (const T*)eps;
+    if constexpr (pack_has<ApgArgs, RsT...> && !pack_has<NoiseArgs, RsT...>) {      // the APG entry alone has a RESAMPLE form (its DDIM layout, no noise)
+        if (mode == TMIX_STEP_RESAMPLE) {
+            solver_step_kernel<DT, TMIX_STEP_RESAMPLE, RsT...><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss, rs...);
+            TMIX_LAUNCH_CHECK();
+            return TMIX_OK;
+        }
+    }
     if (mode == TMIX_STEP_FUSION)
         solver_step_kernel<DT, TMIX_STEP_FUSION, RsT...><<<grid, 256, 0, st>>>(x, e, masks, out_x, out_x0, x0_prev, K, n, hw, prm, rows, mss, rs...);
     else
@@ -204,5 +220,27 @@ extern "C" int tmix_fused_tweedie_step_cond_dev(const float* x, const void* eps,
     return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
         if (keys) return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, nz, CondArgs());
         return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, CondArgs());
+    });
+}
+
+// The APG step: every conditional row's Tweedie estimate becomes A tc + B (tc - tu), {A, B} = coeffs[seed][row - 1] (tmix_apg_coeffs),
+// in all three modes; everything behind it -- the blend, the move (the DDIM move's noise term stays the unconditional row), the noise -- is the
+// parent's.  x0_prev NULL: the DDIM params layout and move (FUSION, PLAIN, RESAMPLE); else the multistep layout and move (FUSION, PLAIN).
+// keys NULL: no noise (8 floats, the window arguments are not read); else the noise entry's 12 floats and canvas indexing (FUSION, PLAIN).
+extern "C" int tmix_fused_tweedie_step_apg_dev(const float* x, const void* eps, int eps_dtype, const float* masks, int64_t mask_seed_stride,
+                                               float* out_x, float* out_x0, int K, int channels, int64_t hw, int mode, int rows, int seeds,
+                                               const float* params, float* x0_prev, const float* coeffs, const uint32_t* keys, int w, int n_win,
+                                               const int* win_yx, int canvas_h, int canvas_w, void* stream) {
+    const char* me = "tweedie_step_apg_dev";
+    if (int rc = check_dev_step(me, true, false, x, eps, out_x, params, nullptr, coeffs ? nullptr : "null coeffs", masks, K, channels, hw, mode, rows, seeds)) return rc;
+    if (mode == TMIX_STEP_RESAMPLE && (x0_prev || keys))
+        TMIX_FAIL(TMIX_EINVAL, "%s: RESAMPLE exists on the DDIM move without noise only (x0_prev and keys must be null)", me);
+    NoiseArgs nz;
+    if (keys) if (int rc = make_noise_args(me, nz, keys, hw, seeds, w, n_win, win_yx, canvas_h, canvas_w)) return rc;
+    const int64_t n = (int64_t)channels * hw;
+    const ApgArgs ap = {coeffs};
+    return for_dtype(eps_dtype, me, "eps dtype", [&](auto dt) {
+        if (keys) return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, ap, nz);
+        return launch_ms<dt()>(x, eps, masks, mask_seed_stride, out_x, out_x0, x0_prev, K, n, hw, mode, rows, seeds, params, (hipStream_t)stream, ap);
     });
 }

@@ -84,6 +84,45 @@ __device__ __forceinline__ float blended_x0(const typename EpsT<DT>::T* eps, con
     return x0;
 }
 
+// APG (adaptive projected guidance, arXiv:2410.02416): guidance formed on the rows' Tweedie estimates.  With tc / tu the conditional /
+// unconditional estimate of a row's element and d = tc - tu, the row's estimate is t_r = A_r tc + B_r d, {A_r, B_r} = ab[2 (r - 1)], ab[2 (r - 1) + 1]
+// (layout [seeds][rows - 1][2]; tmix_apg_coeffs writes it from the row's sums of d d, d tc and tc tc).  {1, g - 1} is plain CFG in data space.
+// The flag is the presence of ONE trailing ApgArgs kernel argument (in front of a NoiseArgs; never with a RescaleArgs or a CondArgs).
+struct ApgArgs { const float* ab; };
+struct ApgTerm { float tc, d; };
+// tu, once per element, and {tc, d} of one conditional row: the operations of blended_x0's t on the row's own prediction.  The ONE definition of
+// what the statistics (cfg_rescale.hip) sum and the step kernel combines.
+template <int DT> __device__ __forceinline__ float apg_tu(float xv, float eu, float sa, float s1) { return (xv - rnd<DT>(s1 * eu)) / sa; }
+template <int DT> __device__ __forceinline__ ApgTerm apg_term(float xv, float tu, float ec, float sa, float s1) {
+    const float tc = (xv - rnd<DT>(s1 * ec)) / sa;
+    return {tc, tc - tu};
+}
+__device__ __forceinline__ float apg_row(const ApgTerm& t, const float* ab) { return ab[0] * t.tc + ab[1] * t.d; }     // two products, one sum
+
+// blended_x0 with t_r in the place of every row's t: the same blend (FUSION), row (PLAIN) or (K-1) t_1 - sum_{c<K-1} t_{2+c} (RESAMPLE) behind it.
+// ab is the seed's own; g is not read here (it is inside B).
+template <int DT, int MODE>
+__device__ __forceinline__ float blended_x0_apg(const typename EpsT<DT>::T* eps, const float* masks, const float* ab, int K, int64_t n, int64_t hw,
+                                                int64_t i, float xv, float eu, float sa, float s1) {
+    const float tu = apg_tu<DT>(xv, eu, sa, s1);
+    float x0;
+    if constexpr (MODE == TMIX_STEP_FUSION) {
+        const int64_t p = i % hw;
+        x0 = 0.0f;
+        for (int c = 0; c < K; ++c) {
+            const float t = apg_row(apg_term<DT>(xv, tu, EpsT<DT>::ld(eps, (int64_t)(1 + c) * n + i), sa, s1), ab + 2 * c);
+            x0 = x0 + masks[(int64_t)c * hw + p] * t;
+        }
+    } else if constexpr (MODE == TMIX_STEP_PLAIN) {
+        x0 = apg_row(apg_term<DT>(xv, tu, EpsT<DT>::ld(eps, n + i), sa, s1), ab);
+    } else {
+        x0 = (float)(K - 1) * apg_row(apg_term<DT>(xv, tu, EpsT<DT>::ld(eps, n + i), sa, s1), ab);
+        for (int c = 0; c < K - 1; ++c)
+            x0 = x0 - apg_row(apg_term<DT>(xv, tu, EpsT<DT>::ld(eps, (int64_t)(2 + c) * n + i), sa, s1), ab + 2 * (1 + c));
+    }
+    return x0;
+}
+
 // ---- video sampler (I2VGen-XL loop): video_gen/pipeline_i2vgen_xl.py:699-719.  Latents and predictions share the model dtype in that loop, so in
 // fp16 mode EVERY binary op rounds (rnd<DT>).
 // one element's guided v-prediction and the x0 it gives: what the DDIM and the multistep video kernels have in common.  RS: the guided prediction

@@ -17,6 +17,9 @@ rescaled prediction into x0 AND into the move's eps term.
 The guidance interval (between the two halves) is the other host-side definition about guidance kept here: which timesteps are
 guided, and the restatement of the step that runs without the unconditional row (tmix_fused_tweedie_step_cond_dev).  The video sampler's unguided
 step (tmix_vpred_step_cond / tmix_vpred_step_cond_dev) is restated in the second half, vpred_cond_step_reference.
+
+Adaptive projected guidance (behind the interval) is the third: the setting's check, the coefficients tmix_apg_coeffs writes and the
+step tmix_fused_tweedie_step_apg_dev takes, restated in numpy (apg_coeffs_reference, apg_step_reference, apg_multistep_reference).
 """
 from __future__ import annotations
 
@@ -202,6 +205,149 @@ def cond_step_reference(mode, x, eps, masks, x0_prev, params, key=None, index=No
         z = NZ.normal(idx, key[0], key[1], int(p[9]))
         moved = (moved + (p[8] * z).astype(F32)).astype(F32)
     return moved, x0
+
+
+# ------------------------------------------------------------------------------------------------ adaptive projected guidance
+# Sadat, Hilliges and Weber 2024 (arXiv:2410.02416): guidance on the denoised prediction.  Per conditional row r, with tc / tu the row's conditional
+# and the unconditional Tweedie estimate and d = tc - tu, the update d is split into its part parallel to tc and the rest; the parallel part (the one
+# that inflates contrast and saturation) is scaled by eta, the whole update's norm is clipped at R (0: no clip):
+#     s = R > 0 and Sdd > R^2 ? R / sqrt(Sdd) : 1,   p = Scc > 0 ? s Sdc / Scc : 0,   A = 1 - (g-1)(1-eta) p,   B = (g-1) s,   t_r = A tc + B d
+# which is D_c + (g-1)(D_orth + eta D_par) of the clipped update s d.  t_r takes the place of the row's estimate in the blend; the move behind it is
+# the parent's (the DDIM move's noise term stays the unconditional row).  OUR choices: {A, B} = {1, g-1} -- CFG in data space -- where a sum is not
+# finite, and for rows the mode does not read.  Momentum (the paper's beta) is not implemented.
+def validate_apg(apg, what="apg"):
+    """the ONE check of the APG setting (constructor, CLI, wrappers): None / False (off), True (the defaults) or a dict with eta in [0, 1]
+    (default 0.0: the parallel part is dropped; 1.0: CFG) and norm_threshold >= 0 (default 0.0: no clip), both finite -> None or
+    dict(eta=float, norm_threshold=float)"""
+    if apg is None or apg is False:
+        return None
+    if apg is True:
+        apg = {}
+    bad = ValueError(f"{what}={apg!r}: None or dict(eta=<0..1, the weight of the update's part parallel to the conditional estimate>, "
+                     f"norm_threshold=<finite, >= 0: the clip of the update's norm, 0 = none>)")
+    if not isinstance(apg, dict) or set(apg) - {"eta", "norm_threshold"}:
+        raise bad
+    out = {}
+    for k in ("eta", "norm_threshold"):
+        v = apg.get(k, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not math.isfinite(float(v)) or float(v) < 0.0:
+            raise bad
+        out[k] = float(v)
+    with np.errstate(over="ignore"):
+        if out["eta"] > 1.0 or not math.isfinite(float(F32(out["norm_threshold"]))):     # the kernel takes both as fp32
+            raise bad
+    return out
+
+
+def _apg_terms(x, eps, sa, s1, lowp):
+    """(tc [rows-1, ...], d [rows-1, ...]) in fp32 with the kernel's rounding points: tc = (x - rnd(s1 ec)) / sa, tu likewise, d = tc - tu"""
+    x, eps = np.asarray(x, F32), np.asarray(eps, F32)
+    x = x.reshape((1,) + eps.shape[1:])
+    with np.errstate(all="ignore"):
+        tu = SV._tweedie(x, eps[:1], sa, s1, lowp)
+        tc = SV._tweedie(x, eps[1:], sa, s1, lowp)
+        return tc, (tc - tu).astype(F32)
+
+
+def apg_sums_reference(x, eps, sa, s1, lowp=None):
+    """[rows-1, 3] fp64 = (Sdd, Sdc, Scc) per conditional row of ONE seed: the fp32 terms of the kernel, products and sums in fp64"""
+    tc, d = _apg_terms(x, eps, sa, s1, lowp)
+    c64, d64 = tc.astype(np.float64).reshape(tc.shape[0], -1), d.astype(np.float64).reshape(d.shape[0], -1)
+    with np.errstate(all="ignore"):
+        return np.stack([(d64 * d64).sum(1), (d64 * c64).sum(1), (c64 * c64).sum(1)], axis=1)
+
+
+def apg_finalise(sums, g, eta, norm_threshold):
+    """(A, B, s) as python floats (fp64) from one row's (Sdd, Sdc, Scc): the kernel's operations in the kernel's order, from the fp32 values of g,
+    eta and norm_threshold; (1, g-1, 1) where a sum is not finite"""
+    dd, dc, cc = (float(v) for v in sums)
+    gm1 = float(F32(g)) - 1.0
+    if not (math.isfinite(dd) and math.isfinite(dc) and math.isfinite(cc)):
+        return 1.0, gm1, 1.0
+    R = float(F32(norm_threshold))
+    s = R / math.sqrt(dd) if (R > 0.0 and dd > R * R) else 1.0
+    p = s * dc / cc if cc > 0.0 else 0.0
+    return 1.0 - gm1 * (1.0 - float(F32(eta))) * p, gm1 * s, s
+
+
+def apg_coeffs_reference(mode, x, eps, K, g, sa, s1, eta, norm_threshold, lowp=None):
+    """coeffs [rows-1, 2] fp32 = {A, B} of ONE seed's x [1, C, h, w] and eps [rows, C, h, w] (fp32 copies of values of the eps dtype): what
+    tmix_apg_coeffs writes, up to the order of the fp64 sums.  d and tc in fp32 as the kernel forms them, sums in fp64, the coefficients in fp64
+    and rounded once; {1, g-1} where a sum is not finite and for the rows the mode does not read."""
+    eps = np.asarray(eps, F32)
+    used = rows_read(mode, K)
+    if eps.shape[0] < used + 1:
+        raise ValueError(f"apg: mode {mode} needs {used + 1} eps rows, got {eps.shape[0]}")
+    a = validate_apg(dict(eta=eta, norm_threshold=norm_threshold), "apg")
+    sums = apg_sums_reference(x, eps, F32(sa), F32(s1), lowp)
+    out = np.empty((eps.shape[0] - 1, 2), F32)
+    out[:, 0], out[:, 1] = 1.0, F32(float(F32(g)) - 1.0)
+    for r in range(used):
+        A, B, _s = apg_finalise(sums[r], g, a["eta"], a["norm_threshold"])
+        out[r] = F32(A), F32(B)
+    return out
+
+
+def apg_x0_reference(mode, x, eps, masks, K, coeffs, sa, s1, lowp=None):
+    """the blended estimate of the APG step, the kernel's operations in the kernel's order: t_r = A_r tc + B_r d (two products, one sum), then the
+    mask blend (FUSION), row 1 (PLAIN) or (K-1) t_1 - sum_{c<K-1} t_{2+c} (RESAMPLE).  x [1, C, h, w]; coeffs [rows-1, 2]"""
+    tc, d = _apg_terms(x, eps, F32(sa), F32(s1), lowp)
+    ab = np.asarray(coeffs, F32).reshape(-1, 2)
+    with np.errstate(all="ignore"):
+        t = lambda r: ((ab[r, 0] * tc[r:r + 1]).astype(F32) + (ab[r, 1] * d[r:r + 1]).astype(F32)).astype(F32)
+        if mode == STEP_PLAIN:
+            return t(0)
+        if mode == STEP_FUSION:
+            masks = np.asarray(masks, F32)
+            x0 = np.zeros_like(t(0))
+            for c in range(masks.shape[0]):
+                x0 = (x0 + (masks[c][None] * t(c)).astype(F32)).astype(F32)
+            return x0
+        if mode != STEP_RESAMPLE:
+            raise ValueError(f"apg: mode {mode}")
+        x0 = (F32(K - 1) * t(0)).astype(F32)
+        for c in range(K - 1):
+            x0 = (x0 - t(1 + c)).astype(F32)
+        return x0
+
+
+def _apg_noise(moved, p, key, index):
+    if key is None or p[8] == 0:
+        return moved
+    from . import noise as NZ
+    idx = np.arange(moved.size, dtype=np.uint64).reshape(moved.shape) if index is None else np.asarray(index, np.uint64).reshape(moved.shape)
+    return (moved + (p[8] * NZ.normal(idx, key[0], key[1], int(p[9]))).astype(F32)).astype(F32)
+
+
+def apg_step_reference(mode, x, eps, masks, K, coeffs, params, key=None, index=None, lowp=None):
+    """numpy fp32 restatement of tmix_fused_tweedie_step_apg_dev WITHOUT a history buffer, for one row -> (out_x, x0).  params: the floats the
+    entry reads, {t, sa, s1, sa_next, s1_next, is_last, g, -} and with key = (low word, high word) four more, {cz, step index, 0, 0}; index: the
+    canvas index of every element, None = its own linear index.  The DDIM move's noise term is the unconditional row.  Compared by equality."""
+    x, eps = np.asarray(x, F32), np.asarray(eps, F32)
+    p = [F32(v) for v in params]
+    x0 = apg_x0_reference(mode, x, eps, masks, K, coeffs, p[1], p[2], lowp)
+    if p[5] != 0:
+        return x0, x0
+    with np.errstate(all="ignore"):
+        moved = ((p[3] * x0).astype(F32) + SV._h((p[4] * eps[:1]).astype(F32), lowp)).astype(F32)
+    return _apg_noise(moved, p, key, index), x0
+
+
+def apg_multistep_reference(mode, x, eps, masks, x0_prev, coeffs, params, key=None, index=None, lowp=None):
+    """numpy fp32 restatement of tmix_fused_tweedie_step_apg_dev WITH the history buffer x0_prev, for one row -> (out_x, x0); x0 is also the new
+    history.  params {t, sa, s1, cx, c0, c1, is_last, g} (+ {cz, step index, 0, 0} with key).  x0_prev is used only when c1 != 0."""
+    x = np.asarray(x, F32)
+    p = [F32(v) for v in params]
+    K = 1 if mode == STEP_PLAIN else np.asarray(masks).shape[0]
+    x0 = apg_x0_reference(mode, x, eps, masks, K, coeffs, p[1], p[2], lowp)
+    if p[6] != 0:
+        return x0, x0
+    with np.errstate(all="ignore"):
+        m = (p[4] * x0).astype(F32)
+        if p[5] != 0:
+            m = (m + (p[5] * np.asarray(x0_prev, F32)).astype(F32)).astype(F32)
+        moved = ((p[3] * x).astype(F32) + m).astype(F32)
+    return _apg_noise(moved, p, key, index), x0
 
 
 # ------------------------------------------------------------------------------------------------ video sampler (v-prediction; DESIGN.md 7m)

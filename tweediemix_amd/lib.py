@@ -162,6 +162,17 @@ SIGNATURES = {
                                        C.c_int, C.c_int, f32, f32, vp]),
 }
 
+# The extension entries of include/tmix_apg.h (include/tmix.h and SIGNATURES above hold the library's 87 entry points and stay as they are): bound
+# by load() like them.
+SIGNATURES_APG = {
+    # adaptive projected guidance (arXiv:2410.02416).  Per conditional row r, with tc / tu the row's conditional / the unconditional
+    # Tweedie estimate and d = tc - tu: t_r = A_r tc + B_r d replaces the row's estimate in the blend of all three modes.  tmix_apg_coeffs writes
+    # {A, B} [seeds][rows-1][2] from Sdd, Sdc, Scc (fp64 sums of the fp32 terms): s = R > 0 and Sdd > R^2 ? R / sqrt(Sdd) : 1, p = Scc > 0 ?
+    # s Sdc / Scc : 0, A = 1 - (g-1)(1-eta) p, B = (g-1) s; {1, g-1} where a sum is not finite and for rows the mode does not read.
+    "tmix_apg_coeffs": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, f32, vp]),
+    "tmix_fused_tweedie_step_apg_dev": (C.c_int, _DEV_STEP + [vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, vp]),
+}
+
 _lib = None
 
 
@@ -181,7 +192,7 @@ def load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} not found: build it first (python -c 'import __graft_entry__ as g; g.build()' "
                           f"or make -C tweediemix_amd/csrc). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_APG.items()):
         fn = getattr(lib, name)          # AttributeError if the ABI and the header diverge
         fn.restype = res
         fn.argtypes = args

@@ -212,6 +212,54 @@ def fused_tweedie_step_cond_dev(x, eps, masks, mode, K, params, x0_prev=None, ke
     return out_x
 
 
+def apg_coeffs(x, eps, mode, K, params, g_slot, eta=0.0, norm_threshold=0.0, out=None, ws=None):
+    """tmix_apg_coeffs, adaptive projected guidance (arXiv:2410.02416): x [S,C,h,w] fp32 the state the step will read, eps
+    [S*rows,C,h,w] f32|f16|bf16, params the step's device buffer (>= 8 floats: sa, s1 in slots 1, 2; g in slot g_slot -- 6: the DDIM layout, 7:
+    the multistep layout) -> coeffs [S, rows-1, 2] fp32 = {A, B} per conditional row (guidance.apg_coeffs_reference per seed): with d = tc - tu
+    of the rows' Tweedie estimates, s = R > 0 and Sdd > R^2 ? R / sqrt(Sdd) : 1, p = Scc > 0 ? s Sdc / Scc : 0, A = 1 - (g-1)(1-eta) p,
+    B = (g-1) s; {1, g-1} where a sum is not finite and for rows the mode does not read.  ws: cfg_rescale_ws(rows, S)."""
+    from .guidance import validate_apg
+    a = validate_apg(dict(eta=eta, norm_threshold=norm_threshold), "apg_coeffs")
+    _need_cuda(x, eps, params, out, ws)
+    S = x.shape[0]
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and eps.is_contiguous() and eps.dim() == 4 and eps.shape[0] % S == 0
+    assert tuple(eps.shape[1:]) == tuple(x.shape[1:]) and params.dtype == torch.float32 and params.numel() >= 8
+    rows = eps.shape[0] // S
+    Cc, h, w = eps.shape[1:]
+    if out is None:
+        out = torch.empty(S, rows - 1, 2, device=eps.device, dtype=torch.float32)
+    if ws is None:
+        ws = cfg_rescale_ws(rows, S, eps.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == S * (rows - 1) * 2, tuple(out.shape)
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= L.load().tmix_cfg_rescale_ws_doubles(rows, S)
+    L.check(L.load().tmix_apg_coeffs(_p(x), _p(eps), _EPS_DT[eps.dtype], _p(out), _p(ws), K, Cc, h * w, mode, rows, S, _p(params), int(g_slot),
+                                     a["eta"], a["norm_threshold"], _stream()), "tmix_apg_coeffs")
+    return out
+
+
+def fused_tweedie_step_apg_dev(x, eps, masks, mode, K, params, coeffs, x0_prev=None, keys=None, windows=None, canvas_hw=None, out_x=None,
+                               out_x0=None):
+    """tmix_fused_tweedie_step_apg_dev, the APG step: every conditional row's Tweedie estimate is A tc + B (tc - tu) with {A, B} =
+    coeffs [S, rows-1, 2] (apg_coeffs); the blend, the move and the noise behind it are the parent's.  x0_prev None: params {t, sa, s1, sa_next,
+    s1_next, is_last, g, -} and the DDIM move (FUSION, PLAIN, RESAMPLE); else the history buffer and {t, sa, s1, cx, c0, c1, is_last, g} (FUSION,
+    PLAIN).  keys None: no noise; else int32 [S / n_win, 2] (noise_keys), params holds 12 floats and windows / canvas_hw are
+    fused_tweedie_step_noise_dev's.  guidance.apg_step_reference / apg_multistep_reference give the same bits.  out_x may be x itself."""
+    _need_cuda(x, eps, masks, params, coeffs, keys, x0_prev)
+    S, _n, _hw, rows, out_x, head = _dev_step_head(x, eps, masks, mode, K, params, out_x, out_x0, x0_prev)
+    assert coeffs.dtype == torch.float32 and coeffs.is_contiguous() and coeffs.numel() == S * (rows - 1) * 2, tuple(coeffs.shape)
+    n_win = 1 if windows is None else len(windows)
+    if keys is not None:
+        assert params.numel() >= 12, params.numel()
+        assert keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() == 2 * (S // n_win) and S % n_win == 0, (tuple(keys.shape), S, n_win)
+    yx, ch, cw = None, 0, 0
+    if windows is not None:
+        yx = (C.c_int32 * (2 * n_win))(*[int(v) for o in windows for v in o])
+        ch, cw = int(canvas_hw[0]), int(canvas_hw[1])
+    L.check(L.load().tmix_fused_tweedie_step_apg_dev(*head, _p(x0_prev), _p(coeffs), _p(keys), x.shape[-1], n_win, yx, ch, cw, _stream()),
+            "tmix_fused_tweedie_step_apg_dev")
+    return out_x
+
+
 def window_consensus(x, groups, offsets, canvas_hw, weight=None):
     """tmix_window_consensus, in place on x [groups * n_win, C, h, w] fp32 (group-major: b = group * n_win + window): every canvas pixel
     that several windows cover becomes their weighted mean in all of them.  offsets [(oy, ox), ...] the windows' corners on the canvas

@@ -39,7 +39,7 @@ import torch
 from . import lib as L
 from . import ops
 from .schedule import Schedule
-from .guidance import is_guided, validate_interval, validate_phi
+from .guidance import is_guided, validate_apg, validate_interval, validate_phi
 from .plan import ParamRing
 from .solver import SOLVERS, ddim_eta_coeffs, multistep_coeffs, multistep_eta_coeffs, validate_eta
 from .unet import KVCache, PlanGroup, TokenMapSpec, TokenPropSpec, UNetPlan, UNetWeights
@@ -139,7 +139,17 @@ class Tweediemix:
                       second order only when the step before had the same guidedness.  The whole first timestep, the look-ahead, the probe and
                       the propagate rounds stay guided.  An interval that holds every timestep of the schedule is None's run bit for bit.  Not
                       with set_keep.  DESIGN.md 7q.
-    noise_seeds       one integer (a 64-bit seed value) per trajectory the caller sees; set_noise_seeds replaces them between runs.  A
+    apg               None (off: today's entries, plan kinds, launches, graph keys, uploads and bits), or dict(eta=0.0, norm_threshold=0.0):
+                      adaptive projected guidance (arXiv:2410.02416).  Every GUIDED step of every phase -- start, resampling, look-ahead,
+                      probe, propagate, plain and fusion, DDIM and solver entries, with or without `eta`, eager, captured and with a stand-in
+                      UNet -- forms its guidance on the rows' Tweedie estimates: the update tc - tu is split into the part parallel to the
+                      conditional estimate tc, which is scaled by apg["eta"] (0 drops it, 1 is CFG), and the rest, which is kept; its norm is
+                      clipped at apg["norm_threshold"] (0: no clip).  tmix_apg_coeffs (two small launches on the state and the eps rows the
+                      plan has just written) and then tmix_fused_tweedie_step_apg_dev in place of the step, in the same captured graph (keys
+                      get a trailing "apg"); both settings are launch arguments fixed at capture, the upload stays 32 or 48 bytes.  Unguided
+                      steps (guidance_interval) launch neither.  Statistics are per UNet row: on a canvas per window.  Not with
+                      guidance_rescale > 0, not with set_keep.  No momentum.  DESIGN.md 7s.
+    noise_seeds      one integer (a 64-bit seed value) per trajectory the caller sees; set_noise_seeds replaces them between runs.  A
                       trajectory's noise depends on its own seed alone: not on what it is co-batched with, the GPU, graphs or windows.
     """
 
@@ -147,10 +157,14 @@ class Tweediemix:
                  concept_num: int, lora: bool = False, strict_reference: bool = True, use_graphs: bool = False,
                  n_seeds: int = 1, n_streams: int = 1, vae=None, fp8: bool = False, attention_masks=None, canvas=None,
                  mask_soften=None, solver: str = "ddim", timestep_spacing: str = "leading", guidance_rescale: float = 0.0,
-                 eta: float = 0.0, noise_seeds=None, guidance_interval=None):
+                 eta: float = 0.0, noise_seeds=None, guidance_interval=None, apg=None):
         self.config = config
         self.guidance_interval = validate_interval(guidance_interval)
         self.guidance_rescale = validate_phi(guidance_rescale)
+        self.apg = validate_apg(apg)
+        if self.apg is not None and self.guidance_rescale > 0.0:     # both re-shape the same prediction and no order between them is defined
+            raise ValueError(f"apg={self.apg}: not with guidance_rescale={self.guidance_rescale} (both re-shape the guided prediction; no order "
+                             f"between them is defined)")
         self.eta = validate_eta(eta)
         if self.eta > 0.0 and noise_seeds is None:
             raise ValueError(f"eta={self.eta}: noise_seeds (one integer per trajectory) are what the step's noise is a function of")
@@ -259,7 +273,13 @@ class Tweediemix:
         if self.guidance_rescale > 0.0:
             self._rs_factors = torch.ones(S * (self._rs_rows - 1), device=self.device, dtype=F32)
             self._rs_ws = ops.cfg_rescale_ws(self._rs_rows, S, self.device)
-        self._keep = self._keep_bufs = None    # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
+        # apg: the {A, B} pairs [seeds][rows - 1][2] of the step being run and the fp64 workspace of their reduction, sized and kept like the
+        # rescale's (which never exists at the same time)
+        self._apg_coeffs = self._apg_ws = None
+        if self.apg is not None:
+            self._apg_coeffs = torch.ones(S * (self._rs_rows - 1) * 2, device=self.device, dtype=F32)
+            self._apg_ws = ops.cfg_rescale_ws(self._rs_rows, S, self.device)
+        self._keep = self._keep_bufs = None   # keep region (set_keep): (x0, weight, eps) in buffers of fixed address; _keep is None while none is set
         self._ring = ParamRing(cuda=self.device.type == "cuda", width=self._n_params)     # staging for the asynchronous upload of step_params
         self._mask_buf = None            # fixed-address copy of self.masks that the captured fusion step reads
 
@@ -333,6 +353,8 @@ class Tweediemix:
             raise ValueError(f"set_keep: not with eta={self.eta} (the keep region exists on the deterministic step only)")
         if self.guidance_rescale > 0.0:  # a keep entry that takes factors does not exist (yet)
             raise ValueError(f"set_keep: not with guidance_rescale={self.guidance_rescale} (the keep region exists on the unscaled step only)")
+        if self.apg is not None:         # the keep entry has no APG form
+            raise ValueError(f"set_keep: not with apg={self.apg} (the keep region exists on the step without adaptive projected guidance only)")
         if self.solver != "ddim":        # the keep term needs sa_next / s1_next, which the multistep entry's eight floats do not carry
             raise ValueError(f"set_keep: not with solver={self.solver!r} (the keep region exists on the solver='ddim' step only)")
         if self.windows is not None:     # the mean of equal values is not always that value bit for bit: the kept region's promise would break
@@ -499,6 +521,19 @@ class Tweediemix:
                                                          self.w, 1 if yx is None else len(self.windows), yx, self.canvas_h, self.canvas_w, st),
                     "tmix_fused_tweedie_step_cond_dev")
             return
+        if self.apg is not None:         # the {A, B} pairs of these eps rows and this state (g, sa, s1 read on the device), then the one APG entry
+            if rows > self._rs_rows:
+                raise ValueError(f"apg: {rows} eps rows per seed, the buffers were sized for {self._rs_rows}")
+            L.check(lib.tmix_apg_coeffs(self.x_state.data_ptr(), eps_ptr, eps_dt, self._apg_coeffs.data_ptr(), self._apg_ws.data_ptr(),
+                                        self.concept_num, 4, hw, mode, rows, self.n_seeds, self.step_params.data_ptr(), 7 if ms else 6,
+                                        self.apg["eta"], self.apg["norm_threshold"], st), "tmix_apg_coeffs")
+            yx = None
+            if nz and self.windows is not None:
+                yx = (C.c_int32 * (2 * len(self.windows)))(*[int(v) for o in self.windows for v in o])
+            L.check(lib.tmix_fused_tweedie_step_apg_dev(*head, self._x0_prev.data_ptr() if ms else None, self._apg_coeffs.data_ptr(),
+                                                        self._noise_keys.data_ptr() if nz else None, self.w, 1 if yx is None else len(self.windows),
+                                                        yx, self.canvas_h, self.canvas_w, st), "tmix_fused_tweedie_step_apg_dev")
+            return
         if self.guidance_rescale > 0.0:  # the factors of these eps rows (g read on the device from the layout the step uploaded), then the rs form of the step
             if rows > self._rs_rows:
                 raise ValueError(f"guidance_rescale: {rows} eps rows per seed, the buffers were sized for {self._rs_rows}")
@@ -575,6 +610,8 @@ class Tweediemix:
             gkey = gkey + ("rs",)
         if nz:                                            # another entry, two more pointers and the window table: graphs of their own
             gkey = gkey + ("eta",)
+        if self.apg is not None and not cond:             # two more launches and the APG entry (eta and R are launch arguments fixed at capture)
+            gkey = gkey + ("apg",)
         g = self.graphs.get(gkey)
         if g is None:
             self._enqueue_step(kind, mode, ms is not None, **nzk)    # warm-up outside capture (kernel attributes, lazy module load);
